@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: Arnoldi steps (time-stepper matvec + orthogonalisation) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--case cfg2|cfg3]
+    python bench.py --gpus N --steps K --warmup W [--case cfg2|cfg3] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step (--dump-outputs) and prints
+the record: the headline figure and nothing else.  `--full` adds everything else the record can carry: the continuation
+to k_dim = 128 and the leading Ritz pair, the byte accounting and the kernel rooflines, the CPU baseline, the Fortran-host
+leg, and at N > 1 the same steps on one GPU and the short sharded run of cfg3 (`--extras` and `--ref-logfile` imply it).
+A plain run at N > 1 over RCCL still does, before its timed steps, what picks the configuration it times: the RCCL pre-flight
+(tests/mp_rccl_worker.py in fresh processes, see supervise) and the comparison of the three sharded step modes.
 
 The workload is the SAME at every N (default: BASELINE configs[1], the configuration the metric is quoted on): Re=50
 cylinder, lx1=8, E=1996, direct Arnoldi, k_dim=128.  One "step" = one Arnoldi step = nsteps(=183) linearised Navier-Stokes
@@ -65,7 +72,12 @@ def parse():
     ap.add_argument("--cpu-baseline-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--no-preflight", action="store_true", help="N>1 over RCCL: skip the two-form RCCL check (tests/mp_rccl_worker.py in fresh processes) in front of the timed run")
     ap.add_argument("--ref-logfile", default=None, help="a logfile of a nekStab run of the same case (its 'Time per iteration' lines, core/krylov_decomposition.f:92-98, and Nek5000's step lines): the record gains `reference_logfile` with the reference's own matvecs/s")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every optional section of the record (k_dim continuation, Ritz pair, byte accounting, rooflines, CPU baseline, Fortran host, one-GPU comparison and cfg3 run at N>1); a plain run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB in all: larger outputs as a fixed, seeded sample of elements): the Hessenberg matrix and the new Krylov vector (krylov_*; cfg5: the map's output, map_*); a sharded run (N>1) writes the Hessenberg matrix only, as no rank holds the whole vector, so its outputs compare with an N=1 run's hessenberg.npy alone")
+    a = ap.parse_args()
+    if a.extras or a.ref_logfile:
+        a.full = True
+    return a
 
 
 METRIC = "Arnoldi matvecs/sec + wall-time to k_dim=128 eigenpairs, cylinder Re=50"
@@ -104,12 +116,14 @@ def supervise(a):
     # takes rccl_fuse = 0 and the record says so.
     preflight = None
     ngpu = 0
-    try:
-        import torch
-        ngpu = torch.cuda.device_count()                    # (counting devices does not initialise the GPU)
-    except Exception:                                       # noqa: BLE001
-        pass
-    if not a.replicas and not a.no_preflight and os.environ.get("NSK_DIST_BACKEND", "nccl") == "nccl" and ngpu >= world:
+    wants_preflight = not a.replicas and not a.no_preflight and os.environ.get("NSK_DIST_BACKEND", "nccl") == "nccl"
+    if wants_preflight:                                     # (dry runs over gloo never count the devices)
+        try:
+            import torch
+            ngpu = torch.cuda.device_count()
+        except Exception:                                   # noqa: BLE001
+            pass
+    if wants_preflight and ngpu >= world:
         preflight = rccl_preflight(world, ranks, under_launcher, base_port)
         print("bench.py supervisor: RCCL pre-flight: %s" % json.dumps(preflight), file=sys.stderr, flush=True)
     rc = 1
@@ -484,6 +498,35 @@ def pmc_traffic(kernel_key):
     return None, "the committed PMC tables (profiles/r*_pmc_traffic.json) are from other builds of the library"
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per output of the timed path's last step.  When they exceed 64 MB together,
+    every array whose first axis is the element index keeps the same fixed, seeded sample of elements (sorted), so two builds
+    are compared output for output."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BYTES:
+        nel = max(v.shape[0] for v in arrays.values())
+        big = sum(v.nbytes for v in arrays.values() if v.shape[0] == nel)
+        keep = int(nel * (DUMP_BYTES - (1 << 16) - (total - big)) / big)       # (64 kB for the .npy headers)
+        rows = np.sort(np.random.default_rng(20240611).choice(nel, size=keep, replace=False))
+        arrays = {k: (v[rows] if v.shape[0] == nel else v) for k, v in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v))
+    print("[bench] outputs of the last timed step: %s in %s" % (", ".join("%s %s" % (k, v.shape) for k, v in arrays.items()), dirname), file=sys.stderr, flush=True)
+
+
+def vector_outputs(ctx, v, prefix, hexa):
+    """The fields of one state vector on the host: {prefix_u, prefix_v, [prefix_w,] prefix_p}."""
+    f = ctx.download3(v) if hexa else ctx.download(v)
+    names = ("u", "v", "w", "p") if hexa else ("u", "v", "p")
+    return {prefix + "_" + n: a for n, a in zip(names, f)}
+
+
 def build_case(name, lx1_override=None):
     from nekstab_amd import mesh
     if name == "cfg4":
@@ -538,12 +581,11 @@ def run_cfg5(a):
     for _ in range(steps):
         h.matvec(f, q, 0)
     h.norm(f); torch.cuda.synchronize(); elapsed = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, vector_outputs(h, f, "map", True))
     st = h.stats()
     ms_ts = 1e3 * elapsed / (steps * a.map_steps)
     za = int(st.get("zero_arrays", 0))
-    rule, distinct = roofline.helm_launch_bytes(nel=c.nel, lx1=10, ndim=3, zero_arrays=za)
-    kr = h.bench_kernel("helm", 10)
-    traffic, tnote = pmc_traffic("k3::helm<10>")
     out = {"metric": METRIC, "value": 1.0 / (1e-3 * ms_ts * nfull), "unit": "matvecs/s", "n_gpus": 1, "steps": steps, "warmup": warm,
            "ms_per_step": 1e3 * elapsed / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
            "data": "synthetic: a smooth three-dimensional perturbation of an analytic vortex on the box mesh (the reference's lid_driven case needs its 3-D base flow, which is not in the tree)",
@@ -552,12 +594,20 @@ def run_cfg5(a):
                                   % (c.nel, a.map_steps, nfull, 8e-9 * h.nstate),
                       "tolerances": "Helmholtz 1e-9, pressure 1e-2 relative, projection space %d, host-read convergence flags" % nproj, "parallelism": "1 GPU"},
            "setup_s": setup_s, "ms_per_time_step": ms_ts, "helm_iters_per_step": st["helm_iters"] / max(st["steps"], 1), "pres_iters_per_step": st["pres_iters"] / max(st["steps"], 1),
-           "zero_arrays": za,
+           "zero_arrays": za}
+    if not a.full:
+        print(json.dumps(out), flush=True)
+        h.close()
+        return 0
+    rule, distinct = roofline.helm_launch_bytes(nel=c.nel, lx1=10, ndim=3, zero_arrays=za)
+    kr = h.bench_kernel("helm", 10)
+    traffic, tnote = pmc_traffic("k3::helm<10>")
+    out.update({
            "roofline": {"bound": "hbm", "kernel": "k3::k_helm_p<10> (one CG iteration of the three components: resident workgroups, the next element's vectors by LDS-DMA; 64-69 % of the kernel time of a time step: profiles/r06_cfg5_trace_summary.txt)", "achieved": distinct / kr["avg_us"] / 1e3, "peak": 8000.0, "unit": "GB/s",
                         "frac": distinct / kr["avg_us"] / 1e3 / 8000.0, "traffic": traffic, "traffic_source": tnote, "avg_launch_us": kr["avg_us"], "algorithmic_bytes_per_launch": distinct,
                         "survey_rule": {"algorithmic_bytes_per_launch": rule, "frac": rule / kr["avg_us"] / 1e3 / 8000.0},
                         "note": "every distinct array of the launch ONCE (the figure to quote); SURVEY 8(d)'s per-component rule counts the arrays the three components share three times: `survey_rule`, not a bandwidth"},
-           "cpu_baseline": None, "cpu_baseline_note": "the C / OpenMP port covers quadrilaterals: the default record (configs[1]) carries the CPU baseline"}
+           "cpu_baseline": None, "cpu_baseline_note": "the C / OpenMP port covers quadrilaterals: the default record (configs[1]) carries the CPU baseline"})
     kt = {}
     for kn in ("divgs", "schwarz", "convect_mfma", "helm_wg"):
         try:
@@ -800,7 +850,7 @@ def main():
         h.set_nsteps(int(os.environ["NSK_BENCH_MAP_STEPS"]))
         if sharded and rank == 0 and not local_setup:
             full.set_nsteps(int(os.environ["NSK_BENCH_MAP_STEPS"]))
-    ktot = max(a.warmup + steps, K_DIM if (headline and not a.no_kdim) else 0)
+    ktot = max(a.warmup + steps, K_DIM if (headline and a.full and not a.no_kdim) else 0)
     Q = h.alloc(ktot + 1)
     upload_seed(h, Q[0])
     h.scal(Q[0], 1.0 / h.norm(Q[0]))
@@ -819,6 +869,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kdone = a.warmup + steps
+    if a.dump_outputs and rank == 0:
+        # the factorisation so far and the basis vector the last timed step appended (sharded: the Hessenberg matrix only)
+        dumped = {"hessenberg": H[:kdone + 1, :kdone]}
+        if not sharded:
+            dumped.update(vector_outputs(h, Q[kdone], "krylov", hexa))
+        dump_outputs(a.dump_outputs, dumped)
     kdim_case = 256 if hexa else K_DIM
     par = "1 GPU"
     if world > 1:
@@ -891,7 +947,7 @@ def main():
         guarded("reference_logfile", sec_reflog)
 
     opt_wd = None
-    if world == 1:
+    if world == 1 and a.full:
         def _optional_overrun():
             out["optional_sections_cut"] = "the sections after the timed steps outlived --optional-budget-s = %g s: the record is printed as it stood" % a.optional_budget_s
             emit()
@@ -906,14 +962,15 @@ def main():
         if kdone < ktot:
             krylov.arnoldi_factorization(h, Q, H, kdone + 1, ktot, amode, stats=stats)
             kdone = ktot
-    guarded("wall_time_kdim_s", sec_kdim)
+    if a.full:
+        guarded("wall_time_kdim_s", sec_kdim)
     kdone = len(stats["matvec_s"])                          # (what was completed, also after a failure half way)
     step_s = np.array(stats["matvec_s"][:kdone]) + np.array(stats["orth_s"][:kdone])
     wall_kdim = float(step_s[:K_DIM].sum()) if kdone >= K_DIM else None
     if not isinstance(out.get("wall_time_kdim_s"), dict):
         out["wall_time_kdim_s"] = wall_kdim
     if wall_kdim is None:
-        out["wall_time_kdim_note"] = "only %d of the %d Arnoldi steps were run (--steps / --no-kdim); per-step time x %d = %.1f s projected" % (kdone, kdim_case, kdim_case, kdim_case * elapsed / steps)
+        out["wall_time_kdim_note"] = "only %d of the %d Arnoldi steps were run (--steps / --no-kdim / no --full); per-step time x %d = %.1f s projected" % (kdone, kdim_case, kdim_case, kdim_case * elapsed / steps)
 
     def sec_ritz():
         kk = min(kdone, K_DIM) if kdone >= K_DIM else kdone
@@ -927,9 +984,10 @@ def main():
                               "Spectre_Ha.dat (adjoint, lx1 = 8) and rows 1, 4 of Spectre_Hd.dat (direct, lx1 = 6); the wake rows 5-23 of Spectre_Hd.dat sit 1.2e-5 .. 4.6e-5 "
                               "from the table and are pinned to the ORACLE only (1e-8 HIP vs oracle): DESIGN.md section 1")
         out["leading_ritz"] = ritz
-    guarded("leading_ritz", sec_ritz)
+    if a.full:
+        guarded("leading_ritz", sec_ritz)
 
-    if not sharded:
+    if not sharded and a.full:
         st = {}
 
         def sec_bytes():
@@ -1031,7 +1089,7 @@ def main():
         guarded("roofline", sec_roofline)
         if isinstance(out.get("roofline"), dict) and "error" in out["roofline"]:
             out["roofline"].update({"bound": "hbm", "achieved": None, "peak": 8000.0, "unit": "GB/s", "frac": None, "traffic": None})
-    else:
+    elif sharded:
         st = h.stats()
         out.update({"helm_iters_per_step_last_map": st["helm_iters"] / max(st["steps"], 1), "pres_iters_per_step_last_map": st["pres_iters"] / max(st["steps"], 1),
                     "map_retries": st["retries"], "graph_recaptures": st["recaptures"]})
@@ -1055,7 +1113,7 @@ def main():
         setup_local = {"rank_local": bool(local_setup), "seconds_rank0": setup_s, "elements_rank0": int(full.nel), "elements_mesh": int(case.nel)}
         if local_setup:
             h.close(); full.close()                              # (the shard and its sub-mesh context: done)
-            if rank == 0:
+            if rank == 0 and a.full:
                 t0 = time.perf_counter()
                 full = make_context(case)
                 setup_local["whole_mesh_seconds_rank0"] = time.perf_counter() - t0
@@ -1064,7 +1122,7 @@ def main():
             out["rccl_preflight"] = dict(json.loads(os.environ["NSK_BENCH_PREFLIGHT"]), note="tests/mp_rccl_worker.py in fresh processes before the timed run: a sharded map with the all-reduce inside the halo messages' RCCL group (fuse1) and, only if that fails, with separate calls (fuse0); `rccl_fuse` is the form this run used")
         out["shard_mode"] = dict(shard_mode, config=a.case, note="seconds for 24 sharded time steps with captured step graphs (RCCL calls inside) / with eager launches and host-read convergence flags / the same with the halo of the velocity solve overlapped with its interior work; the timed run uses the fastest") if shard_mode else \
             {"picked": "hostcheck" if backend != "nccl" or shard_graph == 0 else "graph", "note": "not compared in this attempt"}
-        if rank == 0:
+        if rank == 0 and a.full:
             try:
                 r1 = one_gpu_same_steps(full, case, steps)
                 out["single_gpu_same_config"] = {"matvecs_per_s": r1, "sample": "the same %d + %d Arnoldi steps of the same case on rank 0's full-mesh context (hipGraph path), timed after the sharded run" % (a.warmup, steps),
@@ -1078,7 +1136,7 @@ def main():
         # ---- BASELINE configs[2] next to the headline workload: where element sharding is meant to pay (1.15 M points per field).
         # The headline record is PRINTED at this point; this section runs under its own watchdog (a stall ends the worker with
         # code 0), every rank catches its own exceptions and the ranks agree on the outcome before anyone goes on.
-        if a.case == "cfg2" and not a.no_cfg3_probe:
+        if a.case == "cfg2" and not a.no_cfg3_probe and a.full:
             def _cfg3_stalled():
                 print("bench.py rank %d: config3_sharded: no result after %d s: keeping the headline record" % (rank, C3_PROBE_S), file=sys.stderr, flush=True)
                 if rank == 0:
@@ -1162,15 +1220,15 @@ def main():
 
     # ---- N = 1: the CPU baseline and the Fortran-host leg, then THE RECORD; the optional diagnostics run after it
     if world == 1:
-        if headline and not a.no_cpu_baseline:
+        if headline and a.full and not a.no_cpu_baseline:
             def sec_cpu():
                 qs = full.download(Q[a.warmup]) if not hexa else None      # the input of the first timed Arnoldi step
                 out["cpu_baseline"] = cpu_baseline(case, a.cpu_threads, (a.tol_helm, a.tol_pres, a.min_pres), a.nproj, out["value"], qs)
             guarded("cpu_baseline", sec_cpu)
-        if hexa:
+        if hexa and a.full:
             out["cpu_baseline"] = None
             out["cpu_baseline_note"] = "the C / OpenMP port of the step (oracle/cpu_step.c) covers quadrilaterals; the hexahedral oracle (oracle/linns3d.py) uses sparse direct solves and does not reach this size: the default record (BASELINE configs[1]) carries the CPU baseline"
-        if headline and not a.no_fortran_host:
+        if headline and a.full and not a.no_fortran_host:
             def sec_fortran():
                 out["fortran_host"] = fortran_host_leg(case, (qx, qy, zp), a, steps, out["value"])
             guarded("fortran_host", sec_fortran)

@@ -1,7 +1,7 @@
 #!/bin/bash
 O=gpurun_out/r05; mkdir -p $O
 run() {
-  env "${@:2}" python3 bench.py --steps 118 --warmup 10 --no-cpu-baseline --no-fortran-host --no-kdim > $O/abs_$1.json 2> $O/abs_$1.err
+  env "${@:2}" python3 bench.py --full --steps 118 --warmup 10 --no-cpu-baseline --no-fortran-host --no-kdim > $O/abs_$1.json 2> $O/abs_$1.err
   python3 -c "
 import json; r=json.load(open('$O/abs_$1.json')); print('$1', 'value %.3f' % r['value'], 'ms/time step %.4f' % r['ms_per_time_step'], 'retries', r['map_retries'], r['launch_budgets']['per_time_step'], 'tail maps', r['launch_budgets']['persistent_tail_maps'])"
 }

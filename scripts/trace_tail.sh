@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 cd /tmp; export TMPDIR=/tmp
 OUT=$R/gpurun_out/r05
 mkdir -p $OUT
-NSK_TAIL=${NSK_TAIL:--1} timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/p_tail --output-format csv -- python3 $R/bench.py --steps 12 --warmup 10 --no-cpu-baseline --no-kdim --no-fortran-host > $OUT/r05_prof_tail.json 2> $OUT/r05_prof_tail.err
+NSK_TAIL=${NSK_TAIL:--1} timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/p_tail --output-format csv -- python3 $R/bench.py --full --steps 12 --warmup 10 --no-cpu-baseline --no-kdim --no-fortran-host > $OUT/r05_prof_tail.json 2> $OUT/r05_prof_tail.err
 python3 $R/scripts/trace_summary.py $OUT/p_tail --last 0.5 > $OUT/r05_tail_trace_summary.txt 2>&1
 python3 - <<PY
 import csv, glob, numpy as np

@@ -13,18 +13,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
     config.addinivalue_line("markers", "slow: long CPU test")
-    config.addinivalue_line("markers", "lanes: lanes / band Arnoldi (nsk_clone, nsk_matvec_batch: NOT in the reference; out of the default suites, NSK_TEST_LANES=1 runs them)")
-
-
-def pytest_collection_modifyitems(config, items):
-    """Lanes and the band Arnoldi factorisation are this build's own (the reference runs one map per MPI job): their tests
-    stay in the tree but out of the default CPU and GPU suites (the GPU suite must stay well inside the driver's limit)."""
-    if os.environ.get("NSK_TEST_LANES") == "1":
-        return
-    skip = pytest.mark.skip(reason="lanes / band Arnoldi are not in the reference: set NSK_TEST_LANES=1 to run these tests")
-    for it in items:
-        if "lanes" in it.keywords:
-            it.add_marker(skip)
+    config.addinivalue_line("markers", "lanes: lanes / band Arnoldi (nsk_clone, nsk_matvec_batch: NOT in the reference; part of the GPU suite, -m 'not lanes' leaves them out)")
 
 
 def _gpu_available():

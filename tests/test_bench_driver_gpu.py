@@ -1,6 +1,7 @@
-"""The driver's bench command, exactly: `python3 bench.py --gpus 1 --steps 20 --warmup 5` in a fresh child process.
-BENCH_r04 was lost (rc 1, no JSON) because an optional diagnostic raised before the record was printed and no test ran this
-command; this one does, and checks what the judge reads from the record."""
+"""The driver's bench command, `python3 bench.py --gpus 1 --steps N --warmup W`, in a fresh child process: the plain run
+(the timed steps, the outputs of the last one, the headline record) and the same command with --full (every optional
+section).  BENCH_r04 was lost (rc 1, no JSON) because an optional diagnostic raised before the record was printed and no
+test ran this command; these do, and check what the judge reads from the record."""
 import json
 import os
 import subprocess
@@ -22,8 +23,36 @@ def _run(args, timeout=900, env=None):
     return out, wall, lines
 
 
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """The plain run does the timed steps and nothing of the optional sections; --dump-outputs writes the Hessenberg matrix and
+    the basis vector of the last timed step, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    dumps = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dumps:
+        out, wall, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", d])
+        assert out.returncode == 0, out.stderr[-3000:]
+        assert len(lines) == 1, out.stdout[-2000:]
+        r = json.loads(lines[0])
+        assert r["metric"].startswith("Arnoldi matvecs/sec") and r["unit"] == "matvecs/s" and r["n_gpus"] == 1 and r["dtype"] == "f64"
+        assert r["steps"] == 3 and r["warmup"] == 2 and r["higher_is_better"] is True
+        assert r["value"] > 1.0 and abs(r["value"] - 1e3 / r["ms_per_step"]) < 1e-6 * r["value"]
+        assert r["ms_per_step"] * r["steps"] * 1e-3 < wall
+        for k in ("roofline", "cpu_baseline", "fortran_host", "leading_ritz", "bytes_per_matvec"):
+            assert k not in r, k
+        assert r["wall_time_kdim_s"] is None
+    names = sorted(os.listdir(dumps[0]))
+    assert names == ["hessenberg.npy", "krylov_p.npy", "krylov_u.npy", "krylov_v.npy"] and sorted(os.listdir(dumps[1])) == names
+    H = np.load(os.path.join(dumps[0], "hessenberg.npy"))
+    assert H.shape == (6, 5) and H.dtype == np.float64 and np.all(np.diag(H, -1) > 0)
+    u = np.load(os.path.join(dumps[0], "krylov_u.npy"))
+    assert u.shape == (1996, 8, 8) and np.isfinite(u).all() and np.abs(u).max() > 0
+    for n in names:
+        x, y = np.load(os.path.join(dumps[0], n)), np.load(os.path.join(dumps[1], n))
+        assert x.shape == y.shape and np.abs(x - y).max() <= 1e-6 * np.abs(x).max(), n
+
+
 def test_driver_command_prints_one_complete_record():
-    out, wall, lines = _run(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    out, wall, lines = _run(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
     assert out.returncode == 0, out.stderr[-3000:]
     assert len(lines) == 1, out.stdout[-2000:]                      # ONE JSON line
     r = json.loads(lines[0])
@@ -51,7 +80,7 @@ def test_record_survives_failing_optional_sections(tmp_path):
     record still has the headline and the roofline, the failed fields say why, and the exit code is 0; --extras writes the
     diagnostics to their own file AFTER the record."""
     ex = os.path.join(str(tmp_path), "extras.json")
-    out, wall, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-kdim", "--extras", "--extras-out", ex],
+    out, wall, lines = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-kdim", "--extras", "--extras-out", ex],
                             env={"NSK_BENCH_TEST_FAIL": "cpu_baseline,fortran_host"})
     assert out.returncode == 0, out.stderr[-3000:]
     assert len(lines) == 1

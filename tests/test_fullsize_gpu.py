@@ -186,12 +186,12 @@ def test_config5_lid_driven_cube_E99452_lx1_10():
 
 
 def test_bench_case_cfg4_record_shape():
-    """`bench.py --case cfg4` (BASELINE configs[3], the bandwidth-sized configuration) on a thin slab of the same mesh: one JSON
+    """`bench.py --case cfg4 --full` (BASELINE configs[3], the bandwidth-sized configuration) on a thin slab of the same mesh: one JSON
     line with the hexahedral byte accounting (Gram-Schmidt bytes from the logged basis indices, coarse-solve bytes from the
     context), the dominant-kernel and end-to-end rooflines and the live per-kernel table."""
     import json, subprocess, sys
     env = dict(os.environ, NSK_BENCH_CFG4_LAYERS="2")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--case", "cfg4", "--steps", "1", "--warmup", "1"], capture_output=True, text=True, timeout=900, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--case", "cfg4", "--steps", "1", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
