@@ -229,6 +229,35 @@ module nekstab_hip
       type(c_ptr), value :: ctx
       type(c_ptr), value :: v
     end function
+    ! sensitivity post-processing (core/sensitivity.f)
+    integer(c_int) function nsk_biorthogonalize(ctx, dRe, dIm, aRe, aIm, gamma_delta) bind(c, name='nsk_biorthogonalize')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: dRe, dIm, aRe, aIm
+      real(c_double), dimension(*) :: gamma_delta
+    end function
+    integer(c_int) function nsk_wavemaker(ctx, dRe, dIm, aRe, aIm, wm) bind(c, name='nsk_wavemaker')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: dRe, dIm, aRe, aIm
+      type(c_ptr), value :: wm
+    end function
+    ! parts: c_null_ptr or c_loc of a type(c_ptr) array {tr, ti, pr, pi}
+    integer(c_int) function nsk_bf_sensitivity(ctx, dRe, dIm, aRe, aIm, sr, si, parts) bind(c, name='nsk_bf_sensitivity')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: dRe, dIm, aRe, aIm
+      type(c_ptr), value :: sr, si
+      type(c_ptr), value :: parts
+    end function
+    integer(c_int) function nsk_forced_map(ctx, mode, f, q, force) bind(c, name='nsk_forced_map')
+      import
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: mode
+      type(c_ptr), value :: f
+      type(c_ptr), value :: q
+      type(c_ptr), value :: force
+    end function
     integer(c_int) function nsk_clone(ctx, lane) bind(c, name='nsk_clone')
       import
       type(c_ptr), value :: ctx

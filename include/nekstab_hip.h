@@ -190,6 +190,30 @@ int nsk_basis_gemv(nsk_ctx* ctx, const nsk_vec* Q, int k, const double* y_re,
 /* add_noise seed (core/utils.f:344-408): deterministic pseudo-noise, dssum-averaged, masked */
 int nsk_seed_noise(nsk_ctx* ctx, nsk_vec v);
 
+/* ---- sensitivity post-processing (core/sensitivity.f; uparam(1) = 4.2, 4.3, 4.41 / 4.42) ----
+ * Single-rank full-mesh contexts, quadrilaterals and hexahedra; shard and rank-local contexts return NSK_EINVAL.
+ * Inner products are the bm1s-weighted velocity products of nsk_dot. */
+/* biorthogonalize (core/sensitivity.f:428-504), in place: d <- d / ||d|| (||d||^2 = ||dRe||^2 + ||dIm||^2; the whole vector is
+ * scaled), then with <a, d> = gamma + i delta: a <- a / (gamma - i delta), so that <a, d> = 1 afterwards.  gamma_delta (optional)
+ * receives {gamma, delta}. */
+int nsk_biorthogonalize(nsk_ctx* ctx, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, double* gamma_delta);
+/* wave_maker (core/sensitivity.f:7-81) on modes already biorthogonalised: |d| |a| pointwise (velocity components), in wm's
+ * first component; the other components and the pressure of wm are 0. */
+int nsk_wavemaker(nsk_ctx* ctx, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec wm);
+/* bf_sensitivity (core/sensitivity.f:93-284) on modes already biorthogonalised (Marquet, Sipp & Jacquin 2008):
+ *   tr_i = -sum_j (aRe_j d dRe_j/dx_i + aIm_j d dIm_j/dx_i)    ti_i = sum_j (aRe_j d dIm_j/dx_i - aIm_j d dRe_j/dx_i)
+ *   pr_i =  sum_j (dRe_j d aRe_i/dx_j + dIm_j d aIm_i/dx_j)    pi_i = sum_j (dRe_j d aIm_i/dx_j - dIm_j d aRe_i/dx_j)
+ *   sr = tr + pr, si = ti + pi,
+ * with the physical gradients of the GLL mesh averaged over shared nodes (gradm1 + dsavg).  parts: NULL or {tr, ti, pr, pi}.
+ * The pressure of every output is 0.  In 3-D the reference's transport term reads d w / d z where the formula has d v / d z
+ * (core/sensitivity.f:219, 222, 228, 231): this entry implements the formula; on 2-D and z-invariant fields the two agree. */
+int nsk_bf_sensitivity(nsk_ctx* ctx, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec sr, nsk_vec si, nsk_vec* parts);
+/* f = the linearised map of q under the steady body force `force` (fcx / fcy / fcz of nekStab_forcing, core/utils.f:160-162),
+ * mode NSK_DIRECT or NSK_ADJOINT: B force enters every time step where the sponge term does, before the EXT extrapolation.
+ * initialize_rhs_ts_steady_force_sensitivity (core/sensitivity.f:380-422) is the adjoint map with q = 0.  The time steps run
+ * eagerly (the captured step graphs belong to the unforced maps); force = 0 gives the bits of nsk_matvec. */
+int nsk_forced_map(nsk_ctx* ctx, int mode, nsk_vec f, nsk_vec q, nsk_vec force);
+
 /* ---- lanes: independent maps in flight at once on one GPU ----
  * nsk_clone gives a context a second LANE: its own stream, time-stepper state, solver work arrays and projection space; geometry,
  * operators and preconditioner are shared (quadrilateral full-mesh contexts).  nsk_matvec_batch(lanes, b, mode, f, q) runs

@@ -105,6 +105,10 @@ SYMBOLS = {
     "nsk_group_test": (C.c_int, [_vpp, C.c_int, C.c_int, C.POINTER(_dp), C.POINTER(_dp)]),
     "nsk_local_dots": (C.c_int, [_vp, _vp, _vpp, C.c_int, _dp]),
     "nsk_project_out": (C.c_int, [_vp, _vp, _vpp, C.c_int, _dp]),
+    "nsk_biorthogonalize": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _dp]),
+    "nsk_wavemaker": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "nsk_bf_sensitivity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vpp]),
+    "nsk_forced_map": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "nsk_bench_kernel": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),
     "nsk_get_step_iters": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nsk_get_stats": (C.c_int, [_vp, C.POINTER(NskStats)]),
@@ -353,6 +357,26 @@ class NekStabHip:
     def seed_noise(self, v):
         """add_noise (core/utils.f:344-408) on the device."""
         self._chk(self.lib.nsk_seed_noise(self.ctx, v))
+
+    # ---- sensitivity post-processing (core/sensitivity.f)
+    def biorthogonalize(self, dRe, dIm, aRe, aIm):
+        """In place: ||d|| = 1 and <a, d> = 1 (nsk_biorthogonalize).  Returns (gamma, delta), the inner product before."""
+        gd = np.zeros(2)
+        self._chk(self.lib.nsk_biorthogonalize(self.ctx, dRe, dIm, aRe, aIm, _p(gd)))
+        return float(gd[0]), float(gd[1])
+
+    def wavemaker(self, dRe, dIm, aRe, aIm, wm):
+        """|d| |a| into wm's first component (nsk_wavemaker)."""
+        self._chk(self.lib.nsk_wavemaker(self.ctx, dRe, dIm, aRe, aIm, wm))
+
+    def bf_sensitivity(self, dRe, dIm, aRe, aIm, sr, si, parts=None):
+        """sr, si (and, if ``parts`` = [tr, ti, pr, pi] is given, the four terms) of the base-flow sensitivity."""
+        arr = (C.c_void_p * 4)(*[v.value for v in parts]) if parts is not None else None
+        self._chk(self.lib.nsk_bf_sensitivity(self.ctx, dRe, dIm, aRe, aIm, sr, si, arr))
+
+    def forced_map(self, f, q, force, mode=NSK_ADJOINT):
+        """f = linearised map of q under the steady body force ``force`` (nsk_forced_map)."""
+        self._chk(self.lib.nsk_forced_map(self.ctx, int(mode), f, q, force))
 
     # Lanes (nsk_clone) hold their solver settings BY VALUE: a setter called after lanes exist acts on every lane, so that
     # matvec_batch / band_arnoldi never apply different operators on different lanes (ADVICE r3).

@@ -28,6 +28,7 @@
 #include "nsk_persist.hpp"
 #include "nsk3_kernels.hpp"
 #include "nsk3_mfma.hpp"
+#include "nsk_sens.hpp"
 
 using namespace nsk;
 
@@ -184,6 +185,7 @@ struct nsk_ctx {
   long long hc_checks = 0;                              // flag reads since init (diagnostics)
   double* scratch = nullptr;            // one state vector
   const double* xyz = nullptr;          // GLL coordinates [ndim][nloc] (nsk_seed_noise)
+  const double* force = nullptr;        // steady body force [ndim][nloc] of the running forced map (nsk_forced_map; eager steps only), else null
   double* rc_big = nullptr;             // coarse restriction for nvert > 3072
   Dev d{};
   Stats hstats{};
@@ -1442,6 +1444,8 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       hipLaunchKernelGGL(nsk::k3::k_convect_mfma_nl<10>, dim3(c->nel), dim3(1024), 0, c->stream, d, (const double*)d.u, d.bf);
     else
       hipLaunchKernelGGL(k_convect<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)d.u, d.bf, adjoint);
+    if (c->force)                     // forced map: + B f where the sponge entered, before the EXT extrapolation (k_rhs)
+      hipLaunchKernelGGL(nsk::sens::k_add_force, dim3((unsigned)((d.nloc + 255) / 256)), dim3(256), 0, c->stream, d.bf, d.cs, d.bm1, c->force, d.nloc, c->ndim);
     if (c->fused) {
       // persistent velocity solve: rhs + every CG iteration + pressure right-hand side in one launch
       HIPCHK(hipMemsetAsync(c->sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
@@ -2964,6 +2968,129 @@ int nsk_seed_noise(nsk_ctx* c, nsk_vec v) {
   hipLaunchKernelGGL(k_seed_avg, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)q, c->scratch, 0);
   hipLaunchKernelGGL(k_seed_avg, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, q, 1);
   return 0;
+}
+
+// ---- sensitivity post-processing (core/sensitivity.f) ---------------------------------------------------------------
+static int sens_ctx_ok(nsk_ctx* c, const char* who) {
+  if (!c) return fail(NSK_EINVAL, std::string(who) + ": bad argument");
+  if (c->parent || c->local || c->released || c->d.nranks > 1)
+    return fail(NSK_EINVAL, std::string(who) + ": single-rank full-mesh contexts only (sharded sensitivity is not supported)");
+  return 0;
+}
+
+static bool distinct(const std::vector<const void*>& v) {
+  for (size_t a = 0; a < v.size(); ++a)
+    for (size_t b = a + 1; b < v.size(); ++b)
+      if (v[a] == v[b]) return false;
+  return true;
+}
+
+int nsk_biorthogonalize(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, double* gamma_delta) {
+  int rc = sens_ctx_ok(c, "nsk_biorthogonalize");
+  if (rc) return rc;
+  if (!dRe || !dIm || !aRe || !aIm || !distinct({dRe, dIm, aRe, aIm})) return fail(NSK_EINVAL, "nsk_biorthogonalize: four distinct vectors needed");
+  double a = 0, b = 0;                                           // || d ||^2 = || dRe ||^2 + || dIm ||^2  (:459-465)
+  if ((rc = nsk_dot(c, dRe, dRe, &a)) || (rc = nsk_dot(c, dIm, dIm, &b))) return rc;
+  if (!(a + b > 0.0)) return fail(NSK_EINVAL, "nsk_biorthogonalize: the direct mode is zero");
+  const double s = 1.0 / std::sqrt(a + b);
+  if ((rc = nsk_scal(c, dRe, s)) || (rc = nsk_scal(c, dIm, s))) return rc;
+  double rr = 0, ii = 0, ri = 0, ir = 0;                         // <a, d> = gamma + i delta  (:468-476)
+  if ((rc = nsk_dot(c, aRe, dRe, &rr)) || (rc = nsk_dot(c, aIm, dIm, &ii)) || (rc = nsk_dot(c, aRe, dIm, &ri)) ||
+      (rc = nsk_dot(c, aIm, dRe, &ir))) return rc;
+  const double gamma = rr + ii, delta = ri - ir, den = gamma * gamma + delta * delta;
+  if (!(den > 0.0)) return fail(NSK_EINVAL, "nsk_biorthogonalize: the adjoint mode is orthogonal to the direct mode");
+  hipLaunchKernelGGL(nsk::sens::k_cdiv, dim3((unsigned)((c->nstate + 255) / 256)), dim3(256), 0, c->stream, (double*)aRe, (double*)aIm,
+                     gamma / den, delta / den, c->nstate);
+  HIPCHK(hipGetLastError());
+  if (gamma_delta) { gamma_delta[0] = gamma; gamma_delta[1] = delta; }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int nsk_wavemaker(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec wm) {
+  int rc = sens_ctx_ok(c, "nsk_wavemaker");
+  if (rc) return rc;
+  if (!dRe || !dIm || !aRe || !aIm || !wm) return fail(NSK_EINVAL, "nsk_wavemaker: bad argument");
+  if (!distinct({dRe, wm}) || !distinct({dIm, wm}) || !distinct({aRe, wm}) || !distinct({aIm, wm}))
+    return fail(NSK_EINVAL, "nsk_wavemaker: the output may not be one of the modes");
+  HIPCHK(hipMemsetAsync(wm, 0, c->nstate * sizeof(double), c->stream));
+  hipLaunchKernelGGL(nsk::sens::k_wavemaker, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream, (const double*)dRe,
+                     (const double*)dIm, (const double*)aRe, (const double*)aIm, (double*)wm, c->nloc, c->ndim);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int nsk_bf_sensitivity(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec sr, nsk_vec si, nsk_vec* parts) {
+  int rc = sens_ctx_ok(c, "nsk_bf_sensitivity");
+  if (rc) return rc;
+  if (!dRe || !dIm || !aRe || !aIm || !sr || !si) return fail(NSK_EINVAL, "nsk_bf_sensitivity: bad argument");
+  if (parts && (!parts[0] || !parts[1] || !parts[2] || !parts[3])) return fail(NSK_EINVAL, "nsk_bf_sensitivity: parts needs four vectors");
+  if (!c->xyz || !c->scratch) return fail(NSK_EINVAL, "nsk_bf_sensitivity: context holds no coordinates");
+  std::vector<const void*> all = {dRe, dIm, aRe, aIm, sr, si};
+  if (parts) all.insert(all.end(), parts, parts + 4);
+  if (!distinct(all))
+    return fail(NSK_EINVAL, "nsk_bf_sensitivity: inputs and outputs must be distinct vectors");
+  double* outs[6] = {(double*)sr, (double*)si, parts ? (double*)parts[0] : nullptr, parts ? (double*)parts[1] : nullptr,
+                     parts ? (double*)parts[2] : nullptr, parts ? (double*)parts[3] : nullptr};
+  for (double* o : outs) if (o) HIPCHK(hipMemsetAsync(o, 0, c->nstate * sizeof(double), c->stream));
+  double* tR = parts ? outs[2] : outs[0];                        // transport (tr, ti) and production (pr, pi) terms
+  double* tI = parts ? outs[3] : outs[1];
+  double* pR = parts ? outs[4] : outs[0];
+  double* pI = parts ? outs[5] : outs[1];
+  const double* m[4] = {(const double*)dRe, (const double*)dIm, (const double*)aRe, (const double*)aIm};
+  // kind 0 / 1: gradient of the direct mode (transport), kind 2 / 3: of the adjoint mode (production); sensitivity.f:215-256
+  // with d v / d z where the reference reads d w / d z in the transport term (:219, 222, 228, 231)
+  const nsk::sens::SensAcc acc[4] = {
+      {m[2], m[3], tR, tI, -1.0, -1.0, 0, 0},
+      {m[3], m[2], tR, tI, -1.0, 1.0, 0, 0},
+      {m[0], m[1], pR, pI, 1.0, -1.0, 0, 1},
+      {m[1], m[0], pR, pI, 1.0, 1.0, 0, 1}};
+  const unsigned grid = (unsigned)((c->nloc + 255) / 256);
+  for (int kind = 0; kind < 4; ++kind)
+    for (int comp = 0; comp < c->ndim; ++comp) {
+      const double* f = m[kind] + (size_t)comp * c->nloc;
+      switch (c->key) {
+        case 6: nsk::sens::launch_sens_grad<6, 2>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
+        case 8: nsk::sens::launch_sens_grad<8, 2>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
+        case 10: nsk::sens::launch_sens_grad<10, 2>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
+        case 12: nsk::sens::launch_sens_grad<12, 2>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
+        case 106: nsk::sens::launch_sens_grad<6, 3>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
+        case 108: nsk::sens::launch_sens_grad<8, 3>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
+        case 110: nsk::sens::launch_sens_grad<10, 3>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
+        default: return fail(NSK_EINVAL, "unsupported lx1");
+      }
+      nsk::sens::SensAcc a = acc[kind];
+      a.comp = comp;
+      if (c->ndim == 2) hipLaunchKernelGGL(nsk::sens::k_sens_acc<2>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, a);
+      else hipLaunchKernelGGL(nsk::sens::k_sens_acc<3>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, a);
+    }
+  if (parts) {
+    const long long nv = (long long)c->ndim * c->nloc;
+    const unsigned gv = (unsigned)((nv + 255) / 256);
+    hipLaunchKernelGGL(nsk::sens::k_add3, dim3(gv), dim3(256), 0, c->stream, outs[0], (const double*)tR, (const double*)pR, nv);
+    hipLaunchKernelGGL(nsk::sens::k_add3, dim3(gv), dim3(256), 0, c->stream, outs[1], (const double*)tI, (const double*)pI, nv);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int nsk_forced_map(nsk_ctx* c, int mode, nsk_vec fv, nsk_vec qv, nsk_vec force) {
+  int rc = sens_ctx_ok(c, "nsk_forced_map");
+  if (rc) return rc;
+  if (!fv || !qv || !force) return fail(NSK_EINVAL, "nsk_forced_map: bad argument");
+  if (mode != NSK_DIRECT && mode != NSK_ADJOINT) return fail(NSK_EINVAL, "nsk_forced_map: mode must be NSK_DIRECT or NSK_ADJOINT");
+  if (force == fv) return fail(NSK_EINVAL, "nsk_forced_map: the force may not be the output vector");
+  // eager time steps: the captured step graphs of the unforced maps stay as they are (and are not used here)
+  c->hstats = Stats{};
+  const int use_graph = c->use_graph;
+  c->force = (const double*)force;
+  c->use_graph = 0;
+  rc = run_map_adaptive(c, mode, (double*)fv, (const double*)qv);
+  c->use_graph = use_graph;
+  c->force = nullptr;
+  return rc;
 }
 
 // diagnostic (NSK_STAMPS build): run `reps` full pressure iterations' k_divgs and dump the stamps

@@ -1,0 +1,160 @@
+// Sensitivity post-processing on the device (core/sensitivity.f): wavemaker, base-flow sensitivity, biorthogonalisation,
+// and the steady body force of the forced linearised maps (core/utils.f:160-162).
+//
+// The base-flow sensitivity is linear in each mode's gradient times the other modes' values, so it is built one mode
+// COMPONENT at a time: k_sens_grad writes the element-local physical gradient of that component (ndim fields, gradm1 with
+// the metrics derived in the kernel from the GLL coordinates), k_sens_acc averages it over shared nodes (dsavg through the
+// gather tables of the dssum) and adds its products with the other modes' values into the outputs.  Scratch: ndim
+// velocity-sized fields (the context's state-sized scratch vector); nothing is kept between calls.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "nsk_dev.hpp"
+#include "nsk_kernels.hpp"
+
+namespace nsk {
+namespace sens {
+
+template <int N, int NDIM>
+struct SensCfg {
+  static constexpr int NP = NDIM == 3 ? N * N * N : N * N;     // GLL nodes of one element
+  static constexpr int NT = ((NP + 63) / 64) * 64;
+};
+
+// g[i * nloc + l] = d f / d x_i at the element-local node l (no averaging): (r_x f_r + s_x f_s [+ t_x f_t]) with the
+// inverse mapping from the coordinates' own derivatives (Nek5000 gradm1: cofactors over the Jacobian).  One workgroup per element.
+template <int N, int NDIM>
+__global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_sens_grad(const double* __restrict__ D, const double* __restrict__ xyz,
+                                                                    const double* __restrict__ f, double* __restrict__ g, long long nloc) {
+  constexpr int NP = SensCfg<N, NDIM>::NP;
+  __shared__ double sD[N * N];
+  __shared__ double sf[NP], sx[NP], sy[NP], sz[NDIM == 3 ? NP : 1];
+  const int tid = threadIdx.x;
+  const long long e0 = (long long)blockIdx.x * NP;
+  if (tid < N * N) sD[tid] = D[tid];
+  const bool act = tid < NP;
+  if (act) {
+    sf[tid] = f[e0 + tid];
+    sx[tid] = xyz[e0 + tid];
+    sy[tid] = xyz[nloc + e0 + tid];
+    if constexpr (NDIM == 3) sz[tid] = xyz[2 * nloc + e0 + tid];
+  }
+  __syncthreads();
+  if (!act) return;
+  const int i = tid % N, j = (tid / N) % N, k = NDIM == 3 ? tid / (N * N) : 0;
+  const int bj = NDIM == 3 ? (k * N * N + i) : i;           // line of constant (i, k) runs over j with stride N
+  const int bi = tid - i, bk = j * N + i;                   // line of constant (j, k) over i; of constant (i, j) over k (stride N*N)
+  double fr = 0, fs = 0, ft = 0, xr = 0, xs = 0, xt = 0, yr = 0, ys = 0, yt = 0, zr = 0, zs = 0, zt = 0;
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    const double di = sD[i * N + q], dj = sD[j * N + q];
+    fr += di * sf[bi + q]; xr += di * sx[bi + q]; yr += di * sy[bi + q];
+    fs += dj * sf[bj + q * N]; xs += dj * sx[bj + q * N]; ys += dj * sy[bj + q * N];
+    if constexpr (NDIM == 3) {
+      const double dk = sD[k * N + q];
+      zr += di * sz[bi + q]; zs += dj * sz[bj + q * N];
+      ft += dk * sf[bk + q * N * N]; xt += dk * sx[bk + q * N * N]; yt += dk * sy[bk + q * N * N]; zt += dk * sz[bk + q * N * N];
+    }
+  }
+  const long long l = e0 + tid;
+  if constexpr (NDIM == 2) {
+    const double jinv = 1.0 / (xr * ys - xs * yr);
+    g[l] = (ys * fr - yr * fs) * jinv;                      // r_x = y_s / J, s_x = -y_r / J
+    g[nloc + l] = (xr * fs - xs * fr) * jinv;               // r_y = -x_s / J, s_y = x_r / J
+  } else {
+    const double c_rx = ys * zt - yt * zs, c_ry = xt * zs - xs * zt, c_rz = xs * yt - xt * ys;
+    const double c_sx = yt * zr - yr * zt, c_sy = xr * zt - xt * zr, c_sz = xt * yr - xr * yt;
+    const double c_tx = yr * zs - ys * zr, c_ty = xs * zr - xr * zs, c_tz = xr * ys - xs * yr;
+    const double jinv = 1.0 / (xr * c_rx + yr * c_ry + zr * c_rz);
+    g[l] = (c_rx * fr + c_sx * fs + c_tx * ft) * jinv;
+    g[nloc + l] = (c_ry * fr + c_sy * fs + c_ty * ft) * jinv;
+    g[2 * nloc + l] = (c_rz * fr + c_sz * fs + c_tz * ft) * jinv;
+  }
+}
+
+template <int N, int NDIM>
+inline void launch_sens_grad(hipStream_t st, int nel, const double* D, const double* xyz, const double* f, double* g, long long nloc) {
+  hipLaunchKernelGGL((k_sens_grad<N, NDIM>), dim3(nel), dim3(SensCfg<N, NDIM>::NT), 0, st, D, xyz, f, g, nloc);
+}
+
+// Accumulation of one mode component's averaged gradient G_i = dsavg(g_i) (sensitivity.f:215-256, Marquet et al. 2008):
+//   transport (the mode is direct, component j):      outR_i += wR sR_j G_i,         outI_i += wI sI_j G_i
+//   production (the mode is adjoint, component i):     outR_i += wR sum_j sR_j G_j,   outI_i += wI sum_j sI_j G_j
+// s* are velocity fields with component stride nloc (the other mode's values), out* the output vectors.
+struct SensAcc {
+  const double *sR, *sI;
+  double *outR, *outI;
+  double wR, wI;
+  int comp, production;
+};
+
+template <int NDIM>
+__global__ void k_sens_acc(const Dev d, const double* __restrict__ g, const SensAcc a) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= d.nloc) return;
+  const long long n = d.nloc;
+  const double mi = d.minv[l];
+  double G[NDIM];
+#pragma unroll
+  for (int q = 0; q < NDIM; ++q) G[q] = gs_gather(g + q * n, d, l) * mi;
+  if (!a.production) {
+    const double cr = a.wR * a.sR[a.comp * n + l], ci = a.wI * a.sI[a.comp * n + l];
+#pragma unroll
+    for (int q = 0; q < NDIM; ++q) {
+      a.outR[q * n + l] += cr * G[q];
+      a.outI[q * n + l] += ci * G[q];
+    }
+  } else {
+    double r = 0.0, m = 0.0;
+#pragma unroll
+    for (int q = 0; q < NDIM; ++q) {
+      r += a.sR[q * n + l] * G[q];
+      m += a.sI[q * n + l] * G[q];
+    }
+    a.outR[a.comp * n + l] += a.wR * r;
+    a.outI[a.comp * n + l] += a.wI * m;
+  }
+}
+
+// wave_maker (sensitivity.f:70-72): |d| |a| pointwise, velocity components only
+__global__ void k_wavemaker(const double* __restrict__ dR, const double* __restrict__ dI, const double* __restrict__ aR,
+                            const double* __restrict__ aI, double* __restrict__ wm, long long nloc, int ndim) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= nloc) return;
+  double sd = 0.0, sa = 0.0;
+  for (int c = 0; c < ndim; ++c) {
+    const long long o = c * nloc + l;
+    sd += dR[o] * dR[o] + dI[o] * dI[o];
+    sa += aR[o] * aR[o] + aI[o] * aI[o];
+  }
+  wm[l] = sqrt(sd) * sqrt(sa);
+}
+
+// biorthogonalize (sensitivity.f:487-501): a <- a / conj(gamma + i delta), i.e. aR' = p aR - q aI, aI' = p aI + q aR
+// with p = gamma / (gamma^2 + delta^2), q = delta / (gamma^2 + delta^2)
+__global__ void k_cdiv(double* __restrict__ aR, double* __restrict__ aI, double p, double q, long long n) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= n) return;
+  const double r = aR[l], m = aI[l];
+  aR[l] = p * r - q * m;
+  aI[l] = p * m + q * r;
+}
+
+// out = a + b over n entries (sr = tr + pr, si = ti + pi)
+__global__ void k_add3(double* __restrict__ out, const double* __restrict__ a, const double* __restrict__ b, long long n) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l < n) out[l] = a[l] + b[l];
+}
+
+// Steady body force of a forced map (nekStab_forcing, core/utils.f:160-162, made mass-weighted by makeuf): bf += B f,
+// after the convection kernel has written this step's sponge + convection term and before the EXT extrapolation reads it.
+__global__ void k_add_force(double* __restrict__ bf, long long cs, const double* __restrict__ bm1, const double* __restrict__ f,
+                            long long nloc, int ndim) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= nloc) return;
+  const double b = bm1[l];
+  for (int c = 0; c < ndim; ++c) bf[c * cs + l] += b * f[c * nloc + l];
+}
+
+}  // namespace sens
+}  // namespace nsk

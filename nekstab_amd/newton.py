@@ -15,8 +15,9 @@ from .capi import NSK_NEWTON
 from . import krylov
 
 
-def ts_gmres(be, rhs, sol, k_dim, tol, maxiter=100, log=None):
-    """GMRES on (exp(LT) - I) with the reference's restart logic; returns matvec count."""
+def ts_gmres(be, rhs, sol, k_dim, tol, maxiter=100, log=None, mode=NSK_NEWTON):
+    """GMRES on (exp(LT) - I) with the reference's restart logic; returns matvec count.  ``mode``: the map whose system is
+    solved (NSK_NEWTON; NSK_FORCE_SENSITIVITY, (I - exp(L^+ T)), for ts_steady_force_sensitivity)."""
     Q = be.alloc(k_dim + 1)
     dq, f = be.alloc(2)
     be.zero(sol)
@@ -30,7 +31,7 @@ def ts_gmres(be, rhs, sol, k_dim, tol, maxiter=100, log=None):
         evec[0] = beta
         k_used = k_dim
         for k in range(1, k_dim + 1):
-            krylov.arnoldi_factorization(be, Q, H, k, k, NSK_NEWTON)            # one column at a time (:255)
+            krylov.arnoldi_factorization(be, Q, H, k, k, mode)                  # one column at a time (:255)
             y = np.linalg.lstsq(H[:k + 1, :k], evec[:k + 1], rcond=None)[0]      # lstsq -> dgels (:258)
             res = np.linalg.norm(evec[:k + 1] - H[:k + 1, :k] @ y)
             calls += 1
@@ -42,7 +43,7 @@ def ts_gmres(be, rhs, sol, k_dim, tol, maxiter=100, log=None):
         be.basis_gemv(Q[:k_used], y[:k_used], dq)                               # krylov_matmul (:275)
         be.axpy(sol, 1.0, dq)
         # sanity residual and new seed: f = rhs - A sol  (initialize_gmres_vector)
-        be.matvec(f, sol, NSK_NEWTON)
+        be.matvec(f, sol, mode)
         calls += 1
         be.axpy(f, -1.0, rhs)
         be.scal(f, -1.0)

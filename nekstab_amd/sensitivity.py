@@ -1,0 +1,246 @@
+"""Sensitivity post-processing of direct and adjoint modes, restating core/sensitivity.f (uparam(1) = 4.x):
+
+    wave_maker                       4.2   Giannetti & Luchini (2007), structural sensitivity |d| |a|
+    bf_sensitivity                   4.3   Marquet, Sipp & Jacquin (2008), sensitivity to base-flow modifications
+    ts_steady_force_sensitivity      4.41 / 4.42   sensitivity to a steady force: GMRES on (I - exp(L^+ T))
+    delta_forcing                    4.43  eigenvalue drift under a steady force proportional to the base flow (eq. 5.1)
+
+The fields are computed on the device (nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity, nsk_forced_map); delta_forcing
+is pointwise and stays on the host.  Output files carry the reference's prefixes (wm_, tr_, ti_, pr_, pi_, sr_, si_, fsr, fsi,
+dfr) so that nekStab's own scripts read them.  ``np_*`` functions are the numpy restatement the device is tested against.
+
+Two departures from the reference, both deliberate:
+  * in 3-D the transport term uses d v / d z where core/sensitivity.f:219, 222, 228, 231 read d w / d z (Marquet's formula;
+    the two agree in 2-D and on z-invariant fields);
+  * biorthogonalisation scales the direct mode's pressure with its velocity (the reference passes one shared pressure array).
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from . import nekio, newton
+from .capi import NSK_ADJOINT, NSK_FORCE_SENSITIVITY
+from .quadrature import deriv_matrix, gauss_legendre, gauss_lobatto_legendre, interp_matrix
+
+
+def fld_name(prefix: str, session: str, num: int = 1) -> str:
+    """Nek's outpost file name: prefix + session + '0.f' + 5-digit number (e.g. sr_1cyl0.f00001)."""
+    return "%s%s0.f%05d" % (prefix, session, num)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# mode files at another polynomial order (load_fld interpolates GLL -> GLL on read)
+# ----------------------------------------------------------------------------------------------------------------------
+
+def interp_gll(f: np.ndarray, lx_to: int, *, ndim: int = 2) -> np.ndarray:
+    """(..., [nz,] ny, nx) element fields on GLL(lx_from) points -> GLL(lx_to), tensor-product interpolation per element."""
+    lx_from = f.shape[-1]
+    if lx_from == lx_to:
+        return np.array(f, dtype=np.float64)
+    J = interp_matrix(gauss_lobatto_legendre(lx_from)[0], gauss_lobatto_legendre(lx_to)[0])
+    if ndim == 2:
+        return np.einsum("ai,bj,...ji->...ba", J, J, f, optimize=True)
+    return np.einsum("ai,bj,ck,...kji->...cba", J, J, J, f, optimize=True)
+
+
+def gll_to_gauss(p: np.ndarray, lx1: int, *, ndim: int = 2) -> np.ndarray:
+    """Pressure stored on GLL(lx_from) points (field files) -> the lx1 - 2 Gauss points of the state vector."""
+    J = interp_matrix(gauss_lobatto_legendre(p.shape[-1])[0], gauss_legendre(lx1 - 2)[0])
+    if ndim == 2:
+        return np.einsum("ai,bj,...ji->...ba", J, J, p, optimize=True)
+    return np.einsum("ai,bj,ck,...kji->...cba", J, J, J, p, optimize=True)
+
+
+def load_mode(path: str, lx1: int):
+    """A mode file (dRe / dIm / aRe / aIm ...) at order lx1, whatever order it was written at: (u [ndim, nel, ...], p on the
+    lx1 - 2 Gauss points or None).  core/sensitivity.f reads lx1 = 6 direct and lx1 = 8 adjoint files in one case."""
+    fld = nekio.read_fld(path)
+    ndim = 3 if fld.nz > 1 else 2
+    u = fld.u if ndim == 3 else fld.u[:, :, 0]
+    u = interp_gll(u, lx1, ndim=ndim)
+    p = None
+    if fld.p is not None:
+        p0 = fld.p if ndim == 3 else fld.p[:, 0]
+        p = gll_to_gauss(p0, lx1, ndim=ndim)
+    return u, p
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# numpy restatement (the yardstick of the device entries)
+# ----------------------------------------------------------------------------------------------------------------------
+
+class NpGeom:
+    """GLL-mesh geometry of a case: mass matrix bm1 / bm1s, gradm1 and dsavg (Nek5000 restated in numpy)."""
+
+    def __init__(self, case):
+        self.ndim = int(getattr(case, "ndim", 2))
+        n = case.lx1
+        z, w = gauss_lobatto_legendre(n)
+        self.D = deriv_matrix(z)
+        self.gid = np.asarray(case.gid, dtype=np.int64)
+        self.nglob = int(case.nglob)
+        X = [np.asarray(case.x, dtype=np.float64), np.asarray(case.y, dtype=np.float64)]
+        if self.ndim == 3:
+            X.append(np.asarray(case.z, dtype=np.float64))
+        J = np.array([self._drst(a) for a in X])          # J[a][r] = d x_a / d r_r
+        if self.ndim == 2:
+            self.jac = J[0][0] * J[1][1] - J[0][1] * J[1][0]
+            inv = [[J[1][1], -J[0][1]], [-J[1][0], J[0][0]]]            # inv[r][a] * jac = d r_r / d x_a
+        else:
+            cof = lambda a, r: (J[(a + 1) % 3][(r + 1) % 3] * J[(a + 2) % 3][(r + 2) % 3]
+                                - J[(a + 1) % 3][(r + 2) % 3] * J[(a + 2) % 3][(r + 1) % 3])
+            self.jac = sum(J[0][r] * cof(0, r) for r in range(3))
+            inv = [[cof(a, r) for a in range(3)] for r in range(3)]
+        self.inv = [[inv[r][a] / self.jac for a in range(self.ndim)] for r in range(self.ndim)]
+        W = w[:, None] * w[None, :] if self.ndim == 2 else w[:, None, None] * w[None, :, None] * w[None, None, :]
+        self.bm1 = self.jac * W
+        self.bm1s = np.where(np.asarray(case.spng) != 0.0, 0.0, self.bm1)
+        self.mult = np.bincount(self.gid.ravel(), minlength=self.nglob)[self.gid]
+
+    def _drst(self, f):
+        D = self.D
+        if self.ndim == 2:
+            return [f @ D.T, np.einsum("jq,eqi->eji", D, f)]
+        return [np.einsum("iq,ekjq->ekji", D, f), np.einsum("jq,ekqi->ekji", D, f), np.einsum("kq,eqji->ekji", D, f)]
+
+    def grad(self, f):
+        """gradm1: [d f / d x_a] on the element-local nodes."""
+        dr = self._drst(f)
+        return [sum(self.inv[r][a] * dr[r] for r in range(self.ndim)) for a in range(self.ndim)]
+
+    def dsavg(self, f):
+        g = np.bincount(self.gid.ravel(), weights=f.ravel(), minlength=self.nglob)[self.gid]
+        return g / self.mult
+
+    def inner(self, a, b, w=None):
+        w = self.bm1s if w is None else w
+        return float(sum(np.sum(x * w * y) for x, y in zip(a, b)))
+
+
+def np_biorthogonalize(geom: NpGeom, dRe, dIm, aRe, aIm):
+    """biorthogonalize (core/sensitivity.f:428-504) on velocity fields: returns (dRe, dIm, aRe, aIm, gamma, delta)."""
+    s = 1.0 / np.sqrt(geom.inner(dRe, dRe) + geom.inner(dIm, dIm))
+    dRe, dIm = np.asarray(dRe) * s, np.asarray(dIm) * s
+    gamma = geom.inner(aRe, dRe) + geom.inner(aIm, dIm)
+    delta = geom.inner(aRe, dIm) - geom.inner(aIm, dRe)
+    den = gamma ** 2 + delta ** 2
+    aRe, aIm = np.asarray(aRe), np.asarray(aIm)
+    return dRe, dIm, (gamma * aRe - delta * aIm) / den, (gamma * aIm + delta * aRe) / den, gamma, delta
+
+
+def np_wavemaker(dRe, dIm, aRe, aIm):
+    return np.sqrt(np.sum(np.asarray(dRe) ** 2 + np.asarray(dIm) ** 2, axis=0)) * \
+        np.sqrt(np.sum(np.asarray(aRe) ** 2 + np.asarray(aIm) ** 2, axis=0))
+
+
+def np_bf_sensitivity(geom: NpGeom, dRe, dIm, aRe, aIm):
+    """bf_sensitivity (core/sensitivity.f:93-284) on biorthogonalised velocity fields: dict of tr, ti, pr, pi, sr, si,
+    each [ndim, nel, ...].  G[c][a] = dsavg(d u_c / d x_a)."""
+    nd = geom.ndim
+    G = {k: [[geom.dsavg(g) for g in geom.grad(m[c])] for c in range(nd)]
+         for k, m in (("dRe", dRe), ("dIm", dIm), ("aRe", aRe), ("aIm", aIm))}
+    tr = np.array([-sum(aRe[j] * G["dRe"][j][i] + aIm[j] * G["dIm"][j][i] for j in range(nd)) for i in range(nd)])
+    ti = np.array([sum(aRe[j] * G["dIm"][j][i] - aIm[j] * G["dRe"][j][i] for j in range(nd)) for i in range(nd)])
+    pr = np.array([sum(dRe[j] * G["aRe"][i][j] + dIm[j] * G["aIm"][i][j] for j in range(nd)) for i in range(nd)])
+    pi = np.array([sum(dRe[j] * G["aIm"][i][j] - dIm[j] * G["aRe"][i][j] for j in range(nd)) for i in range(nd)])
+    return dict(tr=tr, ti=ti, pr=pr, pi=pi, sr=tr + pr, si=ti + pi)
+
+
+def delta_forcing(ub, fsr, fsi, alpha=1.0):
+    """delta_forcing (core/sensitivity.f, uparam(1) = 4.43): eigenvalue drift of a steady force alpha |U| U, pointwise:
+    (delta_lambda, delta_omega) = (-alpha |U| fsr . U, alpha |U| fsi . U)."""
+    ub, fsr, fsi = (np.asarray(a, dtype=np.float64) for a in (ub, fsr, fsi))
+    work = np.sqrt(np.sum(ub ** 2, axis=0))
+    return -alpha * work * np.sum(fsr * ub, axis=0), alpha * work * np.sum(fsi * ub, axis=0)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# device drivers
+# ----------------------------------------------------------------------------------------------------------------------
+
+def upload_velocity(h, v, u, p=None):
+    """u [ndim, nel, ...] (and p on the Gauss points, default 0) into the device vector v."""
+    if p is None:
+        p = np.zeros((h.nel,) + (h.lx2,) * h.ndim)
+    if h.ndim == 3:
+        h.upload3(v, u[0], u[1], u[2], p)
+    else:
+        h.upload(v, u[0], u[1], p)
+
+
+def download_velocity(h, v):
+    out = h.download3(v) if h.ndim == 3 else h.download(v)
+    return np.array(out[:h.ndim])
+
+
+def _coords(h):
+    k = h._keep
+    X = [k["x"], k["y"]] + ([k["z"]] if h.ndim == 3 else [])
+    return np.array([np.asarray(a).reshape((h.nel,) + (h.lx1,) * h.ndim) for a in X])
+
+
+def _write(h, path, *, u=None, t=None):
+    """outpost: coordinates + velocity (or a scalar in the temperature slot), arrays as (ncomp, nel, nz, ny, nx)."""
+    ex = (lambda a: a[..., None, :, :]) if h.ndim == 2 else (lambda a: a)
+    nekio.write_fld(path, x=ex(_coords(h)), u=None if u is None else ex(np.asarray(u)), t=None if t is None else ex(np.asarray(t)))
+
+
+def wave_maker(h, dRe, dIm, aRe, aIm, *, outdir=None, session="1cyl"):
+    """uparam(1) = 4.2.  Modes as device vectors (biorthogonalised in place).  Returns (field [nel, ...], (gamma, delta));
+    writes wm_<session>0.f00001 into ``outdir`` when given."""
+    gd = h.biorthogonalize(dRe, dIm, aRe, aIm)
+    (wm,) = h.alloc(1)
+    try:
+        h.wavemaker(dRe, dIm, aRe, aIm, wm)
+        field = download_velocity(h, wm)[0]
+    finally:
+        h.free([wm])
+    if outdir is not None:
+        _write(h, os.path.join(outdir, fld_name("wm_", session)), t=field)
+    return field, gd
+
+
+def bf_sensitivity(h, dRe, dIm, aRe, aIm, *, outdir=None, session="1cyl"):
+    """uparam(1) = 4.3.  Modes as device vectors (biorthogonalised in place).  Returns (dict of tr, ti, pr, pi, sr, si velocity
+    fields, (gamma, delta)); writes tr_ ti_ pr_ pi_ sr_ si_ files into ``outdir`` when given."""
+    gd = h.biorthogonalize(dRe, dIm, aRe, aIm)
+    vecs = h.alloc(6)
+    try:
+        h.bf_sensitivity(dRe, dIm, aRe, aIm, vecs[0], vecs[1], parts=vecs[2:])
+        out = {k: download_velocity(h, v) for k, v in zip(("sr", "si", "tr", "ti", "pr", "pi"), vecs)}
+    finally:
+        h.free(vecs)
+    if outdir is not None:
+        for k in ("tr", "ti", "pr", "pi", "sr", "si"):
+            _write(h, os.path.join(outdir, fld_name(k + "_", session)), u=out[k])
+    return out, gd
+
+
+def steady_force_sensitivity(h, force, *, k_dim=100, tol=None, maxiter=10, log=None, outdir=None, session="1cyl",
+                             prefix="fsr"):
+    """uparam(1) = 4.41 (force = sr, prefix fsr) / 4.42 (force = si, prefix fsi): ts_steady_force_sensitivity.
+    rhs = forced adjoint map of 0 under ``force`` (a device vector), normalised; GMRES on (I - exp(L^+ T)) x = rhs with the
+    reference's ts_gmres(rhs, sol, 10, k_dim); x scaled back.  ``tol`` is the reference's max(param(21), param(22)) on the
+    SQUARED residual (default 1e-12).  Returns (device vector x -- free it with h.free --, linearised-map calls)."""
+    rhs, sol, zero = h.alloc(3)
+    try:
+        h.zero(zero)
+        h.forced_map(rhs, zero, force, NSK_ADJOINT)               # initialize_rhs_ts_steady_force_sensitivity
+        alpha = h.norm(rhs)                                       # krylov_normalize
+        h.scal(rhs, 1.0 / alpha)
+        calls = newton.ts_gmres(h, rhs, sol, k_dim, 1e-12 if tol is None else tol, maxiter=maxiter, log=log,
+                                mode=NSK_FORCE_SENSITIVITY)
+        h.scal(sol, alpha)
+    finally:
+        h.free([rhs, zero])
+    if outdir is not None:
+        _write(h, os.path.join(outdir, fld_name(prefix, session)), u=download_velocity(h, sol))
+    return sol, calls
+
+
+def write_delta_forcing(h, path, dl, dw):
+    """dfr file of delta_forcing: (delta_lambda, delta_omega [, 0]) in the velocity slots."""
+    u = [dl, dw] + ([np.zeros_like(dl)] if h.ndim == 3 else [])
+    _write(h, path, u=np.array(u))
