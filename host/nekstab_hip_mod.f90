@@ -258,6 +258,16 @@ module nekstab_hip
       type(c_ptr), value :: q
       type(c_ptr), value :: force
     end function
+    ! stability_energy_budget (core/postproc.f:657-872, uparam(1) = 4.1).  prod: c_null_ptr or c_loc of a type(c_ptr) array
+    ! of ndim vectors; diss: c_null_ptr or a vector; integrals(10): P(1,1:3), P(2,1:3), P(3,1:3), D
+    integer(c_int) function nsk_energy_budget(ctx, ub, dRe, dIm, prod, diss, integrals) bind(c, name='nsk_energy_budget')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: ub, dRe, dIm
+      type(c_ptr), value :: prod
+      type(c_ptr), value :: diss
+      real(c_double), dimension(*) :: integrals
+    end function
     integer(c_int) function nsk_clone(ctx, lane) bind(c, name='nsk_clone')
       import
       type(c_ptr), value :: ctx

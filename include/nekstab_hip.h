@@ -190,7 +190,7 @@ int nsk_basis_gemv(nsk_ctx* ctx, const nsk_vec* Q, int k, const double* y_re,
 /* add_noise seed (core/utils.f:344-408): deterministic pseudo-noise, dssum-averaged, masked */
 int nsk_seed_noise(nsk_ctx* ctx, nsk_vec v);
 
-/* ---- sensitivity post-processing (core/sensitivity.f; uparam(1) = 4.2, 4.3, 4.41 / 4.42) ----
+/* ---- sensitivity post-processing (core/sensitivity.f; uparam(1) = 4.2, 4.3, 4.41 / 4.42) and the energy budget (4.1) ----
  * Single-rank full-mesh contexts, quadrilaterals and hexahedra; shard and rank-local contexts return NSK_EINVAL.
  * Inner products are the bm1s-weighted velocity products of nsk_dot. */
 /* biorthogonalize (core/sensitivity.f:428-504), in place: d <- d / ||d|| (||d||^2 = ||dRe||^2 + ||dIm||^2; the whole vector is
@@ -213,6 +213,17 @@ int nsk_bf_sensitivity(nsk_ctx* ctx, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_
  * initialize_rhs_ts_steady_force_sensitivity (core/sensitivity.f:380-422) is the adjoint map with q = 0.  The time steps run
  * eagerly (the captured step graphs belong to the unforced maps); force = 0 gives the bits of nsk_matvec. */
 int nsk_forced_map(nsk_ctx* ctx, int mode, nsk_vec f, nsk_vec q, nsk_vec force);
+/* stability_energy_budget (core/postproc.f:657-872, uparam(1) = 4.1) of the direct mode dRe + i dIm about the base flow ub
+ * (velocity of a state vector).  prod: NULL or ndim vectors, vector c holding P[c][1..ndim] in its velocity components;
+ * diss: NULL or a vector receiving D in its first component; integrals[10]: bm1-weighted sums (reference order).
+ * Pressure and unused components of every output are 0; inputs are not modified.
+ *   P[c][j] = -1/2 (uR_c uR_j + uI_c uI_j) dU_c/dx_j    (gradm1 of the base flow, element-local: no dsavg)
+ *   D = 1/2 nu sum_j (uR_j Lap uR_j + uI_j Lap uI_j),  Lap a = dsavg(sum_i d/dx_i dsavg(d a/dx_i)),  nu = 1/Re
+ * integrals = {P[1][1..3], P[2][1..3], P[3][1..3], D} (2-D: entries of a third component or direction are 0).  The mode enters
+ * divided by alpha = sqrt(||dRe||^2 + ||dIm||^2) (nsk_dot's product), so the budget does not depend on the mode's scale: the
+ * reference's comment says "normalize to unit-norm" where its code multiplies by alpha (postproc.f:703-707; the two agree when
+ * alpha = 1).  A zero mode returns NSK_EINVAL. */
+int nsk_energy_budget(nsk_ctx* ctx, nsk_vec ub, nsk_vec dRe, nsk_vec dIm, nsk_vec* prod, nsk_vec diss, double* integrals);
 
 /* ---- lanes: independent maps in flight at once on one GPU ----
  * nsk_clone gives a context a second LANE: its own stream, time-stepper state, solver work arrays and projection space; geometry,

@@ -109,6 +109,7 @@ SYMBOLS = {
     "nsk_wavemaker": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "nsk_bf_sensitivity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vpp]),
     "nsk_forced_map": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "nsk_energy_budget": (C.c_int, [_vp, _vp, _vp, _vp, _vpp, _vp, _dp]),
     "nsk_bench_kernel": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),
     "nsk_get_step_iters": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nsk_get_stats": (C.c_int, [_vp, C.POINTER(NskStats)]),
@@ -377,6 +378,17 @@ class NekStabHip:
     def forced_map(self, f, q, force, mode=NSK_ADJOINT):
         """f = linearised map of q under the steady body force ``force`` (nsk_forced_map)."""
         self._chk(self.lib.nsk_forced_map(self.ctx, int(mode), f, q, force))
+
+    def energy_budget(self, ub, dRe, dIm, prod=None, diss=None):
+        """stability_energy_budget (nsk_energy_budget): the 10 bm1-weighted integrals P[1][1..3], P[2][1..3], P[3][1..3], D of
+        the mode dRe + i dIm (taken at unit norm) about the base flow ub; ``prod`` = ndim vectors receive P[c][1..ndim], ``diss``
+        receives D in its first component.  The inputs are not modified."""
+        if prod is not None and len(prod) != self.ndim:
+            raise ValueError("energy_budget: prod needs %d vectors" % self.ndim)
+        arr = (C.c_void_p * len(prod))(*[v.value for v in prod]) if prod is not None else None
+        out = np.zeros(10)
+        self._chk(self.lib.nsk_energy_budget(self.ctx, ub, dRe, dIm, arr, diss, _p(out)))
+        return out
 
     # Lanes (nsk_clone) hold their solver settings BY VALUE: a setter called after lanes exist acts on every lane, so that
     # matvec_batch / band_arnoldi never apply different operators on different lanes (ADVICE r3).

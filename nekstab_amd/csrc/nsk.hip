@@ -186,6 +186,7 @@ struct nsk_ctx {
   double* scratch = nullptr;            // one state vector
   const double* xyz = nullptr;          // GLL coordinates [ndim][nloc] (nsk_seed_noise)
   const double* force = nullptr;        // steady body force [ndim][nloc] of the running forced map (nsk_forced_map; eager steps only), else null
+  double* budget_wrk = nullptr;         // nsk_energy_budget: divergence field [nloc], per-workgroup partials, 10 sums (first call; freed with the context)
   double* rc_big = nullptr;             // coarse restriction for nvert > 3072
   Dev d{};
   Stats hstats{};
@@ -3072,6 +3073,77 @@ int nsk_bf_sensitivity(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_ve
     hipLaunchKernelGGL(nsk::sens::k_add3, dim3(gv), dim3(256), 0, c->stream, outs[1], (const double*)tI, (const double*)pI, nv);
   }
   HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// stability_energy_budget (core/postproc.f:657-872): 1 + 6 ndim launches + 2 reductions, one workspace allocated once per context
+extern "C++" {
+template <int N, int NDIM>
+static void energy_budget_launch(nsk_ctx* c, const double* ub, const double* uR, const double* uI, double* const* prod, double* diss,
+                                 double s, double* wrk) {
+  const long long n = c->nloc;
+  const int nb = (int)((n + 255) / 256);
+  double* div = wrk;
+  double* ppart = wrk + n;                                       // [9][nel]
+  double* dpart = ppart + 9 * (size_t)c->nel;                    // [2 ndim][nb]
+  double* out = dpart + 2 * NDIM * (size_t)nb;                   // [10]
+  nsk::sens::BudgetProd bp{{prod ? prod[0] : nullptr, prod ? prod[1] : nullptr, prod && NDIM == 3 ? prod[2] : nullptr}};
+  hipLaunchKernelGGL((nsk::sens::k_budget_prod<N, NDIM>), dim3(c->nel), dim3(nsk::sens::SensCfg<N, NDIM>::NT), 0, c->stream, c->d.D,
+                     c->xyz, ub, uR, uI, c->d.bm1, bp, -0.5 * s, ppart, n);
+  const double wd = 0.5 * c->d.nu * s;                           // param(2) / param(1) = 1 / Re
+  for (int k = 0; k < 2 * NDIM; ++k) {                           // u_R,x  u_I,x  u_R,y  u_I,y [ u_R,z  u_I,z ]
+    const double* a = ((k & 1) ? uI : uR) + (size_t)(k >> 1) * n;
+    nsk::sens::launch_sens_grad<N, NDIM>(c->stream, c->nel, c->d.D, c->xyz, a, c->scratch, n);
+    hipLaunchKernelGGL((nsk::sens::k_budget_div<N, NDIM>), dim3(c->nel), dim3(nsk::sens::SensCfg<N, NDIM>::NT), 0, c->stream, c->d,
+                       c->xyz, (const double*)c->scratch, div);
+    hipLaunchKernelGGL(nsk::sens::k_budget_diss, dim3(nb), dim3(256), 0, c->stream, c->d, (const double*)div, a, diss, wd, k == 0 ? 1 : 0,
+                       dpart + (size_t)k * nb);
+  }
+  hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)ppart, 9, c->nel, out);
+  hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)dpart, 1, 2 * NDIM * nb, out + 9);
+}
+}  // extern "C++"
+
+int nsk_energy_budget(nsk_ctx* c, nsk_vec ub, nsk_vec dRe, nsk_vec dIm, nsk_vec* prod, nsk_vec diss, double* integrals) {
+  int rc = sens_ctx_ok(c, "nsk_energy_budget");
+  if (rc) return rc;
+  if (!ub || !dRe || !dIm || !integrals) return fail(NSK_EINVAL, "nsk_energy_budget: bad argument (ub, dRe, dIm and integrals are required)");
+  if (prod) for (int k = 0; k < c->ndim; ++k) if (!prod[k]) return fail(NSK_EINVAL, "nsk_energy_budget: prod needs ndim vectors");
+  if (!c->xyz || !c->scratch) return fail(NSK_EINVAL, "nsk_energy_budget: context holds no coordinates");
+  std::vector<const void*> outs;
+  if (prod) outs.insert(outs.end(), prod, prod + c->ndim);
+  if (diss) outs.push_back(diss);
+  for (const void* o : outs)
+    if (o == ub || o == dRe || o == dIm) return fail(NSK_EINVAL, "nsk_energy_budget: an output may not be one of the inputs");
+  if (!distinct(outs)) return fail(NSK_EINVAL, "nsk_energy_budget: the outputs must be distinct vectors");
+  if (c->key != 6 && c->key != 8 && c->key != 10 && c->key != 12 && c->key != 106 && c->key != 108 && c->key != 110)
+    return fail(NSK_EINVAL, "nsk_energy_budget: unsupported lx1");
+  double a = 0, b = 0;                                           // alpha^2 = ||dRe||^2 + ||dIm||^2  (postproc.f:703-707)
+  if ((rc = nsk_dot(c, dRe, dRe, &a)) || (rc = nsk_dot(c, dIm, dIm, &b))) return rc;
+  if (!(a + b > 0.0)) return fail(NSK_EINVAL, "nsk_energy_budget: the direct mode is zero");
+  // the mode divided by alpha (the reference's comment; its code multiplies): every term is quadratic in the mode, so the scale
+  // enters as 1 / alpha^2 on the weights and the inputs are left as they are
+  const double s = 1.0 / (a + b);
+  const long long nb = (c->nloc + 255) / 256;
+  if (!c->budget_wrk && (rc = dalloc(c, &c->budget_wrk, (size_t)(c->nloc + 9LL * c->nel + 2LL * c->ndim * nb + 10)))) return rc;
+  const long long nv = (long long)c->ndim * c->nloc;
+  if (prod) for (int k = 0; k < c->ndim; ++k) HIPCHK(hipMemsetAsync((double*)prod[k] + nv, 0, (c->nstate - nv) * sizeof(double), c->stream));
+  if (diss) HIPCHK(hipMemsetAsync((double*)diss + c->nloc, 0, (c->nstate - c->nloc) * sizeof(double), c->stream));
+  double* const* pv = (double* const*)prod;
+  const double *u = (const double*)ub, *r = (const double*)dRe, *m = (const double*)dIm;
+  switch (c->key) {
+    case 6: energy_budget_launch<6, 2>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
+    case 8: energy_budget_launch<8, 2>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
+    case 10: energy_budget_launch<10, 2>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
+    case 12: energy_budget_launch<12, 2>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
+    case 106: energy_budget_launch<6, 3>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
+    case 108: energy_budget_launch<8, 3>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
+    default: energy_budget_launch<10, 3>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
+  }
+  HIPCHK(hipGetLastError());
+  const double* out = c->budget_wrk + c->nloc + 9LL * c->nel + 2LL * c->ndim * nb;
+  HIPCHK(hipMemcpyAsync(integrals, out, 10 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }

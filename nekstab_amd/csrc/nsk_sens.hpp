@@ -1,5 +1,6 @@
 // Sensitivity post-processing on the device (core/sensitivity.f): wavemaker, base-flow sensitivity, biorthogonalisation,
-// and the steady body force of the forced linearised maps (core/utils.f:160-162).
+// the steady body force of the forced linearised maps (core/utils.f:160-162), and the stability energy budget
+// (core/postproc.f:657-872, at the end of this file).
 //
 // The base-flow sensitivity is linear in each mode's gradient times the other modes' values, so it is built one mode
 // COMPONENT at a time: k_sens_grad writes the element-local physical gradient of that component (ndim fields, gradm1 with
@@ -154,6 +155,173 @@ __global__ void k_add_force(double* __restrict__ bf, long long cs, const double*
   if (l >= nloc) return;
   const double b = bm1[l];
   for (int c = 0; c < ndim; ++c) bf[c * cs + l] += b * f[c * nloc + l];
+}
+
+// ---- stability_energy_budget (core/postproc.f:657-872, uparam(1) = 4.1) ------------------------------------------------
+// Production P[c][j] = w uu_cj dU_c/dx_j (w = -1/2 / ||u||^2, uu_cj = uR_c uR_j + uI_c uI_j, base-flow gradient element-local:
+// gradm1 without dsavg) by k_budget_prod; dissipation D = 1/2 nu / ||u||^2 sum over the 2 ndim mode components a of a Lap(a),
+// Lap(a) = dsavg(sum_i d/dx_i dsavg(d a / dx_i)), one component at a time: k_sens_grad (gradient into scratch), k_budget_div
+// (gather-average of the gradient, divergence, element-local), k_budget_diss (gather-average of the divergence, product,
+// accumulation).  Every kernel writes bm1-weighted per-workgroup partials; k_reduce_final sums them in a fixed order.
+
+// inverse mapping at element-local node tid: m[r][a] = d r_r / d x_a (cofactors over the Jacobian, as k_sens_grad)
+template <int N, int NDIM>
+__device__ inline void elem_inv_metric(const double* sD, const double* sx, const double* sy, const double* sz, int tid,
+                                       double (&m)[NDIM][NDIM]) {
+  const int i = tid % N, j = (tid / N) % N, k = NDIM == 3 ? tid / (N * N) : 0;
+  const int bj = NDIM == 3 ? (k * N * N + i) : i, bi = tid - i, bk = j * N + i;
+  double xr = 0, xs = 0, xt = 0, yr = 0, ys = 0, yt = 0, zr = 0, zs = 0, zt = 0;
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    const double di = sD[i * N + q], dj = sD[j * N + q];
+    xr += di * sx[bi + q]; yr += di * sy[bi + q];
+    xs += dj * sx[bj + q * N]; ys += dj * sy[bj + q * N];
+    if constexpr (NDIM == 3) {
+      const double dk = sD[k * N + q];
+      zr += di * sz[bi + q]; zs += dj * sz[bj + q * N];
+      xt += dk * sx[bk + q * N * N]; yt += dk * sy[bk + q * N * N]; zt += dk * sz[bk + q * N * N];
+    }
+  }
+  if constexpr (NDIM == 2) {
+    const double jinv = 1.0 / (xr * ys - xs * yr);
+    m[0][0] = ys * jinv; m[0][1] = -xs * jinv;
+    m[1][0] = -yr * jinv; m[1][1] = xr * jinv;
+  } else {
+    const double c_rx = ys * zt - yt * zs, c_ry = xt * zs - xs * zt, c_rz = xs * yt - xt * ys;
+    const double c_sx = yt * zr - yr * zt, c_sy = xr * zt - xt * zr, c_sz = xt * yr - xr * yt;
+    const double c_tx = yr * zs - ys * zr, c_ty = xs * zr - xr * zs, c_tz = xr * ys - xs * yr;
+    const double jinv = 1.0 / (xr * c_rx + yr * c_ry + zr * c_rz);
+    m[0][0] = c_rx * jinv; m[0][1] = c_ry * jinv; m[0][2] = c_rz * jinv;
+    m[1][0] = c_sx * jinv; m[1][1] = c_sy * jinv; m[1][2] = c_sz * jinv;
+    m[2][0] = c_tx * jinv; m[2][1] = c_ty * jinv; m[2][2] = c_tz * jinv;
+  }
+}
+
+// reference-space derivatives (f_r, f_s [, f_t]) of the element field sf at node tid
+template <int N, int NDIM>
+__device__ inline void elem_ref_deriv(const double* sD, const double* sf, int tid, double (&fd)[NDIM]) {
+  const int i = tid % N, j = (tid / N) % N, k = NDIM == 3 ? tid / (N * N) : 0;
+  const int bj = NDIM == 3 ? (k * N * N + i) : i, bi = tid - i, bk = j * N + i;
+  double fr = 0, fs = 0, ft = 0;
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    fr += sD[i * N + q] * sf[bi + q];
+    fs += sD[j * N + q] * sf[bj + q * N];
+    if constexpr (NDIM == 3) ft += sD[k * N + q] * sf[bk + q * N * N];
+  }
+  fd[0] = fr; fd[1] = fs;
+  if constexpr (NDIM == 3) fd[2] = ft;
+}
+
+template <int N, int NDIM>
+__device__ inline void elem_load_geom(const double* __restrict__ D, const double* __restrict__ xyz, long long e0, long long nloc,
+                                      int tid, double* sD, double* sx, double* sy, double* sz) {
+  constexpr int NP = SensCfg<N, NDIM>::NP;
+  if (tid < N * N) sD[tid] = D[tid];
+  if (tid < NP) {
+    sx[tid] = xyz[e0 + tid];
+    sy[tid] = xyz[nloc + e0 + tid];
+    if constexpr (NDIM == 3) sz[tid] = xyz[2 * nloc + e0 + tid];
+  }
+}
+
+// production: prod[c] (may be null) receives P[c][j] in its velocity component j; part[(3 c + j) * nel + e] the bm1-weighted
+// sum over element e (9 rows; rows of a missing third dimension are 0).  One workgroup per element.
+struct BudgetProd { double* p[3]; };
+
+template <int N, int NDIM>
+__global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_budget_prod(const double* __restrict__ D, const double* __restrict__ xyz,
+    const double* __restrict__ ub, const double* __restrict__ uR, const double* __restrict__ uI, const double* __restrict__ bm1,
+    const BudgetProd prod, double w, double* __restrict__ part, long long nloc) {
+  constexpr int NP = SensCfg<N, NDIM>::NP, NT = SensCfg<N, NDIM>::NT;
+  __shared__ double sD[N * N];
+  __shared__ double sf[NP], sx[NP], sy[NP], sz[NDIM == 3 ? NP : 1];
+  __shared__ double sred[3 * 16];
+  const int tid = threadIdx.x;
+  const long long e0 = (long long)blockIdx.x * NP, l = e0 + tid;
+  const bool act = tid < NP;
+  elem_load_geom<N, NDIM>(D, xyz, e0, nloc, tid, sD, sx, sy, sz);
+  __syncthreads();
+  double m[NDIM][NDIM] = {};
+  if (act) elem_inv_metric<N, NDIM>(sD, sx, sy, sz, tid, m);
+  double r[NDIM] = {}, im[NDIM] = {};
+  if (act) {
+#pragma unroll
+    for (int c = 0; c < NDIM; ++c) { r[c] = uR[c * nloc + l]; im[c] = uI[c * nloc + l]; }
+  }
+  const double b = act ? bm1[l] : 0.0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {                               // row c of the partials (c = 2 in 2-D: zeros)
+    double v[3] = {0.0, 0.0, 0.0};
+    if (c < NDIM) {
+      if (act) sf[tid] = ub[c * nloc + l];
+      __syncthreads();
+      if (act) {
+        double fd[NDIM];
+        elem_ref_deriv<N, NDIM>(sD, sf, tid, fd);
+#pragma unroll
+        for (int j = 0; j < NDIM; ++j) {
+          double g = 0.0;
+#pragma unroll
+          for (int q = 0; q < NDIM; ++q) g += m[q][j] * fd[q];   // d U_c / d x_j
+          const double P = w * (r[c] * r[j] + im[c] * im[j]) * g;
+          if (prod.p[c]) prod.p[c][j * nloc + l] = P;
+          v[j] = b * P;
+        }
+      }
+    }
+    block_reduce<3>(v, sred, tid, NT);                          // its barriers also end the reads of sf
+    if (tid == 0) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) part[(size_t)(3 * c + j) * gridDim.x + blockIdx.x] = v[j];
+    }
+  }
+}
+
+// div[l] = sum_i d/dx_i dsavg(g_i) at the element-local node l (g: ndim gradient fields, stride nloc).  One workgroup per element.
+template <int N, int NDIM>
+__global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_budget_div(const Dev d, const double* __restrict__ xyz,
+                                                                     const double* __restrict__ g, double* __restrict__ div) {
+  constexpr int NP = SensCfg<N, NDIM>::NP;
+  __shared__ double sD[N * N];
+  __shared__ double sf[NP], sx[NP], sy[NP], sz[NDIM == 3 ? NP : 1];
+  const int tid = threadIdx.x;
+  const long long nloc = d.nloc, e0 = (long long)blockIdx.x * NP, l = e0 + tid;
+  const bool act = tid < NP;
+  elem_load_geom<N, NDIM>(d.D, xyz, e0, nloc, tid, sD, sx, sy, sz);
+  const double mi = act ? d.minv[l] : 0.0;
+  __syncthreads();
+  double m[NDIM][NDIM] = {};
+  if (act) elem_inv_metric<N, NDIM>(sD, sx, sy, sz, tid, m);
+  double acc = 0.0;
+#pragma unroll
+  for (int a = 0; a < NDIM; ++a) {
+    if (a) __syncthreads();
+    if (act) sf[tid] = gs_gather(g + a * nloc, d, l) * mi;
+    __syncthreads();
+    if (!act) continue;
+    double fd[NDIM];
+    elem_ref_deriv<N, NDIM>(sD, sf, tid, fd);
+#pragma unroll
+    for (int q = 0; q < NDIM; ++q) acc += m[q][a] * fd[q];
+  }
+  if (act) div[l] = acc;
+}
+
+// D += w a dsavg(div) (diss may be null; first: D = instead of +=), part[blockIdx] = the bm1-weighted sum.  256 threads.
+__global__ void __launch_bounds__(256) k_budget_diss(const Dev d, const double* __restrict__ div, const double* __restrict__ a,
+                                                     double* __restrict__ diss, double w, int first, double* __restrict__ part) {
+  __shared__ double sred[16];
+  const int tid = threadIdx.x;
+  const long long l = (long long)blockIdx.x * 256 + tid;
+  double v[1] = {0.0};
+  if (l < d.nloc) {
+    const double t = w * a[l] * (gs_gather(div, d, l) * d.minv[l]);
+    if (diss) diss[l] = first ? t : diss[l] + t;
+    v[0] = d.bm1[l] * t;
+  }
+  block_reduce<1>(v, sred, tid, 256);
+  if (tid == 0) part[blockIdx.x] = v[0];
 }
 
 }  // namespace sens

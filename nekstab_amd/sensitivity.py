@@ -1,18 +1,23 @@
 """Sensitivity post-processing of direct and adjoint modes, restating core/sensitivity.f (uparam(1) = 4.x):
 
+    energy_budget                    4.1   stability_energy_budget (core/postproc.f:657-872): production and dissipation
     wave_maker                       4.2   Giannetti & Luchini (2007), structural sensitivity |d| |a|
     bf_sensitivity                   4.3   Marquet, Sipp & Jacquin (2008), sensitivity to base-flow modifications
     ts_steady_force_sensitivity      4.41 / 4.42   sensitivity to a steady force: GMRES on (I - exp(L^+ T))
     delta_forcing                    4.43  eigenvalue drift under a steady force proportional to the base flow (eq. 5.1)
+    postprocess                      4.0   energy_budget, wave_maker, bf_sensitivity in the reference's order (core/usr_extra.f)
 
-The fields are computed on the device (nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity, nsk_forced_map); delta_forcing
-is pointwise and stays on the host.  Output files carry the reference's prefixes (wm_, tr_, ti_, pr_, pi_, sr_, si_, fsr, fsi,
-dfr) so that nekStab's own scripts read them.  ``np_*`` functions are the numpy restatement the device is tested against.
+The fields are computed on the device (nsk_energy_budget, nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity,
+nsk_forced_map); delta_forcing is pointwise and stays on the host.  Output files carry the reference's prefixes (KIN, wm_, tr_,
+ti_, pr_, pi_, sr_, si_, fsr, fsi, dfr) so that nekStab's own scripts read them.  ``np_*`` functions are the numpy
+restatement the device is tested against.
 
-Two departures from the reference, both deliberate:
+Three departures from the reference, all deliberate:
   * in 3-D the transport term uses d v / d z where core/sensitivity.f:219, 222, 228, 231 read d w / d z (Marquet's formula;
     the two agree in 2-D and on z-invariant fields);
-  * biorthogonalisation scales the direct mode's pressure with its velocity (the reference passes one shared pressure array).
+  * biorthogonalisation scales the direct mode's pressure with its velocity (the reference passes one shared pressure array);
+  * the energy budget takes the mode divided by its norm, as the reference's comment says (core/postproc.f:703-707 multiplies
+    by it): the budget does not depend on the mode's scale, and the two readings agree for a mode of unit norm.
 """
 from __future__ import annotations
 
@@ -148,6 +153,30 @@ def np_bf_sensitivity(geom: NpGeom, dRe, dIm, aRe, aIm):
     return dict(tr=tr, ti=ti, pr=pr, pi=pi, sr=tr + pr, si=ti + pi)
 
 
+def np_energy_budget(geom: NpGeom, ub, dRe, dIm, nu):
+    """stability_energy_budget (core/postproc.f:657-872) on velocity fields [ndim, nel, ...]: dict of
+      prod       [ndim, ndim, nel, ...]   P[c][j] = -1/2 (uR_c uR_j + uI_c uI_j) d U_c / d x_j  (gradm1 of U, no dsavg)
+      diss       [nel, ...]               D = 1/2 nu sum_j (uR_j Lap uR_j + uI_j Lap uI_j),  Lap a = sum_i dsavg(d/dx_i dsavg(d a/dx_i))
+      integrals  [10]                     bm1-weighted sums of P[1][1..3], P[2][1..3], P[3][1..3], D (missing dimension: 0)
+    with the mode divided by alpha = sqrt(||dRe||^2 + ||dIm||^2) (bm1s-weighted; the reference's comment, not its code)."""
+    nd = geom.ndim
+    alpha = np.sqrt(geom.inner(dRe, dRe) + geom.inner(dIm, dIm))
+    uR, uI = np.asarray(dRe) / alpha, np.asarray(dIm) / alpha
+    gU = [geom.grad(np.asarray(ub[c])) for c in range(nd)]
+    prod = np.array([[-0.5 * (uR[c] * uR[j] + uI[c] * uI[j]) * gU[c][j] for j in range(nd)] for c in range(nd)])
+
+    def lap(a):
+        return sum(geom.dsavg(geom.grad(geom.dsavg(geom.grad(a)[i]))[i]) for i in range(nd))
+
+    diss = 0.5 * nu * sum(uR[j] * lap(uR[j]) + uI[j] * lap(uI[j]) for j in range(nd))
+    integrals = np.zeros(10)
+    for c in range(nd):
+        for j in range(nd):
+            integrals[3 * c + j] = np.sum(geom.bm1 * prod[c, j])
+    integrals[9] = np.sum(geom.bm1 * diss)
+    return dict(prod=prod, diss=diss, integrals=integrals)
+
+
 def delta_forcing(ub, fsr, fsi, alpha=1.0):
     """delta_forcing (core/sensitivity.f, uparam(1) = 4.43): eigenvalue drift of a steady force alpha |U| U, pointwise:
     (delta_lambda, delta_omega) = (-alpha |U| fsr . U, alpha |U| fsi . U)."""
@@ -185,6 +214,42 @@ def _write(h, path, *, u=None, t=None):
     """outpost: coordinates + velocity (or a scalar in the temperature slot), arrays as (ncomp, nel, nz, ny, nx)."""
     ex = (lambda a: a[..., None, :, :]) if h.ndim == 2 else (lambda a: a)
     nekio.write_fld(path, x=ex(_coords(h)), u=None if u is None else ex(np.asarray(u)), t=None if t is None else ex(np.asarray(t)))
+
+
+def energy_budget(h, ub, dRe, dIm, *, outdir=None, session="1cyl"):
+    """uparam(1) = 4.1.  Base flow and direct mode as device vectors (left as they are).  Returns (integrals [10], their sum,
+    production fields [ndim, ndim, nel, ...]); writes KIN<session>0.f00001 .. f0000<ndim> into ``outdir`` when given, file c
+    holding P[c][1..ndim] in its velocity slots (outpost(..., "KIN") once per base-flow component)."""
+    vecs = h.alloc(h.ndim)
+    try:
+        integrals = h.energy_budget(ub, dRe, dIm, prod=vecs)
+        prod = np.array([download_velocity(h, v) for v in vecs])
+    finally:
+        h.free(vecs)
+    if outdir is not None:
+        for c in range(h.ndim):
+            _write(h, os.path.join(outdir, fld_name("KIN", session, c + 1)), u=prod[c])
+    return integrals, float(np.sum(integrals)), prod
+
+
+def postprocess(h, ub, dRe, dIm, aRe, aIm, *, outdir=None, session="1cyl"):
+    """uparam(1) = 4.0 (core/usr_extra.f:216-221): energy_budget, then wave_maker, then bf_sensitivity, writing every file of the
+    three into ``outdir`` when given.  Base flow and modes are device vectors, left as they are: as the reference reloads the
+    mode files for each step, wave_maker and bf_sensitivity each biorthogonalise their own copy of the modes.  Returns a dict:
+    integrals, budget_sum, prod, wm, gamma_delta and the bf_sensitivity fields (tr, ti, pr, pi, sr, si)."""
+    integrals, total, prod = energy_budget(h, ub, dRe, dIm, outdir=outdir, session=session)
+    modes = (dRe, dIm, aRe, aIm)
+    work = h.alloc(4)
+    try:
+        for w, m in zip(work, modes):
+            h.copy(w, m)
+        wm, gd = wave_maker(h, *work, outdir=outdir, session=session)
+        for w, m in zip(work, modes):
+            h.copy(w, m)
+        sens, _ = bf_sensitivity(h, *work, outdir=outdir, session=session)
+    finally:
+        h.free(work)
+    return dict(integrals=integrals, budget_sum=total, prod=prod, wm=wm, gamma_delta=gd, **sens)
 
 
 def wave_maker(h, dRe, dIm, aRe, aIm, *, outdir=None, session="1cyl"):
