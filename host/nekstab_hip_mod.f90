@@ -160,6 +160,32 @@ module nekstab_hip
       real(c_double), value :: spng_str
       type(c_ptr), value :: endv
     end function
+    ! Fourier-compressed orbit (core/fourier.f): amp, A, B are C arrays (c_loc of the first element, or c_null_ptr)
+    integer(c_int) function nsk_set_orbit_fourier(ctx, q0, spng_str, nmodes, endv, amp) bind(c, name='nsk_set_orbit_fourier')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: q0
+      real(c_double), value :: spng_str
+      integer(c_int), value :: nmodes
+      type(c_ptr), value :: endv
+      type(c_ptr), value :: amp
+    end function
+    integer(c_int) function nsk_set_orbit_modes(ctx, nmodes, period, A, B) bind(c, name='nsk_set_orbit_modes')
+      import
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: nmodes
+      real(c_double), value :: period
+      type(c_ptr), value :: A
+      type(c_ptr), value :: B
+    end function
+    integer(c_int) function nsk_get_orbit_modes(ctx, nmodes, period, A, B) bind(c, name='nsk_get_orbit_modes')
+      import
+      type(c_ptr), value :: ctx
+      integer(c_int) :: nmodes
+      real(c_double) :: period
+      type(c_ptr), value :: A
+      type(c_ptr), value :: B
+    end function
     integer(c_int) function nsk_dot(ctx, p, q, alpha) bind(c, name='nsk_dot')
       import
       type(c_ptr), value :: ctx

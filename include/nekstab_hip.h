@@ -93,6 +93,9 @@ int nsk_set_tolerances(nsk_ctx* ctx, double tol_helm, double tol_pres, int relat
  * "budget_helm" / "budget_pres" (launch budgets), "fused" (persistent velocity solve: right-hand side, all CG iterations and
  * the pressure right-hand side in one launch with device-side grid barriers; default 0: not faster on config 2),
  * "endtime" (the sampling period T = param(10); used by the next nsk_set_baseflow / nsk_set_orbit),
+ * "orbit_phase" (Fourier orbits, nsk_set_orbit_fourier / nsk_set_orbit_modes: 0 <= phi < 1, default 0 -- maps start at
+ * t0 = phi T of the cycle (intracycle growth, core/matvec.f:193,292); ignored while no Fourier orbit is active, takes effect at
+ * the next map),
  * "gmres_cycle" (the pressure GMRES restarts after this many iterations, default and maximum 48; `max_pres_iter` may be up to 4 x 48),
  * "mfma_convect" (hexahedra, lx1 = 8: convection contractions on v_mfma_f64_16x16x4_f64, default 1),
  * "merged_update" / "merged_iters" (quadrilaterals with the dense in-LDS coarse solve: the GMRES column bookkeeping runs inside
@@ -165,6 +168,26 @@ int nsk_set_baseflow(nsk_ctx* ctx, nsk_vec q);
  * device (quadrilaterals: six arrays per step; hexahedra: the twelve dealiasing-mesh constants per step, 12 * nel * lxd^3 doubles);
  * `end` (optional) receives Phi_T(q0) for a periodicity check. */
 int nsk_set_orbit(nsk_ctx* ctx, nsk_vec q0, double spng_str, nsk_vec end);
+/* The same orbit as its temporal Fourier modes (core/fourier.f):
+ *   U(t_n) = A_0 + sum_{k=1..M} A_k cos(2 pi k n / N) + B_k sin(2 pi k n / N),  n = 0 .. N-1 = nsteps - 1.
+ * Device memory: stored orbit nsteps * (quadrilaterals 6 * nel * lxd^2, hexahedra 12 * nel * lxd^3) doubles;
+ * Fourier orbit (2 M + 1) * ndim * nel * lx1^ndim doubles whatever the number of steps (+ nsteps * 2 M cos / sin factors).
+ * The linearised maps rebuild the base-flow constants of the running step from the modes; a map may then be longer than one
+ * period (nsk_set_nsteps), use another dt, or start at another phase (option "orbit_phase").  Full-mesh contexts only: shards,
+ * rank-local contexts and lanes return NSK_EINVAL.  nsk_set_baseflow / nsk_set_orbit end the Fourier form; nsk_clone refuses it.
+ *
+ * nsk_set_orbit_fourier (fourier_decomposition, core/fourier.f:23-88): the integration of nsk_set_orbit (same dt / nsteps,
+ * sponge and `end`, bit for bit), keeping the lowest `nmodes` harmonics, 0 <= nmodes <= nsteps / 2 (0: the time average);
+ * no snapshot is stored at any point.  `amp` (NULL or 2 nmodes + 1 doubles) receives the bm1-weighted L2 norms of
+ * A_0, A_1, B_1, .. over all velocity components (amp_real / amp_img, core/fourier.f:46-53). */
+int nsk_set_orbit_fourier(nsk_ctx* ctx, nsk_vec q0, double spng_str, int nmodes, nsk_vec end, double* amp);
+/* fourier_reconstruction (core/fourier.f:2-21) from modes computed elsewhere: A[0 .. nmodes], B[0 .. nmodes-1] = B_1 ..
+ * are state vectors (velocity components used, pressure ignored).  dt / nsteps follow the rule of nsk_set_baseflow applied
+ * to U(0) = sum_k A_k with "endtime" as set; `period` is the orbit's T and need not equal endtime. */
+int nsk_set_orbit_modes(nsk_ctx* ctx, int nmodes, double period, const nsk_vec* A, const nsk_vec* B);
+/* the modes of the active Fourier orbit (the fRe / fIm fields of core/fourier.f:78-85, un-normalised) into A[0 .. nmodes],
+ * B[0 .. nmodes-1]; A = B = NULL: count and period only.  NSK_EINVAL when no Fourier orbit is active. */
+int nsk_get_orbit_modes(nsk_ctx* ctx, int* nmodes, double* period, nsk_vec* A, nsk_vec* B);
 
 /* krylov_inner_product / norm / cmult / add2,sub2 / copy / zero
  * (core/krylov_subspace.f:24-212) */
@@ -348,7 +371,8 @@ int nsk_project_out(nsk_ctx* ctx, nsk_vec f, const nsk_vec* Q, int nq, const dou
 int nsk_get_step_iters(nsk_ctx* ctx, int n, int* helm, int* pres, int* nsteps);
 
 /* measurement hook for bench.py: average duration (us) of `reps` back-to-back launches of a hot
- * kernel ("helm"), HIP events on the library's stream, full work in every launch */
+ * kernel ("helm", .., "baseflow_fourier": the per-step reconstruction of an active Fourier orbit), HIP events on the
+ * library's stream, full work in every launch */
 int nsk_bench_kernel(nsk_ctx* ctx, const char* name, int reps, double* avg_us);
 
 /* ---- kernel-level test hooks (parity against oracle/, tests/test_kernels_gpu.py) ---- */

@@ -80,6 +80,9 @@ SYMBOLS = {
     "nsk_nonlinear_map": (C.c_int, [_vp, _vp, _vp, C.c_int]),
     "nsk_set_baseflow": (C.c_int, [_vp, _vp]),
     "nsk_set_orbit": (C.c_int, [_vp, _vp, C.c_double, _vp]),
+    "nsk_set_orbit_fourier": (C.c_int, [_vp, _vp, C.c_double, C.c_int, _vp, _dp]),
+    "nsk_set_orbit_modes": (C.c_int, [_vp, C.c_int, C.c_double, _vpp, _vpp]),
+    "nsk_get_orbit_modes": (C.c_int, [_vp, _ip, _dp, _vpp, _vpp]),
     "nsk_dot": (C.c_int, [_vp, _vp, _vp, _dp]),
     "nsk_norm": (C.c_int, [_vp, _vp, _dp]),
     "nsk_scal": (C.c_int, [_vp, _vp, C.c_double]),
@@ -311,6 +314,43 @@ class NekStabHip:
         a, b, d = C.c_longlong(), C.c_longlong(), C.c_longlong()
         self._chk(self.lib.nsk_get_info(self.ctx, C.byref(dt), C.byref(ns), C.byref(a), C.byref(b), C.byref(d)))
         self.dt, self.nsteps = dt.value, ns.value
+
+    def _refresh_dt(self):
+        dt, ns = C.c_double(), C.c_int()
+        a, b, d = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        self._chk(self.lib.nsk_get_info(self.ctx, C.byref(dt), C.byref(ns), C.byref(a), C.byref(b), C.byref(d)))
+        self.dt, self.nsteps = dt.value, ns.value
+
+    # ---- the orbit as temporal Fourier modes (core/fourier.f)
+    def set_orbit_fourier(self, q0, nmodes, spng_str=0.0, end=None):
+        """The integration of ``set_orbit``, keeping the lowest ``nmodes`` harmonics instead of every step's constants.
+        Returns the 2 nmodes + 1 bm1-weighted L2 norms of A_0, A_1, B_1, .. (nsk_set_orbit_fourier)."""
+        amp = np.zeros(2 * max(int(nmodes), 0) + 1)
+        self._chk(self.lib.nsk_set_orbit_fourier(self.ctx, q0, float(spng_str), int(nmodes), end, _p(amp)))
+        self._refresh_dt()
+        return amp
+
+    def set_orbit_modes(self, A, B, period):
+        """Fourier orbit from mode vectors A = [A_0 .. A_M], B = [B_1 .. B_M] (device state vectors; nsk_set_orbit_modes)."""
+        M = len(B)
+        if len(A) != M + 1:
+            raise ValueError("set_orbit_modes: A needs len(B) + 1 vectors")
+        aa = (C.c_void_p * (M + 1))(*[v.value for v in A])
+        bb = (C.c_void_p * max(M, 1))(*[v.value for v in B])
+        self._chk(self.lib.nsk_set_orbit_modes(self.ctx, M, float(period), aa, bb if M else None))
+        self._refresh_dt()
+
+    def get_orbit_modes(self, A=None, B=None):
+        """(nmodes, period) of the active Fourier orbit; with A (nmodes + 1 vectors) and B (nmodes) the modes are copied out."""
+        m, per = C.c_int(), C.c_double()
+        aa = (C.c_void_p * len(A))(*[v.value for v in A]) if A is not None else None
+        bb = (C.c_void_p * max(len(B), 1))(*[v.value for v in B]) if B is not None else None
+        if A is not None:
+            self._chk(self.lib.nsk_get_orbit_modes(self.ctx, C.byref(m), C.byref(per), None, None))
+            if len(A) != m.value + 1 or len(B or []) != m.value:
+                raise ValueError("get_orbit_modes: needs %d + %d vectors" % (m.value + 1, m.value))
+        self._chk(self.lib.nsk_get_orbit_modes(self.ctx, C.byref(m), C.byref(per), aa, bb))
+        return m.value, per.value
 
     def dot(self, p, q):
         a = C.c_double()

@@ -243,6 +243,12 @@ struct nsk_ctx {
   double* orbit[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   const double* steady[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   int orbit_steps = 0;
+  // ---- the same orbit as temporal Fourier modes (core/fourier.f): Dev::fmodes / Dev::ftrig; the table of cos / sin factors
+  // belongs to (nsteps, dt, period, harmonics, phase) and is rebuilt by the next map when one of them changed (forb_trig_ensure)
+  double* forb_modes = nullptr; size_t forb_modes_cap = 0;
+  double* forb_trig = nullptr; size_t forb_trig_cap = 0;
+  double forb_T = 0.0, forb_phase = 0.0;
+  int trig_n = -1, trig_M = -1; double trig_dt = 0.0, trig_T = 0.0, trig_phase = 0.0;
 };
 
 // every captured step is stale (Dev, coefficients, kernel choices are baked in): class graphs re-captured on next use, the
@@ -1437,6 +1443,9 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
   int nh = hc ? c->max_helm : (nh_over > 0 ? nh_over : c->cur_helm[sc.cls]);
   DISPATCH_N(c->key, {
     constexpr int NT = Cfg<N>::NT;
+    if (d.forb && adjoint != 2)       // Fourier orbit: the base flow of this step into the steady slot (hexahedra: cUr is the 12-constant array)
+      hipLaunchKernelGGL(k_baseflow_fourier<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (double*)d.cUr, (double*)d.cUs,
+                         (double*)d.GUx, (double*)d.GUy, (double*)d.GVx, (double*)d.GVy);
     if (c->key == 108 && adjoint != 2 && c->mfma_convect)
       hipLaunchKernelGGL(nsk::k3::k_convect_mfma8, dim3(c->nel), dim3(512), 0, c->stream, d, (const double*)d.u, d.bf, adjoint);
     else if (c->key == 110 && adjoint != 2 && c->mfma_convect)
@@ -1562,8 +1571,40 @@ static bool step_budgets_ready(const nsk_ctx* c, int kind) {
   return c->step_budgets && !c->sb_force_class && !c->fused && !c->budget_freeze && c->d.step_iters && (int)b.bh.size() == c->nsteps && (int)b.bp.size() == c->nsteps;
 }
 
+// Fourier orbit: row i of the table holds cos / sin (2 pi frac(k s_i)), k = 1..M, s_i = phase + i dt / T -- the base flow of
+// time step i + 1 of a direct or adjoint map (the slot rule of the stored orbit).  Any nsteps, any dt.
+static int forb_trig_ensure(nsk_ctx* c) {
+  Dev& d = c->d;
+  const int M = d.forb_M, n = c->nsteps;
+  if (c->trig_n == n && c->trig_M == M && c->trig_dt == c->dt && c->trig_T == c->forb_T && c->trig_phase == c->forb_phase) return 0;
+  const size_t need = (size_t)n * (size_t)std::max(2 * M, 1);
+  HIPCHK(hipStreamSynchronize(c->stream));                    // (no queued step may still read the old table)
+  if (need > c->forb_trig_cap) {
+    if (c->forb_trig) { nsk_vec v = c->forb_trig; nsk_vec_free(c, 1, &v); c->forb_trig = nullptr; c->forb_trig_cap = 0; }
+    int rc = dalloc(c, &c->forb_trig, need);
+    if (rc) return rc;
+    c->forb_trig_cap = need;
+  }
+  std::vector<double> t(need, 0.0);
+  const double twopi = 8.0 * std::atan(1.0);
+  for (int i = 0; i < n; ++i) {
+    const double si = c->forb_phase + (double)i * c->dt / c->forb_T;
+    for (int k = 1; k <= M; ++k) {
+      double fr = (double)k * si; fr -= std::floor(fr);
+      t[(size_t)i * 2 * M + 2 * k - 2] = std::cos(twopi * fr);
+      t[(size_t)i * 2 * M + 2 * k - 1] = std::sin(twopi * fr);
+    }
+  }
+  HIPCHK(hipMemcpy(c->forb_trig, t.data(), need * sizeof(double), hipMemcpyHostToDevice));
+  d.ftrig = c->forb_trig; d.forb_rows = n;
+  c->trig_n = n; c->trig_M = M; c->trig_dt = c->dt; c->trig_T = c->forb_T; c->trig_phase = c->forb_phase;
+  invalidate_graphs(c);           // the table's address and row count are baked into the captured steps
+  return 0;
+}
+
 static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   Dev& d = c->d;
+  if (d.forb && adjoint != 2) { int rc = forb_trig_ensure(c); if (rc) return rc; }
   // one- and two-step maps (newton.py: time derivative of the orbit) run eagerly: capturing six step-class graphs for them
   // costs more than the steps, and their iteration counts say nothing about the budgets of the real maps
   const bool use_graph = c->use_graph && c->nsteps > 2 && !hostcheck_on(c);
@@ -1594,8 +1635,8 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   for (int cc = 0; cc < c->ndim; ++cc)
     HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d.p, q + c->ndim * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  if (d.bf_stride) {
-    if (adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
+  if (d.bf_stride || d.forb) {
+    if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
     HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
   }
   for (int istep = 1; istep <= c->nsteps; ++istep) {
@@ -2435,7 +2476,7 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
   else if (n == "helm_pf") { c->helm_pf = (int)value; invalidate_graphs(c); }
   else if (n == "helm_pf_grid") { c->helm_pf_grid = std::max(8, (int)value / 8 * 8); invalidate_graphs(c); }      // resident workgroups of k_helm_p (tests: fewer than elements; default: what the device holds)
   else if (n == "zero_metrics") {       // 0: every array is loaded (the cleaned ones included: same bits); 1: back to the masks of the set-up
-    c->d.zmask = value != 0.0 ? c->zmask_built : 0u; c->d.bfmask = (value != 0.0 && !c->d.bf_stride) ? c->bfmask_built : 0u;
+    c->d.zmask = value != 0.0 ? c->zmask_built : 0u; c->d.bfmask = (value != 0.0 && !c->d.bf_stride && !c->d.forb) ? c->bfmask_built : 0u;
     invalidate_graphs(c);
   }
   else if (n == "eapply_pipe") { c->eapply_pipe = (int)value; invalidate_graphs(c); }
@@ -2452,6 +2493,10 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
   else if (n == "endtime") {                     // param(10): the sampling period T (Newton for periodic orbits changes it every iteration)
     if (!(value > 0.0)) return fail(NSK_EINVAL, "endtime must be positive");
     c->endtime = value;                          // takes effect at the next nsk_set_baseflow / nsk_set_orbit (dt, nsteps from the CFL rule)
+  }
+  else if (n == "orbit_phase") {                 // Fourier orbits: maps start at t0 = phi T (intracycle growth, core/matvec.f:193,292)
+    if (!(value >= 0.0 && value < 1.0)) return fail(NSK_EINVAL, "orbit_phase: 0 <= phi < 1");
+    c->forb_phase = value;                       // takes effect at the next map (forb_trig_ensure)
   }
   else if (n == "gmres_cycle") c->gmres_cycle = std::max(2, std::min((int)value, MAXMR));
   else if (n == "fused") {
@@ -2661,6 +2706,7 @@ int nsk_set_baseflow(nsk_ctx* c, nsk_vec qv) {
   if (c->parent || c->nranks > 1) return fail(NSK_EINVAL, "shards: use nsk_group_set_baseflow");
   if (c->clone_of) return fail(NSK_EINVAL, "lanes share the base-flow constants of the context they were cloned from: set the base flow there, before nsk_clone");
   Dev& d = c->d;
+  d.forb = 0;                     // a Fourier orbit ends here (nsk_set_orbit comes through here too)
   const double* q = (const double*)qv;
   DISPATCH_N(c->key, {
     hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, q, (double*)d.cUr, (double*)d.cUs,
@@ -2695,24 +2741,107 @@ int nsk_set_baseflow(nsk_ctx* c, nsk_vec qv) {
   return 0;
 }
 
+// ---- Fourier-compressed periodic base flow (core/fourier.f) --------------------------------------------------------------
+// U(t_n) = A_0 + sum_{k=1..M} A_k cos(2 pi k n / N) + B_k sin(2 pi k n / N): the device holds the 2M+1 mode arrays
+// [2M+1][ndim][nloc] (A_0, A_1, B_1, ..) whatever the number of steps; k_baseflow_fourier rebuilds the base-flow constants of
+// the running step from them (step()).
+static int forb_refuse(const nsk_ctx* c, const char* who) {
+  if (c->parent || c->nranks > 1) return fail(NSK_EINVAL, std::string(who) + ": not on a shard (Fourier orbits: full-mesh contexts only)");
+  if (c->local) return fail(NSK_EINVAL, std::string(who) + ": not on a rank-local context (Fourier orbits: full-mesh contexts only)");
+  if (c->clone_of) return fail(NSK_EINVAL, std::string(who) + ": not on a lane (nsk_clone)");
+  if (c->released) return fail(NSK_EINVAL, std::string(who) + ": context was released (nsk_shard_release_parent)");
+  return 0;
+}
+// room for the modes, zeroed (on the stream)
+static int forb_alloc(nsk_ctx* c, int M) {
+  const size_t need = (size_t)(2 * M + 1) * (size_t)c->ndim * (size_t)c->nloc;
+  if (need > c->forb_modes_cap) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->forb_modes) { nsk_vec v = c->forb_modes; nsk_vec_free(c, 1, &v); c->forb_modes = nullptr; c->forb_modes_cap = 0; }
+    int rc = dalloc(c, &c->forb_modes, need);
+    if (rc) return rc;
+    c->forb_modes_cap = need;
+    invalidate_graphs(c);         // the address is baked into the captured steps
+  }
+  HIPCHK(hipMemsetAsync(c->forb_modes, 0, need * sizeof(double), c->stream));
+  return 0;
+}
+// the modes are in place: linearised maps take them from now on; amp (NULL or 2M+1 doubles) = bm1-weighted L2 norms of
+// A_0, A_1, B_1, .. over all velocity components (amp_real / amp_img, core/fourier.f:46-53)
+static int forb_activate(nsk_ctx* c, int M, double T, double* amp) {
+  Dev& d = c->d;
+  if (!d.bstep) { int rc = dalloc(c, &d.bstep, 4); if (rc) return rc; }
+  d.fmodes = c->forb_modes; d.forb_M = M; d.forb = 1; d.forb_rows = 0; d.ftrig = nullptr;
+  d.bfmask = 0;                   // every base-flow array is loaded, as for a stored orbit
+  c->forb_T = T; c->trig_n = -1;  // the next map builds its table (forb_trig_ensure)
+  invalidate_graphs(c);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (amp) {
+    const size_t nv = (size_t)c->ndim * (size_t)c->nloc;
+    std::vector<double> h(nv);
+    for (int m = 0; m < 2 * M + 1; ++m) {
+      HIPCHK(hipMemcpy(h.data(), c->forb_modes + (size_t)m * nv, nv * sizeof(double), hipMemcpyDeviceToHost));
+      double s = 0.0;
+      for (int cc = 0; cc < c->ndim; ++cc)
+        for (long long l = 0; l < c->nloc; ++l) { const double v = h[(size_t)cc * c->nloc + l]; s += c->bm1s_host[l] * v * v; }
+      amp[m] = std::sqrt(s);
+    }
+  }
+  return 0;
+}
+
 // Time-periodic base flow for Floquet analysis (uparam(1)=3.11, core/matvec.f:191-236, core/eigensolvers.f:201-210):
 // integrate the full equations from q0 over one period T = endtime (DNS sponge towards the initial field with
 // strength spng_str, core/utils.f:165-170) and store the base-flow constants of every step; the linearised
 // maps then read slot istep-1 at step istep.  Returns Phi_T(q0) in `end` (periodicity check) if not NULL.
-int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
-  if (!c || !q0v) return fail(NSK_EINVAL, "bad argument");
-  if (c->parent) return fail(NSK_EINVAL, "shards: use nsk_group_set_orbit");
-  if (c->clone_of) return fail(NSK_EINVAL, "not on a lane (nsk_clone)");
+// nmodes >= 0 (nsk_set_orbit_fourier): the same integration, but every step's field is added into the lowest nmodes temporal
+// Fourier modes (k_orbit_dft) instead of its constants being stored.
+static int set_orbit_impl(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end, int nmodes, double* amp) {
   Dev& d = c->d;
   const double* q0 = (const double*)q0v;
+  const bool four = nmodes >= 0;
+  const int nm = 2 * nmodes + 1;
+  double* dftw = nullptr;                                       // [nsteps][nm] coefficient rows of k_orbit_dft (Fourier form)
+  // dt, nsteps are known once the base flow is set: the rows c_k / N cos, sin (2 pi k n / N), c_k = 2 except c_0 = c_{N/2} = 1
+  auto four_begin = [&]() -> int {
+    if (nmodes > c->nsteps / 2) return fail(NSK_EINVAL, "nsk_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2 (" + std::to_string(c->nsteps / 2) + ")");
+    for (int k = 0; k < 6; ++k) if (c->orbit[k]) { nsk_vec v = c->orbit[k]; nsk_vec_free(c, 1, &v); c->orbit[k] = nullptr; }
+    c->orbit_steps = 0;
+    int rc = forb_alloc(c, nmodes);
+    if (rc) return rc;
+    const int Nn = c->nsteps;
+    std::vector<double> w((size_t)Nn * nm);
+    const double twopi = 8.0 * std::atan(1.0);
+    for (int n = 0; n < Nn; ++n) {
+      w[(size_t)n * nm] = 1.0 / Nn;
+      for (int k = 1; k <= nmodes; ++k) {
+        const bool nyq = 2 * k == Nn;
+        const double ang = twopi * (double)(((long long)k * n) % Nn) / (double)Nn, ck = (nyq ? 1.0 : 2.0) / Nn;
+        w[(size_t)n * nm + 2 * k - 1] = ck * std::cos(ang);
+        w[(size_t)n * nm + 2 * k] = nyq ? 0.0 : ck * std::sin(ang);
+      }
+    }
+    if ((rc = dalloc(c, &dftw, w.size()))) return rc;
+    HIPCHK(hipMemcpy(dftw, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+  };
+  auto four_add = [&](int istep) {
+    const long long nv = (long long)c->ndim * d.nloc;
+    hipLaunchKernelGGL(k_orbit_dft, dim3((unsigned)std::min<long long>((nv + 255) / 256, 4096)), dim3(256), 0, c->stream, c->forb_modes, (const double*)d.u,
+                       (const double*)(dftw + (size_t)(istep - 1) * nm), nm, d.nloc, d.cs, c->ndim);
+  };
+  auto four_end = [&]() { if (dftw) { nsk_vec v = dftw; nsk_vec_free(c, 1, &v); dftw = nullptr; } };
   if (c->ndim == 3) {
     // hexahedra: the twelve dealiasing-mesh constants of every time step of the orbit, [nsteps][12][nfine] behind Dev::bfc
     if (d.bf_stride) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; d.bf_stride = 0; }
     int rc = nsk_set_baseflow(c, q0v);                          // dt, nsteps from the CFL of the initial field
     if (rc) return rc;
     const long long nfine = d.nfine;
-    if (c->orbit[0]) { nsk_vec v = c->orbit[0]; nsk_vec_free(c, 1, &v); c->orbit[0] = nullptr; }
-    if ((rc = dalloc(c, &c->orbit[0], (size_t)c->nsteps * 12 * nfine))) return rc;
+    if (four) { if ((rc = four_begin())) return rc; }
+    else {
+      if (c->orbit[0]) { nsk_vec v = c->orbit[0]; nsk_vec_free(c, 1, &v); c->orbit[0] = nullptr; }
+      if ((rc = dalloc(c, &c->orbit[0], (size_t)c->nsteps * 12 * nfine))) return rc;
+    }
     double* vr = const_cast<double*>(d.spng_vr);
     if (!vr && (rc = dalloc(c, &vr, 3 * d.cs))) return rc;
     for (int cc = 0; cc < 3; ++cc) HIPCHK(hipMemcpyAsync(vr + cc * d.cs, q0 + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -2725,11 +2854,12 @@ int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
     for (int cc = 0; cc < 3; ++cc) HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q0 + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d.p, q0 + 3 * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     for (int istep = 1; istep <= c->nsteps; ++istep) {
-      DISPATCH_N(c->key, {
+      if (four) four_add(istep);
+      else DISPATCH_N(c->key, {
         hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)d.u, c->orbit[0] + (size_t)(istep - 1) * 12 * nfine,
                            (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr);
       });
-      if ((rc = step(c, istep, 2))) return rc;
+      if ((rc = step(c, istep, 2))) { four_end(); return rc; }
     }
     Stats h;
     HIPCHK(hipMemcpyAsync(&h, d.stats, sizeof(Stats), hipMemcpyDeviceToHost, c->stream));
@@ -2739,7 +2869,9 @@ int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
       HIPCHK(hipMemcpyAsync(f + 3 * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
+    four_end();
     if (h.unconverged > 0) return fail(NSK_ENOCONV, "inner solve hit its iteration cap while integrating the base-flow orbit");
+    if (four) return forb_activate(c, nmodes, c->endtime, amp);
     c->steady[0] = d.bfc;
     d.bfc = c->orbit[0]; d.cUr = c->orbit[0]; d.bfmask = 0;
     d.bf_stride = 12 * nfine; c->orbit_steps = c->nsteps;
@@ -2753,7 +2885,8 @@ int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
   int rc = nsk_set_baseflow(c, q0v);                            // dt, nsteps from the CFL of the initial field
   if (rc) return rc;
   const long long nfine = (long long)c->nel * c->NDD;
-  for (int k = 0; k < 6; ++k) {
+  if (four) { if ((rc = four_begin())) return rc; }
+  else for (int k = 0; k < 6; ++k) {
     if (c->orbit[k]) { nsk_vec v = c->orbit[k]; nsk_vec_free(c, 1, &v); c->orbit[k] = nullptr; }
     if ((rc = dalloc(c, &c->orbit[k], (size_t)c->nsteps * nfine))) return rc;
   }
@@ -2772,11 +2905,12 @@ int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
   HIPCHK(hipMemcpyAsync(d.p, q0 + 2 * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   for (int istep = 1; istep <= c->nsteps; ++istep) {
     const long long off = (long long)(istep - 1) * nfine;
-    DISPATCH_N(c->key, {
+    if (four) four_add(istep);
+    else DISPATCH_N(c->key, {
       hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)d.u, c->orbit[0] + off, c->orbit[1] + off,
                          c->orbit[2] + off, c->orbit[3] + off, c->orbit[4] + off, c->orbit[5] + off);
     });
-    if ((rc = step(c, istep, 2))) return rc;
+    if ((rc = step(c, istep, 2))) { four_end(); return rc; }
   }
   Stats h;
   HIPCHK(hipMemcpyAsync(&h, d.stats, sizeof(Stats), hipMemcpyDeviceToHost, c->stream));
@@ -2787,11 +2921,85 @@ int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
     HIPCHK(hipMemcpyAsync(f + 2 * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
+  four_end();
   if (h.unconverged > 0) return fail(NSK_ENOCONV, "inner solve hit its iteration cap while integrating the base-flow orbit");
+  if (four) return forb_activate(c, nmodes, c->endtime, amp);
   c->steady[0] = d.cUr; c->steady[1] = d.cUs; c->steady[2] = d.GUx; c->steady[3] = d.GUy; c->steady[4] = d.GVx; c->steady[5] = d.GVy;
   d.cUr = c->orbit[0]; d.cUs = c->orbit[1]; d.GUx = c->orbit[2]; d.GUy = c->orbit[3]; d.GVx = c->orbit[4]; d.GVy = c->orbit[5];
   d.bf_stride = nfine; c->orbit_steps = c->nsteps;
   invalidate_graphs(c);
+  return 0;
+}
+
+int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
+  if (!c || !q0v) return fail(NSK_EINVAL, "bad argument");
+  if (c->parent) return fail(NSK_EINVAL, "shards: use nsk_group_set_orbit");
+  if (c->clone_of) return fail(NSK_EINVAL, "not on a lane (nsk_clone)");
+  return set_orbit_impl(c, q0v, spng_str, end, -1, nullptr);
+}
+
+// The orbit of nsk_set_orbit kept as its lowest nmodes temporal harmonics (fourier_decomposition, core/fourier.f:23-88):
+// (2 nmodes + 1) ndim nloc doubles on the device whatever the number of steps; period T = endtime.
+int nsk_set_orbit_fourier(nsk_ctx* c, nsk_vec q0v, double spng_str, int nmodes, nsk_vec end, double* amp) {
+  if (!c || !q0v) return fail(NSK_EINVAL, "bad argument");
+  { const int rc = forb_refuse(c, "nsk_set_orbit_fourier"); if (rc) return rc; }
+  if (nmodes < 0) return fail(NSK_EINVAL, "nsk_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2");
+  return set_orbit_impl(c, q0v, spng_str, end, nmodes, amp);
+}
+
+// Modes computed elsewhere (the reference's fRe / fIm files, a coarser DNS; fourier_reconstruction, core/fourier.f:2-21):
+// A[0..nmodes], B[0..nmodes-1] = B_1.. are state vectors whose velocity components are taken.  dt / nsteps: the rule of
+// nsk_set_baseflow applied to U(0) = sum_k A_k with `endtime` as set; `period` is the orbit's T and need not equal endtime.
+int nsk_set_orbit_modes(nsk_ctx* c, int nmodes, double period, const nsk_vec* A, const nsk_vec* B) {
+  if (!c || !A || nmodes < 0 || (nmodes > 0 && !B)) return fail(NSK_EINVAL, "bad argument");
+  { const int rc = forb_refuse(c, "nsk_set_orbit_modes"); if (rc) return rc; }
+  if (!(period > 0.0)) return fail(NSK_EINVAL, "nsk_set_orbit_modes: period must be positive");
+  for (int k = 0; k <= nmodes; ++k) if (!A[k] || (k < nmodes && !B[k])) return fail(NSK_EINVAL, "nsk_set_orbit_modes: null mode vector");
+  Dev& d = c->d;
+  const long long nv = (long long)c->ndim * c->nloc;
+  // the modes first (A or B may be the vectors nsk_get_orbit_modes filled from the arrays replaced here: staged through a new array)
+  double* fresh = nullptr;
+  int rc = dalloc(c, &fresh, (size_t)(2 * nmodes + 1) * nv);
+  if (rc) return rc;
+  for (int k = 0; k <= nmodes; ++k) {
+    HIPCHK(hipMemcpyAsync(fresh + (size_t)(k ? 2 * k - 1 : 0) * nv, A[k], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (k) HIPCHK(hipMemcpyAsync(fresh + (size_t)(2 * k) * nv, B[k - 1], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(hipMemsetAsync(c->scratch, 0, c->nstate * sizeof(double), c->stream));
+  for (int k = 0; k <= nmodes; ++k)                             // U(0) = sum_k A_k
+    hipLaunchKernelGGL(k_axpby, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, c->scratch, 1.0, (const double*)A[k], 1.0, nv);
+  if (d.bf_stride) {                                            // back to the steady arrays first (as nsk_set_orbit)
+    if (c->ndim == 3) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; }
+    else { d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5]; }
+    d.bf_stride = 0;
+  }
+  if ((rc = nsk_set_baseflow(c, c->scratch))) { nsk_vec v = fresh; nsk_vec_free(c, 1, &v); return rc; }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (c->forb_modes) { nsk_vec v = c->forb_modes; nsk_vec_free(c, 1, &v); }
+  c->forb_modes = fresh; c->forb_modes_cap = (size_t)(2 * nmodes + 1) * nv;
+  return forb_activate(c, nmodes, period, nullptr);
+}
+
+// The modes of the active Fourier orbit into state vectors (velocity components; the rest is zeroed).  A, B NULL: count and period only.
+int nsk_get_orbit_modes(nsk_ctx* c, int* nmodes, double* period, nsk_vec* A, nsk_vec* B) {
+  if (!c) return fail(NSK_EINVAL, "bad argument");
+  if (!c->d.forb) return fail(NSK_EINVAL, "nsk_get_orbit_modes: no Fourier orbit is active");
+  const int M = c->d.forb_M;
+  if (nmodes) *nmodes = M;
+  if (period) *period = c->forb_T;
+  if (!A && !B) return 0;
+  if (!A || (M > 0 && !B)) return fail(NSK_EINVAL, "nsk_get_orbit_modes: A and B, or neither");
+  const size_t nv = (size_t)c->ndim * (size_t)c->nloc;
+  for (int k = 0; k <= M; ++k) {
+    if (!A[k] || (k < M && !B[k])) return fail(NSK_EINVAL, "nsk_get_orbit_modes: null mode vector");
+    HIPCHK(hipMemsetAsync(A[k], 0, c->nstate * sizeof(double), c->stream));
+    HIPCHK(hipMemcpyAsync(A[k], c->forb_modes + (size_t)(k ? 2 * k - 1 : 0) * nv, nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (k) {
+      HIPCHK(hipMemsetAsync(B[k - 1], 0, c->nstate * sizeof(double), c->stream));
+      HIPCHK(hipMemcpyAsync(B[k - 1], c->forb_modes + (size_t)(2 * k) * nv, nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -3227,6 +3435,7 @@ int nsk_clone(nsk_ctx* P, nsk_ctx** out) {
   if (!P || !out) return fail(NSK_EINVAL, "bad argument");
   if (P->parent || P->clone_of || P->ndim != 2 || P->released) return fail(NSK_EINVAL, "nsk_clone: quadrilateral full-mesh contexts only");
   if (P->d.bf_stride) return fail(NSK_EINVAL, "nsk_clone: not with a stored base-flow orbit");
+  if (P->d.forb) return fail(NSK_EINVAL, "nsk_clone: not with a Fourier base-flow orbit");
   nsk_ctx* c = new nsk_ctx();
   auto bail = [&](int rc) { std::string keep = g_err; nsk_finalize(c); g_err = keep; return rc; };
   // scalars and options
@@ -3357,6 +3566,21 @@ int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
       HIPCHK(hipEventRecord(e1, c->stream));
     });
     c->helm_pf = keep_pf;
+  } else if (n == "baseflow_fourier") {
+    // the per-step reconstruction of a Fourier orbit (k_baseflow_fourier) at the first row of the current map's table
+    if (!c->d.forb) return fail(NSK_EINVAL, "baseflow_fourier: no Fourier orbit is active (nsk_set_orbit_fourier / nsk_set_orbit_modes)");
+    { const int rc = forb_trig_ensure(c); if (rc) return rc; }
+    d = c->d;
+    HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    DISPATCH_N(c->key, {
+      for (int r = 0; r < reps + 3; ++r) {
+        if (r == 3) HIPCHK(hipEventRecord(e0, c->stream));
+        hipLaunchKernelGGL(k_baseflow_fourier<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (double*)d.cUr, (double*)d.cUs,
+                           (double*)d.GUx, (double*)d.GUy, (double*)d.GVx, (double*)d.GVy);
+      }
+      HIPCHK(hipEventRecord(e1, c->stream));
+    });
   } else if (n == "convect_nl" || n == "convect_mfma_nl") {
     // the full equations' convection term (mode 2): thread-per-node kernel / matrix-core kernel (hexahedra, lx1 = 10)
     if (n == "convect_mfma_nl" && c->key != 110) return fail(NSK_EINVAL, "k_convect_mfma_nl<10>: hexahedra with lx1 = 10");

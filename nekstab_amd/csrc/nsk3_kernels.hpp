@@ -579,6 +579,65 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_baseflow(Dev d, const double* __
   }
 }
 
+// Time-periodic base flow from its temporal Fourier modes (fourier_reconstruction, core/fourier.f:2-21), once per linearised
+// time step in front of the convection kernel.  Phase 1: U = A_0 + sum_k A_k cos_k + B_k sin_k at the element's GLL nodes, one
+// node per thread (coalesced; the 2M factors are row `*bstep` of Dev::ftrig: wave-uniform), into LDS.  Phase 2: k_baseflow<N>
+// on that field, into the steady slot of the twelve constants.
+template <int N>
+__global__ __launch_bounds__(Cfg<N>::NT) void k_baseflow_fourier(Dev d, double* __restrict__ bfc, double*, double*, double*, double*, double*) {
+  using C = Cfg<N>;
+  constexpr int NN = C::NN, ND = C::ND, NDD = C::NDD, NT = C::NT;
+  static_assert(NT >= NN, "one thread per GLL node");
+  __shared__ double sJ[ND * N], sDd[ND * ND];
+  __shared__ double sf[NDD], t1[N * N * ND], t2[N * ND * ND], sq[3 * NN];
+  const int tid = threadIdx.x;
+  const long long e = blockIdx.x;
+  const int nm = 2 * d.forb_M + 1;
+  const int row = min(max(*d.bstep, 0), d.forb_rows - 1);
+  const double* __restrict__ tr = d.ftrig + (size_t)row * (size_t)(2 * d.forb_M);
+  if (tid < NN) {
+    const double* __restrict__ fm = d.fmodes + (size_t)e * NN + tid;
+    const size_t nl = (size_t)d.nloc;
+    double s0 = 0, s1 = 0, s2 = 0;
+#pragma unroll 4
+    for (int m = 0; m < nm; ++m) {
+      const double w = m ? tr[m - 1] : 1.0;
+      const double* a = fm + (size_t)m * 3 * nl;
+      s0 += w * a[0]; s1 += w * a[nl]; s2 += w * a[2 * nl];
+    }
+    sq[tid] = s0; sq[NN + tid] = s1; sq[2 * NN + tid] = s2;
+  }
+  for (int p = tid; p < ND * N; p += NT) sJ[p] = d.Jd[p];
+  for (int p = tid; p < ND * ND; p += NT) sDd[p] = d.Dd[p];
+  __syncthreads();
+  // from here on: k_baseflow<N>, reading the field from LDS
+  const size_t nf = (size_t)d.nfine;
+#pragma unroll 1
+  for (int c = 0; c < 3; ++c) {
+    to_fine<N>(sJ, sq + c * NN, sf, t1, t2, tid, NT);
+    for (int p = tid; p < NDD; p += NT) {
+      const int a = p % ND, b = (p / ND) % ND, cc = p / (ND * ND);
+      const size_t qq = (size_t)e * NDD + p;
+      double mt[3][3];
+#pragma unroll
+      for (int a2 = 0; a2 < 3; ++a2)
+#pragma unroll
+        for (int x = 0; x < 3; ++x) mt[a2][x] = d.mtd[(a2 * 3 + x) * nf + qq];
+      const double uf = sf[p];
+#pragma unroll
+      for (int a2 = 0; a2 < 3; ++a2) {
+        const double v = mt[a2][c] * uf;
+        bfc[a2 * nf + qq] = (c == 0) ? v : bfc[a2 * nf + qq] + v;
+      }
+      double g[3];
+      fine_grad<N>(sDd, sf, a, b, cc, g);
+#pragma unroll
+      for (int x = 0; x < 3; ++x) bfc[(3 + 3 * c + x) * nf + qq] = mt[0][x] * g[0] + mt[1][x] * g[1] + mt[2][x] * g[2];
+    }
+    lds_barrier();
+  }
+}
+
 // ---------------------------------------------------------------------------
 // K2: makextp + makebdfp + lagfieldp + extrapprp + cresvipp  [UPSTREAM perturb.f]
 // ---------------------------------------------------------------------------
@@ -592,7 +651,7 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_rhs(Dev d, StepCoef sc) {
   double* sP = reg; double* sC = reg + 3 * MM; double* sE = sC + 3 * NMM;
   double* su = reg; double* st = reg + NN;
   const int tid = threadIdx.x;
-  if (d.bf_stride && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;     // next step reads the next orbit slot (as the 2-D k_rhs)
+  if ((d.bf_stride || d.forb) && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;     // next step reads the next orbit slot / trig row (as the 2-D k_rhs)
   if (d.stepctr && blockIdx.x == 0 && tid == 0) *d.stepctr += 1;                          // per-step iteration record (rec_step_iters)
   const long long e = blockIdx.x;
   const bool act = tid < NN;

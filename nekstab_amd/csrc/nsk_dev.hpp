@@ -98,6 +98,12 @@ struct Dev {
   double nl_spng_str;
   int* bstep;                              // time-periodic base flow (Floquet): device step counter and the
   long long bf_stride;                     // stride between the stored per-step base-flow constants (0: steady)
+  // Fourier-compressed periodic base flow (core/fourier.f; nsk_set_orbit_fourier / nsk_set_orbit_modes): the orbit as its
+  // temporal modes fmodes [2 forb_M + 1][ndim][nloc] = A_0, A_1, B_1, ..; k_baseflow_fourier rebuilds the steady slot of the
+  // base-flow constants from them before the convection of every linearised step, with the cos / sin factors of row `*bstep`
+  // of ftrig [forb_rows][2 forb_M].  bf_stride stays 0: every consumer kernel reads the steady slot as it is.
+  int forb, forb_M, forb_rows;
+  const double *fmodes, *ftrig;
   // gather-scatter (dssum) as a gather: CSR of co-located local nodes, ascending
   const int *gs_off, *gs_idx;
   const int4* gs_tab;

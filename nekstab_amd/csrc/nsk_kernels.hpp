@@ -549,6 +549,77 @@ __global__ __launch_bounds__(Cfg<N>::NTD) void k_baseflow(Dev d, const double* _
   }
 }
 
+// Time-periodic base flow from its temporal Fourier modes (fourier_reconstruction, core/fourier.f:2-21), once per linearised
+// time step in front of k_convect: phase 1 sums U = A_0 + sum_k A_k cos_k + B_k sin_k at the element's GLL nodes into LDS
+// (the 2M factors are row `*bstep` of Dev::ftrig: wave-uniform), phase 2 is k_baseflow<N> on that field, into the steady slot.
+// An element has fewer nodes than the workgroup has threads: NT / NN thread groups share the modes, their partial sums are
+// added in group order (the result does not depend on timing).
+template <int N>
+__global__ __launch_bounds__(Cfg<N>::NTD) void k_baseflow_fourier(Dev d, double* cUr, double* cUs, double* GUx, double* GUy,
+                                                                  double* GVx, double* GVy) {
+  using C = Cfg<N>;
+  constexpr int NN = C::NN, ND = C::ND, NDD = C::NDD, NT = C::NTD, G = NT / NN;
+  static_assert(G >= 1, "one thread per GLL node");
+  __shared__ double sJ[ND * N], sDd[ND * ND];
+  __shared__ double su[2][NN], st[2][N * ND], sf[2][NDD], sp[G][2][NN];
+  const int tid = threadIdx.x;
+  const long long e = blockIdx.x;
+  const int nm = 2 * d.forb_M + 1;
+  const int row = min(max(*d.bstep, 0), d.forb_rows - 1);
+  const double* __restrict__ tr = d.ftrig + (size_t)row * (size_t)(2 * d.forb_M);
+  const double* __restrict__ fm = d.fmodes;
+  const int g = tid / NN, nd = tid % NN;
+  if (g < G) {
+    double s0 = 0, s1 = 0;
+#pragma unroll 4
+    for (int m = g; m < nm; m += G) {
+      const double w = m ? tr[m - 1] : 1.0;
+      const double* a = fm + (size_t)m * 2 * (size_t)d.nloc + (size_t)e * NN + nd;
+      s0 += w * a[0]; s1 += w * a[d.nloc];
+    }
+    sp[g][0][nd] = s0; sp[g][1][nd] = s1;
+  }
+  for (int k = tid; k < ND * N; k += NT) sJ[k] = d.Jd[k];
+  for (int k = tid; k < NDD; k += NT) sDd[k] = d.Dd[k];
+  __syncthreads();
+  if (tid < NN) {
+    double s0 = sp[0][0][tid], s1 = sp[0][1][tid];
+#pragma unroll
+    for (int q = 1; q < G; ++q) { s0 += sp[q][0][tid]; s1 += sp[q][1][tid]; }
+    su[0][tid] = s0; su[1][tid] = s1;
+  }
+  __syncthreads();
+  // from here on: k_baseflow<N>
+  if (tid < N * ND) {
+    const int j = tid / ND, a = tid % ND;
+    double s0 = 0, s1 = 0;
+    for (int i = 0; i < N; ++i) { const double w = sJ[a * N + i]; s0 += w * su[0][j * N + i]; s1 += w * su[1][j * N + i]; }
+    st[0][tid] = s0; st[1][tid] = s1;
+  }
+  __syncthreads();
+  const int b = tid / ND, a = tid % ND;
+  const bool fact = tid < NDD;
+  if (fact) {
+    double s0 = 0, s1 = 0;
+    for (int j = 0; j < N; ++j) { const double w = sJ[b * N + j]; s0 += w * st[0][j * ND + a]; s1 += w * st[1][j * ND + a]; }
+    sf[0][tid] = s0; sf[1][tid] = s1;
+  }
+  __syncthreads();
+  if (fact) {
+    double Ur = 0, Us = 0, Vr = 0, Vs = 0;
+    for (int k = 0; k < ND; ++k) {
+      const double dr = sDd[a * ND + k], ds = sDd[b * ND + k];
+      Ur += dr * sf[0][b * ND + k]; Us += ds * sf[0][k * ND + a];
+      Vr += dr * sf[1][b * ND + k]; Vs += ds * sf[1][k * ND + a];
+    }
+    const long long qq = e * NDD + tid;
+    const double rx = d.rxd[qq], ry = d.ryd[qq], sx = d.sxd[qq], sy = d.syd[qq], Uf = sf[0][tid], Vf = sf[1][tid];
+    cUr[qq] = rx * Uf + ry * Vf; cUs[qq] = sx * Uf + sy * Vf;
+    GUx[qq] = rx * Ur + sx * Us; GUy[qq] = ry * Ur + sy * Us;
+    GVx[qq] = rx * Vr + sx * Vs; GVy[qq] = ry * Vr + sy * Vs;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // K2: makextp + makebdfp + lagfieldp + extrapprp + cresvipp  [UPSTREAM perturb.f]
 //   r_loc = EXT(bf) + BDF lags + D^T p* - H u^n   (unassembled)
@@ -568,7 +639,7 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_rhs(Dev d, StepCoef sc) {
   static_assert(NT >= NN, "one basis entry per thread");
   BasisRegs<N> br;
   br.issue(d, tid, true, true);
-  if (d.bf_stride && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;     // next step reads the next orbit slot
+  if ((d.bf_stride || d.forb) && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;     // next step reads the next orbit slot / trig row
   if (d.stepctr && blockIdx.x == 0 && tid == 0) *d.stepctr += 1;                          // per-step iteration record (rec_step_iters)
   if (d.nproj_max > 0 && blockIdx.x == 0 && tid == 0) {
     GmresScal* G = d.gsc;
@@ -2629,6 +2700,19 @@ __global__ void k_project_out_acc(double* __restrict__ f, const double* const* _
 __global__ void k_axpby(double* __restrict__ y, double a, const double* __restrict__ x, double b, long long n) {
   const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (l < n) y[l] = a * x[l] + b * y[l];
+}
+
+// One snapshot of the orbit into its temporal Fourier modes (fourier_decomposition, core/fourier.f:23-88, as a running sum:
+// no snapshot is stored): fm[m][i] += w[m] u[i], m = 0 .. nm-1, over the ndim * nloc velocity values of the stepper's field u
+// (component stride cs).  w = this snapshot's row of the host-built coefficient table (uniform loads).
+__global__ __launch_bounds__(256) void k_orbit_dft(double* __restrict__ fm, const double* __restrict__ u, const double* __restrict__ w,
+                                                   int nm, long long nloc, long long cs, int ndim) {
+  const long long nv = (long long)ndim * nloc;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
+    const double v = u[(i / nloc) * cs + i % nloc];
+#pragma unroll 4
+    for (int m = 0; m < nm; ++m) fm[(size_t)m * (size_t)nv + i] += w[m] * v;
+  }
 }
 
 // scale by 1/sqrt(*nrm2) read from device memory (krylov_normalize without a host round trip)

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_helm_fused(Dev d, StepCoef sc
   load_basis<N, EPB>(d, sD, sDt, sJ12, sD12, tid, NT);
 
   // ================= K2 (k_rhs) =================
-  if (d.bf_stride && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;
+  if ((d.bf_stride || d.forb) && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;
   if (d.stepctr && blockIdx.x == 0 && tid == 0) *d.stepctr += 1;
   if (d.nproj_max > 0 && blockIdx.x == 0 && tid == 0) {
     GmresScal* G = d.gsc;

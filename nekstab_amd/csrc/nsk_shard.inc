@@ -200,7 +200,7 @@ static int shard_fill(nsk_ctx* c, nsk_ctx* P, const int* part, int rank, int nra
   d.cs = nloc + c->nvh; d.nranks = nranks; d.rank = rank; d.dbg = nullptr;
   d.nproj_max = P->d.nproj_max;                            // the projection space of the pinned operator (Nek's residualProj), per shard
   d.PX = d.PEX = d.PD = d.PED = d.ppart = nullptr;
-  d.spng_vr = nullptr; d.nl_spng_str = 0.0; d.bstep = nullptr; d.bf_stride = 0;
+  d.spng_vr = nullptr; d.nl_spng_str = 0.0; d.bstep = nullptr; d.bf_stride = 0; d.forb = 0;
 
   // ---- Schwarz overlap halo of the pressure vector
   std::vector<int> p_idx((size_t)nel * PS, -1);
