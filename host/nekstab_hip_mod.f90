@@ -35,6 +35,7 @@ module nekstab_hip
     real(c_double) :: step_budget_helm_mean, step_budget_pres_mean
     integer(c_long_long) :: tail_maps
     integer(c_long_long) :: zero_arrays
+    integer(c_long_long) :: absorb_maps
   end type
 
   interface

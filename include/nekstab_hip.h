@@ -284,6 +284,9 @@ typedef struct {
   long long zero_arrays;                    /* hexahedra: bit mask of the arrays that are zero on every node and therefore not loaded: bits 0-8 the
                                                nine metric terms, 9-11 the G factors g4 g5 g6 (set-up), 12-23 the twelve base-flow constants of the
                                                convection kernel (nsk_set_baseflow); 0 on quadrilaterals, on deformed meshes, with option zero_metrics = 0 */
+  long long absorb_maps;                    /* maps since init whose time steps ran without a k_proj_update launch: the update of the pressure projection
+                                               space applied by its next readers (option "proj_absorb"; one flush launch per map).  0 wherever the option
+                                               does not apply: hexahedra, shards, host-checked meshes, fuse2 = 0, nproj = 0 */
 } nsk_stats;
 int nsk_get_stats(nsk_ctx* ctx, nsk_stats* s);
 

@@ -142,6 +142,7 @@ struct nsk_ctx {
   int tail_ok = -1;                      // residency verdict (-1: not asked yet)
   int tail_off_h = 0, tail_off_p = 0;    // heads = median + these (options "tail_off_h" / "tail_off_p": tests push work into the tails with negative values)
   long long tail_maps = 0;
+  long long absorb_maps = 0;             // maps run with the deferred update of the projection space (option "proj_absorb")
   long long sb_maps = 0, sb_steps = 0, sb_launch_h = 0, sb_launch_p = 0;     // maps / time steps run on per-step budgets and their budgeted launches (diagnostics)
   bool last_map_per_step = false;        // the map just run took the per-step budgets
   std::map<std::array<int, 4>, hipGraphExec_t> gcache;         // (adjoint, class, nh, np) -> captured step
@@ -151,6 +152,8 @@ struct nsk_ctx {
   int tc32 = 0;                         // k_divgs_t: the fp32 copy of the coarse image (0 = never (default: it moves a map by 2e-8 for 0.6 us per iteration), 1 = always, -1 = where the solve's relative tolerance is >= 1e-5; option "tc32", NSK_TC32)
   int skip_close = 1;                   // no closing launch behind a pressure tail that covers the merged range (option "skip_close", NSK_SKIP_CLOSE; measured +0.3 %)
   int sb_pct = 90;                      // per-step budgets behind the safety-net tail: percentile of the window's counts (100 = the largest, rounds 5 to mid-6; option "sb_pct", NSK_SB_PCT; 90 measured +0.6 %, with skip_close +1.3 %: profiles/r06_ab_fuse2.txt)
+  int proj_absorb = -1;                 // the update of the pressure projection space of step s applied by its first readers in step s + 1 (k_pres_rhs, k_proj_apply_e) instead of a k_proj_update launch per step: -1 = where the solve starts inside A_0 (absorb_on), 0 = never, 1 = the same as -1 (contexts without that start ignore it); option "proj_absorb"
+  bool up_host = false;                 // steps with the deferred update are queued and no flush behind them yet (flush_proj)
   int fuse2_start = 1;                  // ... and the solve's start inside its first launch (k_proj_apply_e; no k_gmres_update(-1) launch); option "fuse2_start", NSK_FUSE2_START
   int fuse2 = 1;                        // round 6: the merged iteration in TWO launches (k_schwarz_uc, k_divgs_t; option "fuse2", NSK_FUSE2); 0 = the three launches of rounds 3-5
   double* kacc = nullptr;               // nsk_orth: coefficients accumulated over the two passes + the squared norm (device)
@@ -1007,6 +1010,16 @@ static void launch_proj_apply_e(nsk_ctx* c, const Dev& d) {
   hipLaunchKernelGGL(nsk::k2::k_proj_apply_e<N>, dim3(c->nblk), dim3(256), 0, c->stream, d);
 }
 template <int N>
+static void launch_rhs_absorb(nsk_ctx* c, const Dev& d, const StepCoef& sc) {      // (quadrilaterals only: absorb_on) the element workgroups + the bookkeeping workgroup
+  if (c->ndim != 2) return;
+  hipLaunchKernelGGL((nsk::k2::k_rhs<N, true>), dim3(c->nblk + 1), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
+}
+template <int N>
+static void launch_pres_rhs_absorb(nsk_ctx* c, const Dev& d, const StepCoef& sc, int helm_par, int check_helm) {      // (quadrilaterals only: absorb_on)
+  if (c->ndim != 2) return;
+  hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
+}
+template <int N>
 static void launch_divgs_t(nsk_ctx* c, const Dev& d, int j) {
   if (c->ndim != 2) return;
   if (d.tc32) hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, true>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
@@ -1043,6 +1056,28 @@ static bool hostcheck_on(const nsk_ctx* c) {
   // (measured: 0.262 -> 0.334 Arnoldi steps per second, scripts/cfg3_hostcheck_ab.sh)
   if (c->ndim == 2) return c->nblk > 4096;
   return c->nel >= 8192;
+}
+
+// Deferred update of the pressure projection space (option "proj_absorb"): exactly the contexts whose every pressure solve starts
+// inside A_0 (f2start of pres_solve_launch, which refuses a step that disagrees) and whose velocity solve is launched per
+// iteration.  Everything else -- hexahedra, shards, host-checked meshes, fuse2 = 0, nproj = 0, the operator tests -- keeps the
+// k_proj_update launch per step, whatever the option says.
+static bool absorb_on(const nsk_ctx* c) {
+  const Dev& d = c->d;
+  if (c->proj_absorb == 0 || c->fused || c->in_test || c->parent || hostcheck_on(c)) return false;
+  if (!(c->merged_update && c->ndim == 2 && d.coarse_lda <= 3072 && !d.use_tot && d.nranks <= 1 && d.rch && d.ecv)) return false;
+  if (!(fuse2_on(c) && c->fuse2_start && d.nproj_max > 0 && d.nproj_max <= MAXPROJ)) return false;
+  return c->max_pres > 0 && std::min(c->merged_iters, c->gmres_cycle) > 0;
+}
+// A map ends, or something is about to read, copy or reset the space: the update its last step left behind goes in with the
+// standalone kernel (one launch per map), and the context looks as it does without the option.
+static int flush_proj(nsk_ctx* c) {
+  if (!c->up_host) return 0;
+  c->up_host = false;
+  Dev d = c->d; d.absorb = 1;                              // (k_proj_update: only if GmresScal::up_pending says so)
+  hipLaunchKernelGGL(k_proj_update, dim3(c->nblk), dim3(256), 0, c->stream, d);
+  HIPCHK(hipMemsetAsync((char*)c->d.gsc + offsetof(GmresScal, up_pending), 0, sizeof(int), c->stream));
+  return 0;
 }
 
 // hexahedral GMRES column j in the lagged form: streaming Gram-Schmidt pass (first-pass subtraction, second-pass dots, the
@@ -1202,8 +1237,9 @@ static void launch_proj_dots3(nsk_ctx* c, const Dev& d) {
 }
 
 template <int N> static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double scale, int min_iter, int ord, bool start = false);
-static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_mul = 1.0, bool allow_cap = false, bool hc = false, bool tail = false) {
+static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_mul = 1.0, bool allow_cap = false, bool hc = false, bool tail = false, bool absorb = false) {
   Dev d = c->d;                                            // by value: the early steps of a map run with a tighter tolerance
+  d.absorb = absorb ? 1 : 0;
   d.tol_pres = early_tol(d, tol_mul);
   // time steps >= 4: optionally a bounded solve (min_pres_iter .. pres_cap iterations): nothing is launched beyond the cap
   if (c->pres_cap > 0 && ord >= 3 && allow_cap && c->ndim == 2) {   // validated on quadrilateral linearised maps only
@@ -1224,6 +1260,7 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
     //  different groups, so a step that switched form with its budget would change bits between otherwise identical runs)
     const bool f2start = merged0 && fuse2_on(c) && c->fuse2_start && d.nproj_max > 0 && d.nproj_max <= MAXPROJ && !c->in_test && np > 0 &&
                          std::min(c->merged_iters, c->gmres_cycle) > 0;
+    if (absorb && !f2start) return fail(NSK_EINVAL, "internal: deferred projection update in a step whose pressure solve does not start inside A_0");
     if (f2start) launch_proj_apply_e<N>(c, d);
     else if (d.nproj_max > 0 && !c->in_test) { hipLaunchKernelGGL(k_proj_apply, dim3(c->nblk), dim3(256), 0, c->stream, d); tot_rows(c, d.gpart, 1, d.gtot); }
     if (!f2start) hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, -1, scale, c->min_pres, ord);
@@ -1436,10 +1473,14 @@ static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double sc
   else hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 12>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
 }
 
-static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_over = -1, bool tail = false) {
+static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_over = -1, bool tail = false, bool in_map = false) {
   Dev& d = c->d;
   const StepCoef sc = make_coef(c, istep, adjoint);
   const bool hc = hostcheck_on(c) && !stream_capturing(c->stream);
+  // the steps of a map (run_map flushes behind the last one) with the deferred update of the projection space: k_rhs gets
+  // the bookkeeping workgroup, k_pres_rhs / k_proj_apply_e apply the last step's update, no k_proj_update launch
+  const bool absorb = in_map && absorb_on(c);
+  Dev da = d; da.absorb = absorb ? 1 : 0;
   int nh = hc ? c->max_helm : (nh_over > 0 ? nh_over : c->cur_helm[sc.cls]);
   DISPATCH_N(c->key, {
     constexpr int NT = Cfg<N>::NT;
@@ -1461,7 +1502,8 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       HIPCHK(hipMemsetAsync(c->sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
       launch_fused<N>(c, sc);
     } else {
-      hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc);
+      if (absorb) launch_rhs_absorb<N>(c, da, sc);
+      else hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc);
       if (tail) nh = std::max(1, std::min(nh, c->max_helm - 1));      // HEAD launches; the persistent tail runs launches nh .. max_helm-1
       for (int it = 0; it < nh; ++it) {
         launch_helm_iter<N>(c, d, sc, it, (const double*)d.rloc);
@@ -1474,15 +1516,16 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
         }
       }
       if (tail) { launch_helm_tail<N>(c, d, sc, nh, c->max_helm); nh = c->max_helm; }
-      hipLaunchKernelGGL(k_pres_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc, (nh - 1) & 1, nh - 1);
+      if (absorb) launch_pres_rhs_absorb<N>(c, da, sc, (nh - 1) & 1, nh - 1);
+      else hipLaunchKernelGGL(k_pres_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc, (nh - 1) & 1, nh - 1);
     }
   });
   // The first steps of a map project out whatever divergence the input vector has (a noise seed is far from
   // solenoidal): an error there survives to the end of the map, so those solves are converged further.
-  int rc = pres_solve_launch(c, sc.h2, sc.cls, hc ? c->max_pres : (np_over > 0 ? np_over : c->cur_pres[sc.cls]), istep <= 3 ? c->early_pres_mul : 1.0, adjoint != 2, hc, tail);
+  int rc = pres_solve_launch(c, sc.h2, sc.cls, hc ? c->max_pres : (np_over > 0 ? np_over : c->cur_pres[sc.cls]), istep <= 3 ? c->early_pres_mul : 1.0, adjoint != 2, hc, tail, absorb);
   if (rc) return rc;
   const bool flat = flat_proj_on(c);
-  Dev df = d; df.flat_proj = flat ? 1 : 0;
+  Dev df = da; df.flat_proj = flat ? 1 : 0;
   DISPATCH_N(c->key, {
     if (flat) launch_pres_comb3<N>(c, df, sc);
     else hipLaunchKernelGGL(k_pres_update<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, d, sc);
@@ -1492,8 +1535,10 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       hipLaunchKernelGGL(k_vel_update_proj<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, df, sc);
       if (flat) launch_proj_dots3<N>(c, df);
     });
-    tot_rows(c, d.ppart, MAXPROJ + 1, d.ptot);
-    hipLaunchKernelGGL(k_proj_update, dim3(c->nblk), dim3(256), 0, c->stream, d);
+    if (!absorb) {
+      tot_rows(c, d.ppart, MAXPROJ + 1, d.ptot);
+      hipLaunchKernelGGL(k_proj_update, dim3(c->nblk), dim3(256), 0, c->stream, d);
+    }
   } else {
     hipLaunchKernelGGL(k_vel_update, dim3((unsigned)((d.nloc + 255) / 256)), dim3(256), 0, c->stream, d, sc);
   }
@@ -1509,7 +1554,7 @@ static int ensure_graph(nsk_ctx* c, int cls, int adjoint) {
   if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
   hipGraph_t graph = nullptr;
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = step(c, CLS_ISTEP[cls], adjoint);
+  int rc = step(c, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
   if (rc) return rc;
   if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1530,7 +1575,7 @@ static int ensure_graph_multi(nsk_ctx* c, int adjoint) {
   hipGraph_t graph = nullptr;
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
-  for (int r = 0; r < c->graph_steps && !rc; ++r) rc = step(c, CLS_ISTEP[cls], adjoint);
+  for (int r = 0; r < c->graph_steps && !rc; ++r) rc = step(c, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
   if (rc) return rc;
   if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1553,7 +1598,7 @@ static int graph_for(nsk_ctx* c, int adjoint, int cls, int nh, int np, hipGraphE
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = step(c, CLS_ISTEP[cls], adjoint, nh, np, tail);
+  int rc = step(c, CLS_ISTEP[cls], adjoint, nh, np, tail, true);
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
   if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
   if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1639,6 +1684,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
     if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
     HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
   }
+  if (absorb_on(c)) { c->up_host = true; c->absorb_maps++; }
   for (int istep = 1; istep <= c->nsteps; ++istep) {
     if (per_step) {
       HIPCHK(hipGraphLaunch(plan[istep - 1], c->stream));
@@ -1650,7 +1696,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
       }
       HIPCHK(hipGraphLaunch(c->graphs[adjoint][step_class(istep)].exec, c->stream));
     } else {
-      int rc = step(c, istep, adjoint);
+      int rc = step(c, istep, adjoint, -1, -1, false, true);
       if (rc) return rc;
       if (c->debug) {
         GmresScal G; double hs[32];
@@ -1665,6 +1711,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
       }
     }
   }
+  { int rc = flush_proj(c); if (rc) return rc; }          // the last step's update of the projection space: the context between maps is what it is without the option
   for (int cc = 0; cc < c->ndim; ++cc)
     HIPCHK(hipMemcpyAsync(f + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(f + c->ndim * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -1794,6 +1841,7 @@ static int reset_solver_state(nsk_ctx* c) {
     HIPCHK(hipMemsetAsync(p, 0, it->second, c->stream));
   }
   c->state_dirty = false;
+  c->up_host = false;                                      // (GmresScal::up_pending went with the rest)
   return 0;
 }
 
@@ -1917,6 +1965,7 @@ int nsk_shard_create(nsk_ctx* parent, const int* part, int rank, int nranks, nsk
   if (!parent || !part || !out) return fail(NSK_EINVAL, "bad argument");
   if (parent->released) return fail(NSK_EINVAL, "parent context was released (nsk_shard_release_parent)");
   if (parent->nscal > 0) return fail(NSK_EINVAL, "sharded vectors do not carry scalar fields yet");
+  { int rc = flush_proj(parent); if (rc) return rc; }
   return shard_create(parent, part, rank, nranks, out);
 }
 
@@ -2460,6 +2509,11 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
   else if (n == "merged_update") { c->merged_update = (int)value; invalidate_graphs(c); }
   else if (n == "fuse2") { c->fuse2 = (int)value; c->tail_ok = -1; invalidate_graphs(c); }
   else if (n == "tc32") { c->tc32 = (int)value; invalidate_graphs(c); }
+  else if (n == "proj_absorb") {
+    if (value != -1.0 && value != 0.0 && value != 1.0) return fail(NSK_EINVAL, "proj_absorb: -1, 0 or 1");
+    int rc = flush_proj(c); if (rc) return rc;
+    c->proj_absorb = (int)value;
+  }
   else if (n == "fuse2_start") { c->fuse2_start = (int)value; invalidate_graphs(c); }
   else if (n == "sb_pct") { c->sb_pct = (int)value; }
   else if (n == "skip_close") { c->skip_close = (int)value; invalidate_graphs(c); }
@@ -2622,6 +2676,7 @@ int nsk_get_stats(nsk_ctx* c, nsk_stats* s) {
   s->total_pres_jsum = c->tot_pres_jsum; s->coarse_bytes_per_solve = c->coarse_bytes;
   s->step_budget_maps = c->sb_maps;
   s->tail_maps = c->tail_maps;
+  s->absorb_maps = c->absorb_maps;
   s->zero_arrays = (long long)c->d.zmask | ((long long)c->d.bfmask << 12);
   s->step_budget_helm_mean = c->sb_maps ? (double)c->sb_launch_h / ((double)c->sb_steps) : 0.0;
   s->step_budget_pres_mean = c->sb_maps ? (double)c->sb_launch_p / ((double)c->sb_steps) : 0.0;
@@ -3436,6 +3491,7 @@ int nsk_clone(nsk_ctx* P, nsk_ctx** out) {
   if (P->parent || P->clone_of || P->ndim != 2 || P->released) return fail(NSK_EINVAL, "nsk_clone: quadrilateral full-mesh contexts only");
   if (P->d.bf_stride) return fail(NSK_EINVAL, "nsk_clone: not with a stored base-flow orbit");
   if (P->d.forb) return fail(NSK_EINVAL, "nsk_clone: not with a Fourier base-flow orbit");
+  { int rc = flush_proj(P); if (rc) return rc; }
   nsk_ctx* c = new nsk_ctx();
   auto bail = [&](int rc) { std::string keep = g_err; nsk_finalize(c); g_err = keep; return rc; };
   // scalars and options
@@ -3542,6 +3598,7 @@ int nsk_get_step_iters(nsk_ctx* c, int n, int* helm, int* pres, int* nsteps) {
 int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
   if (!c || !name || reps < 1 || !avg_us) return fail(NSK_EINVAL, "bad argument");
   const std::string n(name);
+  { int rc = flush_proj(c); if (rc) return rc; }
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
   Dev d = c->d;

@@ -46,6 +46,15 @@ struct GmresScal {               // device-resident small state of one pressure 
   double pc[MAXMR + 2];
   double phinv;
   int pending;
+  // deferred update of the projection space (option "proj_absorb"): the update that k_proj_update would launch behind step s
+  // is applied by the first two readers of the space in step s + 1 (k_pres_rhs: PX, k_proj_apply_e: PEX).  up_pending is
+  // set by k_vel_update_proj of step s; the bookkeeping workgroup of the next k_rhs -- a launch of its own between the two --
+  // sums the partials, stages and commits the append (st_*, pn, pcnt, nproj) and leaves this snapshot of what the update
+  // needs: no reader takes a scalar that a workgroup of its own launch writes (k_proj_apply_e rewrites pa)
+  double up_cf[MAXPROJ];         // coefficient of x_k in the new vector (cf of k_proj_update)
+  double up_as;                  // a_s of the merged slot (proj_restart = 0)
+  int up_pending, up_apply;      // a step left an update behind / this step's readers apply it
+  int up_np, up_s, up_restart;   // vectors before the update, slot written, restart on the total solution
 };
 
 // Step classes: one captured hipGraph and one launch budget each.  Time steps 1, 2, 3 differ in BDF/EXT order and
@@ -146,6 +155,7 @@ struct Dev {
   int nvl;
   double* Wr;
   const double* wraw;
+  int absorb;                    // set per launch: the update of the projection space is deferred into the next step's readers (GmresScal::up_*)
   int uc_start;                  // set per launch (A_0 only): the solve starts inside k_schwarz_uc (g' raw in Wr, written by k_proj_apply_e)
   GmresScal* gsc;
   // projection onto previous pressure solutions (E-orthonormal)

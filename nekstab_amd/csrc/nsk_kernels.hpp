@@ -620,11 +620,87 @@ __global__ __launch_bounds__(Cfg<N>::NTD) void k_baseflow_fourier(Dev d, double*
   }
 }
 
+// Bookkeeping of the pressure projection space with the deferred update (Dev::absorb): ONE extra workgroup of k_rhs, next to
+// the element workgroups and shorter than they are.  It is the one point where an append is staged AND committed: a staged
+// update of the standalone k_proj_update (map-end flush) is committed as k_rhs block 0 does it without the option; an update
+// that k_vel_update_proj left pending is staged here -- the sums of its partial rows, cf[] and the (delta, E delta) norm with
+// the expressions and the summation order of k_proj_update -- and committed, and its operands go to the snapshot
+// GmresScal::up_* that k_pres_rhs and k_proj_apply_e of this step read.  Those two launches and everything behind them see
+// the committed nproj; nothing of this launch reads what this workgroup writes.  (The partial rows were written by the last
+// step's k_vel_update_proj and are rewritten by this step's k_pres_rhs, a later launch: no second buffer is needed.)
+template <int NT>
+__device__ inline void proj_book(const Dev& d, const StepCoef& sc) {
+  __shared__ double sh[MAXPROJ + 1];
+  __shared__ double spn[MAXPROJ], spa[MAXPROJ], stm[MAXPROJ];
+  const int tid = threadIdx.x;
+  GmresScal* G = d.gsc;
+  // every load of this workgroup goes out before the first wait: all MAXPROJ + 1 partial rows (a bound known from the kernel
+  // arguments, as k_proj_update issues them) next to the scalars -- two trips to memory in all
+  const bool regs = NT == 256 && d.nblk <= 512;
+  PartialRows<5> pr0, pr1;              // rows 0..19 and 20..39
+  pr0.issue(d.ppart, d.nblk, regs ? d.nproj_max + 1 : 0, tid, 0);
+  pr1.issue(d.ppart, d.nblk, regs ? d.nproj_max + 1 : 0, tid, 20);
+  const int np = G->nproj, nmax = d.nproj_max, pcnt = G->pcnt;
+  const bool staged = G->st_pending != 0;
+  const bool defer = !staged && G->up_pending != 0;          // (uniform over the workgroup)
+  const double pnv = (tid < MAXPROJ) ? G->pn[tid] : 1.0;
+  const double pav = (tid < MAXPROJ) ? G->pa[tid] : 0.0;
+  const bool full = np >= nmax;
+  const bool restart = full && d.proj_restart;
+  const int s = restart ? 0 : (full ? pcnt % nmax : np);          // slot written
+  double st_n = G->st_n;
+  int st_slot = G->st_slot;
+  if (defer) {
+    const double as = (!restart && s < np) ? G->pa[s] : 0.0;
+    if (tid < MAXPROJ) { spn[tid] = pnv; spa[tid] = pav; }      // (thread 0's loop below reads them from LDS: a global load per term is a trip to memory each)
+    if (regs) {
+      pr0.reduce(d.ppart, d.nblk, np + 1, sh, tid, 0, false);
+      pr1.reduce(d.ppart, d.nblk, np + 1, sh, tid, 20);                   // (+ the barrier)
+    } else sum_partials_multi(d.ppart, d.nblk, np + 1, sh, tid, NT);
+    if (tid < np) {
+      G->up_cf[tid] = ((!restart && tid == s) ? 0.0 : sh[tid] / pnv) - (restart ? pav : 0.0);
+      stm[tid] = sh[tid] * sh[tid] / pnv;                  // the terms of the norm below: the same product and quotient, formed side by side
+    }
+    lds_barrier();
+    if (tid == 0) {
+      double nn = sh[np];                                   // (delta, E delta)
+      for (int k = 0; k < np; ++k) if (restart || k != s) nn -= stm[k];
+      if (restart) { for (int k = 0; k < np; ++k) nn += spa[k] * spa[k] * spn[k]; }
+      else if (s < np) nn += as * as * spn[s] + 2.0 * as * sh[s];
+      st_n = nn; st_slot = restart ? -1 : s;
+      G->st_n = nn; G->st_slot = st_slot;
+      G->up_as = as; G->up_np = np; G->up_s = s; G->up_restart = restart ? 1 : 0;
+    }
+  }
+  __syncthreads();                               // every read of pn / pa above is behind us
+  if (tid == 0) {
+    if (staged || defer) {
+      G->st_pending = 0;
+      if (st_n > 0.0) {
+        if (st_slot < 0) {                           // restart of a full space on the latest total solution
+          G->pn[0] = st_n; G->pcnt = 1; G->nproj = 1;
+        } else {
+          G->pn[st_slot] = st_n;
+          G->pcnt = pcnt + 1;
+          G->nproj = (pcnt + 1 < nmax) ? pcnt + 1 : nmax;
+        }
+      } else {              // degenerate direction: drop the whole space and start again
+        G->pcnt = 0; G->nproj = 0;
+      }
+    }
+    if (d.proj_reset && sc.cls == 0) { G->pcnt = 0; G->nproj = 0; }      // first step of a map: the space of the last map is stale
+    G->up_apply = defer ? 1 : 0;
+    G->up_pending = 0;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // K2: makextp + makebdfp + lagfieldp + extrapprp + cresvipp  [UPSTREAM perturb.f]
 //   r_loc = EXT(bf) + BDF lags + D^T p* - H u^n   (unassembled)
 // ---------------------------------------------------------------------------
-template <int N>
+// AB: the instantiation of the steps with the deferred update of the projection space -- one workgroup more, the bookkeeping
+// workgroup proj_book; every other launch keeps the plain one
+template <int N, bool AB = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_rhs(Dev d, StepCoef sc) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NT = C::NT, NM = N * M;
@@ -637,11 +713,14 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_rhs(Dev d, StepCoef sc) {
   const int j = nd / N, i = nd % N;
   const long long l = e * NN + nd, nl = d.cs;
   static_assert(NT >= NN, "one basis entry per thread");
+  if constexpr (AB) {
+    if (blockIdx.x == (unsigned)d.nblk) { proj_book<NT>(d, sc); return; }     // the extra workgroup of the deferred update
+  }
   BasisRegs<N> br;
   br.issue(d, tid, true, true);
   if ((d.bf_stride || d.forb) && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;     // next step reads the next orbit slot / trig row
   if (d.stepctr && blockIdx.x == 0 && tid == 0) *d.stepctr += 1;                          // per-step iteration record (rec_step_iters)
-  if (d.nproj_max > 0 && blockIdx.x == 0 && tid == 0) {
+  if (d.nproj_max > 0 && !AB && blockIdx.x == 0 && tid == 0) {
     GmresScal* G = d.gsc;
     if (G->st_pending) {
       G->st_pending = 0;
@@ -901,7 +980,9 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_helm(Dev d, StepCoef sc, int it,
 // K4: u* = u + du ;  g = -D u*  -> V[0] (unnormalised), |g|^2 partials
 //     also verifies that the Helmholtz solve converged.   [UPSTREAM incomprp]
 // ---------------------------------------------------------------------------
-template <int N>
+// AB: the instantiation of the steps with the deferred update of the projection space (Dev::absorb); every other launch keeps
+// the plain one
+template <int N, bool AB = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_rhs(Dev d, StepCoef sc, int helm_par, int check_helm) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NT = C::NT, NM = N * M;
@@ -933,6 +1014,20 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_rhs(Dev d, StepCoef sc, int
       l1_[c] = d.dulag[lc]; l2_[c] = d.dulag[2 * nl + lc]; l3_[c] = d.dulag[4 * nl + lc];
       hx_[c] = d.hx[lc]; un_[c] = d.u[lc];
     }
+  }
+  // deferred update of the projection space (Dev::absorb): the last step's new vector  x = delta - sum_k cf_k x_k (+ a_s x_s)
+  // is formed further down from the pxr[] above, with the scalars that the bookkeeping workgroup of this step's k_rhs left in
+  // GmresScal::up_* (uniform loads) -- its only other operand, behind the loads for u*
+  // (everything is loaded here whether an update is pending or not: a load behind the flag would be one more trip to memory)
+  const GmresScal* Gu = d.gsc;
+  __shared__ double scf[MAXPROJ];
+  bool upd = false, ures = false;
+  int unp = 0, us = -1;
+  double pd0 = 0.0, uas = 0.0, ucf = 0.0;
+  if constexpr (AB) {
+    if (act && nd < MM) pd0 = d.PD[e * MM + nd];
+    if (tid < MAXPROJ) ucf = Gu->up_cf[tid];
+    upd = Gu->up_apply != 0; ures = Gu->up_restart != 0; unp = Gu->up_np; us = Gu->up_s; uas = Gu->up_as;
   }
   if (check_helm && blockIdx.x == 0) {       // last partials -> final residual of the velocity solve
     double s[8];
@@ -972,6 +1067,7 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_rhs(Dev d, StepCoef sc, int
     }
   }
   br.commit(nullptr, nullptr, sJ12, sD12, tid);
+  if constexpr (AB) { if (tid < MAXPROJ) scf[tid] = ucf; }
   __syncthreads();
   const double div = opdiv_tiles<N, EPB>(sJ12, sD12, su, sA, act, el, nd, d, e);
   double v[1] = {0.0};
@@ -988,6 +1084,18 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_rhs(Dev d, StepCoef sc, int
     double t[1] = {g};
     block_reduce<1>(t, sred, tid, NT);
     if (tid == 0) d.gpart[(size_t)d.nblk + blockIdx.x] = t[0];
+  }
+  if (upd) {                                   // k_proj_update's arithmetic in its k order, explicit fma (same bits); slot s and pxr[s] take the new vector
+    double x = pd0, xs = 0.0;
+#pragma unroll
+    for (int k = 0; k < PXPRE; ++k) {
+      if (k < unp && (ures || k != us)) x = fma(-scf[k], pxr[k], x);
+      if (k == us) xs = pxr[k];
+    }
+    if (!ures && us < unp) x = fma(uas, xs, x);
+#pragma unroll
+    for (int k = 0; k < PXPRE; ++k) if (k == us) pxr[k] = x;
+    if (pact) d.PX[(size_t)us * d.npr + e * MM + nd] = x;
   }
   if (d.nproj_max > 0) {                       // (x_i, g) for the stored solutions
     if (tid == 0) d.ppart[(size_t)MAXPROJ * d.nblk + blockIdx.x] = v[0];
@@ -1889,6 +1997,16 @@ __global__ __launch_bounds__(256) void k_proj_apply_e(Dev d) {
 #pragma unroll
   for (int k = 0; k < MAXPROJ; ++k) pe[k] = d.PEX[(size_t)(k < npre ? k : 0) * d.npr + q];      // (slots >= nproj: finite stale data, zero coefficient)
   const double pnv = (tid < MAXPROJ) ? G->pn[tid] : 1.0;
+  // deferred update of the projection space (Dev::absorb): the E-image half, as k_pres_rhs does the PX half -- from the
+  // snapshot GmresScal::up_* of this step's k_rhs (this launch rewrites pa, the snapshot is not touched)
+  // (loaded whether an update is pending or not: a load behind the flag would be one more trip to memory)
+  __shared__ double scf[MAXPROJ];
+  const double ped0 = d.absorb ? d.PED[q] : 0.0;
+  const double ucf = (d.absorb && tid < MAXPROJ) ? G->up_cf[tid] : 0.0;
+  const bool upd = d.absorb && G->up_apply;
+  const int unp = d.absorb ? G->up_np : 0, us = d.absorb ? G->up_s : -1;
+  const bool ures = d.absorb && G->up_restart != 0;
+  const double uas = d.absorb ? G->up_as : 0.0;
   const int ecs = d.ecslot[(act ? e : 0) * 4 + (nd & 3)];
   double hatv[(4 * MM + 255) / 256];
 #pragma unroll
@@ -1905,10 +2023,23 @@ __global__ __launch_bounds__(256) void k_proj_apply_e(Dev d) {
     if (tid == 0) G->gnorm0 = sqrt(gg[0]);
   }
   if (tid < np) sh[tid] = sh[tid] / pnv;
+  if (tid < MAXPROJ) scf[tid] = ucf;
 #pragma unroll
   for (int r = 0; r < (4 * MM + 255) / 256; ++r) if (tid + r * 256 < 4 * MM) shat[tid + r * 256] = hatv[r];
   __syncthreads();
   if (blockIdx.x == 0 && tid < np) G->pa[tid] = sh[tid];
+  if (upd) {                                   // (behind the sums: every load above was issued before this waits for pe[])
+    double ex = ped0, exs = 0.0;
+#pragma unroll
+    for (int k = 0; k < MAXPROJ; ++k) {
+      if (k < unp && (ures || k != us)) ex = fma(-scf[k], pe[k], ex);
+      if (k == us) exs = pe[k];
+    }
+    if (!ures && us < unp) ex = fma(uas, exs, ex);
+#pragma unroll
+    for (int k = 0; k < MAXPROJ; ++k) if (k == us) pe[k] = ex;
+    if (pact) d.PEX[(size_t)us * d.npr + q] = ex;
+  }
   double v[1] = {0.0};
   if (pact) {
     double g = g0;
@@ -2494,6 +2625,7 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_vel_update_proj(Dev d, StepCoef 
     su[(0 * EPB + el) * NN + nd] = vx;
     su[(1 * EPB + el) * NN + nd] = vy;
   }
+  if (d.absorb && bid == 0 && tid == 0) d.gsc->up_pending = (G->nit > 0) ? 1 : 0;      // the next k_rhs stages and commits it (proj_book)
   if (G->nit == 0) return;                      // nothing new to absorb
   br.commit(nullptr, nullptr, sJ12, sD12, tid);
   __syncthreads();
@@ -2575,6 +2707,7 @@ __global__ __launch_bounds__(256) void k_proj_update(Dev d) {
   PartialRows<5> pr;
   pr.issue(d.ppart, d.nblk, (!totals && d.nblk <= 512) ? nmax + 1 : 0, tid);
   if (nit == 0) return;
+  if (d.absorb && !G->up_pending) return;       // map-end flush of the deferred update: nothing was left behind (nothing in this launch writes the flag)
   const bool full = np >= nmax;
   const bool restart = full && d.proj_restart;
   const int s = restart ? 0 : (full ? pcnt % nmax : np);          // slot written

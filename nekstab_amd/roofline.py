@@ -21,13 +21,15 @@ def _zero_counts(zero_arrays, ndim):
 
 
 def per_step_bytes(*, nel, lx1, ndim=2, nvert=0, coarse_lda=0, patch_stride=0, nproj=0, helm_iters=0.0, pres_iters=0.0,
-                   pres_jsum=None, coarse_bytes=None, gs_lag=1, zero_arrays=0, fuse2=0, tc_cols=20):
+                   pres_jsum=None, coarse_bytes=None, gs_lag=1, zero_arrays=0, fuse2=0, tc_cols=20, proj_absorb=0):
     """Algorithmic bytes of ONE time step, by kernel family.  ``helm_iters`` / ``pres_iters``: mean iterations per step
     (all velocity components advance together in one CG iteration).  Hexahedra (``ndim = 3``): ``pres_jsum`` = mean per step of
     the sum over the GMRES columns of their basis index j (nsk_stats.total_pres_jsum / total_steps; the Gram-Schmidt bytes
     are proportional to it), ``coarse_bytes`` = nsk_stats.coarse_bytes_per_solve, ``gs_lag``: the lagged Gram-Schmidt
     sequence (two basis reads per column) or the classic one (four).  ``zero_arrays``: nsk_stats.zero_arrays -- arrays that vanish on
-    every node are not inputs of the kernels (Nek5000 skips them on its undeformed elements the same way) and are not counted."""
+    every node are not inputs of the kernels (Nek5000 skips them on its undeformed elements the same way) and are not counted.
+    ``proj_absorb``: the update of the projection space is applied by its next readers (option "proj_absorb", nsk_stats.absorb_maps
+    > 0): no pass over the space for the update -- delta, E delta in and the two new vectors out are what is left of it."""
     zm, zg, zb = _zero_counts(zero_arrays, ndim)
     d = ndim
     N, M, ND = lx1, lx1 - 2, 3 * lx1 // 2
@@ -91,7 +93,8 @@ def per_step_bytes(*, nel, lx1, ndim=2, nvert=0, coarse_lda=0, patch_stride=0, n
     # K10 pressure / velocity update + projection space
     out["K10 pres_update"] = f * (P2 * (pres_iters + nproj + 3 + nmet2) + P * d)
     out["K10 vel_update(+proj)"] = f * (P * (d + 1 + 2 * d + 2.0) + P2 * (nmet2 + 2 + 2 * nproj))
-    out["projection apply/update"] = f * P2 * (2 + nproj + 4 * nproj + 2) if nproj else 0.0
+    upd = 4 if proj_absorb else 4 * nproj + 2          # (absorbed: PD, PED in, the new x and E x out; the space itself is in the readers' registers)
+    out["projection apply/update"] = f * P2 * (2 + nproj + upd) if nproj else 0.0
     return out
 
 
@@ -119,5 +122,7 @@ def matvec_bytes(stats_total, nsteps, **geom):
     steps = max(stats_total["total_steps"], 1)
     if geom.get("ndim", 2) == 3:
         geom = dict(geom, pres_jsum=stats_total.get("total_pres_jsum", 0) / steps, coarse_bytes=stats_total.get("coarse_bytes_per_solve", 0.0))
+    if stats_total.get("absorb_maps", 0) > 0:
+        geom = dict(geom, proj_absorb=1)
     per = per_step_bytes(helm_iters=stats_total["total_helm_iters"] / steps, pres_iters=stats_total["total_pres_iters"] / steps, **geom)
     return nsteps * sum(per.values()), per
