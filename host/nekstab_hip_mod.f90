@@ -409,6 +409,36 @@ module nekstab_hip
       real(c_double), value :: spng_str
       type(c_ptr), dimension(*) :: endv
     end function
+    ! the Fourier form on shards: endv, amp, A, B are C arrays (c_loc of the first element, or c_null_ptr); A, B rank-major,
+    ! A(r * (nmodes + 1) + k), B(r * nmodes + k - 1) (zero-based) for rank r of the call
+    integer(c_int) function nsk_group_set_orbit_fourier(shards, n, q0, spng_str, nmodes, endv, amp) bind(c, name='nsk_group_set_orbit_fourier')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: q0
+      real(c_double), value :: spng_str
+      integer(c_int), value :: nmodes
+      type(c_ptr), value :: endv
+      type(c_ptr), value :: amp
+    end function
+    integer(c_int) function nsk_group_set_orbit_modes(shards, n, nmodes, period, A, B) bind(c, name='nsk_group_set_orbit_modes')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      integer(c_int), value :: nmodes
+      real(c_double), value :: period
+      type(c_ptr), value :: A
+      type(c_ptr), value :: B
+    end function
+    integer(c_int) function nsk_group_get_orbit_modes(shards, n, nmodes, period, A, B) bind(c, name='nsk_group_get_orbit_modes')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      integer(c_int) :: nmodes
+      real(c_double) :: period
+      type(c_ptr), value :: A
+      type(c_ptr), value :: B
+    end function
     integer(c_int) function nsk_shard_release_parent(parent) bind(c, name='nsk_shard_release_parent')
       import
       type(c_ptr), value :: parent

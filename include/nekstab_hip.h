@@ -173,8 +173,9 @@ int nsk_set_orbit(nsk_ctx* ctx, nsk_vec q0, double spng_str, nsk_vec end);
  * Device memory: stored orbit nsteps * (quadrilaterals 6 * nel * lxd^2, hexahedra 12 * nel * lxd^3) doubles;
  * Fourier orbit (2 M + 1) * ndim * nel * lx1^ndim doubles whatever the number of steps (+ nsteps * 2 M cos / sin factors).
  * The linearised maps rebuild the base-flow constants of the running step from the modes; a map may then be longer than one
- * period (nsk_set_nsteps), use another dt, or start at another phase (option "orbit_phase").  Full-mesh contexts only: shards,
- * rank-local contexts and lanes return NSK_EINVAL.  nsk_set_baseflow / nsk_set_orbit end the Fourier form; nsk_clone refuses it.
+ * period (nsk_set_nsteps), use another dt, or start at another phase (option "orbit_phase").  These three entries take full-mesh
+ * contexts: shards (use nsk_group_set_orbit_fourier / _set_orbit_modes / _get_orbit_modes below), rank-local contexts and lanes
+ * return NSK_EINVAL.  nsk_set_baseflow / nsk_set_orbit end the Fourier form; nsk_clone refuses it.
  *
  * nsk_set_orbit_fourier (fourier_decomposition, core/fourier.f:23-88): the integration of nsk_set_orbit (same dt / nsteps,
  * sponge and `end`, bit for bit), keeping the lowest `nmodes` harmonics, 0 <= nmodes <= nsteps / 2 (0: the time average);
@@ -319,6 +320,23 @@ int nsk_group_matvec(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec* q);
 int nsk_group_nonlinear_map(nsk_ctx** shards, int n, nsk_vec* f, nsk_vec* q, int subtract_q);
 int nsk_group_set_baseflow(nsk_ctx** shards, int n, nsk_vec* q);
 int nsk_group_set_orbit(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, nsk_vec* end);
+/* The Fourier form of the orbit on shards (nsk_set_orbit_fourier / nsk_set_orbit_modes / nsk_get_orbit_modes for the ranks of
+ * this process; n = 1 with a transport attached: one process per GPU).  Every rank keeps the modes of its OWN elements,
+ * (2 M + 1) * ndim * nloc_of_the_shard doubles, and its own cos / sin table; the sharded step rebuilds the base-flow constants of
+ * the running step per rank.  Shards of full-mesh and of rank-local parents alike.
+ *   nsk_group_set_orbit_fourier: the integration of nsk_group_set_orbit (bit for bit: the modes are summed from the stepper's
+ *     field, which is only read), 0 <= nmodes <= nsteps / 2 checked once nsteps is known.  `amp` (NULL or 2 nmodes + 1 doubles):
+ *     the bm1-weighted L2 norms of A_0, A_1, B_1, .. over ALL ranks, reduced on the device per rank and summed over the ranks
+ *     (rank order for virtual ranks, the transport's all-reduce otherwise); every rank receives the same values.
+ *   nsk_group_set_orbit_modes / nsk_group_get_orbit_modes: the mode vectors are RANK-MAJOR,
+ *       A[r * (nmodes + 1) + k], k = 0 .. nmodes    and    B[r * nmodes + k - 1], k = 1 .. nmodes
+ *     for rank r = 0 .. n-1 of this call, each a vector of shard r.  dt / nsteps: nsk_group_set_baseflow applied to
+ *     U(0) = sum_k A_k (CFL maximum over all ranks); `period` need not equal endtime.  get: A = B = NULL for count and period only;
+ *     NSK_EINVAL ("no Fourier orbit is active") when none is.
+ * nsk_group_set_baseflow / nsk_group_set_orbit end the Fourier form; the two setters here end a stored orbit. */
+int nsk_group_set_orbit_fourier(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, int nmodes, nsk_vec* end, double* amp);
+int nsk_group_set_orbit_modes(nsk_ctx** shards, int n, int nmodes, double period, const nsk_vec* A, const nsk_vec* B);
+int nsk_group_get_orbit_modes(nsk_ctx** shards, int n, int* nmodes, double* period, nsk_vec* A, nsk_vec* B);
 /* Once a process has cut its shard(s): free every device array of the parent that shards do not share (element-major geometry,
  * preconditioner factors, state, work arrays and ALL vectors allocated on the parent -- their handles become invalid).  The 1-D
  * bases and the replicated coarse operator stay.  The parent then only answers nsk_info / nsk_get_stats / nsk_finalize

@@ -100,6 +100,9 @@ SYMBOLS = {
     "nsk_group_nonlinear_map": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, C.c_int]),
     "nsk_group_set_baseflow": (C.c_int, [_vpp, C.c_int, _vpp]),
     "nsk_group_set_orbit": (C.c_int, [_vpp, C.c_int, _vpp, C.c_double, _vpp]),
+    "nsk_group_set_orbit_fourier": (C.c_int, [_vpp, C.c_int, _vpp, C.c_double, C.c_int, _vpp, _dp]),
+    "nsk_group_set_orbit_modes": (C.c_int, [_vpp, C.c_int, C.c_int, C.c_double, _vpp, _vpp]),
+    "nsk_group_get_orbit_modes": (C.c_int, [_vpp, C.c_int, _ip, _dp, _vpp, _vpp]),
     "nsk_comm_init_host": (C.c_int, [_vp, _vp, _vp, _vp]),
     "nsk_shard_release_parent": (C.c_int, [_vp]),
     "nsk_comm_unique_id": (C.c_int, [_vp]),

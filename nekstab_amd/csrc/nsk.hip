@@ -1618,9 +1618,10 @@ static bool step_budgets_ready(const nsk_ctx* c, int kind) {
 
 // Fourier orbit: row i of the table holds cos / sin (2 pi frac(k s_i)), k = 1..M, s_i = phase + i dt / T -- the base flow of
 // time step i + 1 of a direct or adjoint map (the slot rule of the stored orbit).  Any nsteps, any dt.
-static int forb_trig_ensure(nsk_ctx* c) {
+static int forb_trig_ensure(nsk_ctx* c, bool* rebuilt = nullptr) {
   Dev& d = c->d;
   const int M = d.forb_M, n = c->nsteps;
+  if (rebuilt) *rebuilt = false;
   if (c->trig_n == n && c->trig_M == M && c->trig_dt == c->dt && c->trig_T == c->forb_T && c->trig_phase == c->forb_phase) return 0;
   const size_t need = (size_t)n * (size_t)std::max(2 * M, 1);
   HIPCHK(hipStreamSynchronize(c->stream));                    // (no queued step may still read the old table)
@@ -1644,6 +1645,7 @@ static int forb_trig_ensure(nsk_ctx* c) {
   d.ftrig = c->forb_trig; d.forb_rows = n;
   c->trig_n = n; c->trig_M = M; c->trig_dt = c->dt; c->trig_T = c->forb_T; c->trig_phase = c->forb_phase;
   invalidate_graphs(c);           // the table's address and row count are baked into the captured steps
+  if (rebuilt) *rebuilt = true;
   return 0;
 }
 
@@ -2064,6 +2066,7 @@ static int group_set_baseflow(std::vector<nsk_ctx*>& G, const double* const* q) 
     if (!P) return fail(NSK_EINVAL, "needs shard contexts");
     const int nd = c->ndim, NN = c->NN;
     d.bfmask = 0;                                          // (the new constants are not scanned for zero arrays on shards)
+    d.forb = 0;                                            // a Fourier orbit ends here (nsk_group_set_orbit comes through here too)
     DISPATCH_N(c->key, {                                   // (hexahedra: Dev::cUr aliases the 12-constant array bfc)
       hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, q[r], (double*)d.cUr, (double*)d.cUs,
                          (double*)d.GUx, (double*)d.GUy, (double*)d.GVx, (double*)d.GVy);
@@ -2801,11 +2804,27 @@ int nsk_set_baseflow(nsk_ctx* c, nsk_vec qv) {
 // [2M+1][ndim][nloc] (A_0, A_1, B_1, ..) whatever the number of steps; k_baseflow_fourier rebuilds the base-flow constants of
 // the running step from them (step()).
 static int forb_refuse(const nsk_ctx* c, const char* who) {
-  if (c->parent || c->nranks > 1) return fail(NSK_EINVAL, std::string(who) + ": not on a shard (Fourier orbits: full-mesh contexts only)");
-  if (c->local) return fail(NSK_EINVAL, std::string(who) + ": not on a rank-local context (Fourier orbits: full-mesh contexts only)");
+  if (c->parent || c->nranks > 1) return fail(NSK_EINVAL, std::string(who) + ": not on a shard: use nsk_group_set_orbit_fourier / nsk_group_set_orbit_modes");
+  if (c->local) return fail(NSK_EINVAL, std::string(who) + ": not on a rank-local context (cut its shard and use nsk_group_set_orbit_fourier / nsk_group_set_orbit_modes)");
   if (c->clone_of) return fail(NSK_EINVAL, std::string(who) + ": not on a lane (nsk_clone)");
   if (c->released) return fail(NSK_EINVAL, std::string(who) + ": context was released (nsk_shard_release_parent)");
   return 0;
+}
+// the coefficient rows of k_orbit_dft, [Nn][2 M + 1]: c_k / N cos, sin (2 pi k n / N), c_k = 2 except c_0 = c_{N/2} = 1
+static std::vector<double> forb_dft_rows(int Nn, int nmodes) {
+  const int nm = 2 * nmodes + 1;
+  std::vector<double> w((size_t)Nn * nm);
+  const double twopi = 8.0 * std::atan(1.0);
+  for (int n = 0; n < Nn; ++n) {
+    w[(size_t)n * nm] = 1.0 / Nn;
+    for (int k = 1; k <= nmodes; ++k) {
+      const bool nyq = 2 * k == Nn;
+      const double ang = twopi * (double)(((long long)k * n) % Nn) / (double)Nn, ck = (nyq ? 1.0 : 2.0) / Nn;
+      w[(size_t)n * nm + 2 * k - 1] = ck * std::cos(ang);
+      w[(size_t)n * nm + 2 * k] = nyq ? 0.0 : ck * std::sin(ang);
+    }
+  }
+  return w;
 }
 // room for the modes, zeroed (on the stream)
 static int forb_alloc(nsk_ctx* c, int M) {
@@ -2864,18 +2883,7 @@ static int set_orbit_impl(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end,
     c->orbit_steps = 0;
     int rc = forb_alloc(c, nmodes);
     if (rc) return rc;
-    const int Nn = c->nsteps;
-    std::vector<double> w((size_t)Nn * nm);
-    const double twopi = 8.0 * std::atan(1.0);
-    for (int n = 0; n < Nn; ++n) {
-      w[(size_t)n * nm] = 1.0 / Nn;
-      for (int k = 1; k <= nmodes; ++k) {
-        const bool nyq = 2 * k == Nn;
-        const double ang = twopi * (double)(((long long)k * n) % Nn) / (double)Nn, ck = (nyq ? 1.0 : 2.0) / Nn;
-        w[(size_t)n * nm + 2 * k - 1] = ck * std::cos(ang);
-        w[(size_t)n * nm + 2 * k] = nyq ? 0.0 : ck * std::sin(ang);
-      }
-    }
+    const std::vector<double> w = forb_dft_rows(c->nsteps, nmodes);
     if ((rc = dalloc(c, &dftw, w.size()))) return rc;
     HIPCHK(hipMemcpy(dftw, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
     return 0;
@@ -3036,8 +3044,7 @@ int nsk_set_orbit_modes(nsk_ctx* c, int nmodes, double period, const nsk_vec* A,
 }
 
 // The modes of the active Fourier orbit into state vectors (velocity components; the rest is zeroed).  A, B NULL: count and period only.
-int nsk_get_orbit_modes(nsk_ctx* c, int* nmodes, double* period, nsk_vec* A, nsk_vec* B) {
-  if (!c) return fail(NSK_EINVAL, "bad argument");
+static int get_orbit_modes(nsk_ctx* c, int* nmodes, double* period, nsk_vec* A, nsk_vec* B) {
   if (!c->d.forb) return fail(NSK_EINVAL, "nsk_get_orbit_modes: no Fourier orbit is active");
   const int M = c->d.forb_M;
   if (nmodes) *nmodes = M;
@@ -3055,6 +3062,163 @@ int nsk_get_orbit_modes(nsk_ctx* c, int* nmodes, double* period, nsk_vec* A, nsk
     }
   }
   HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+int nsk_get_orbit_modes(nsk_ctx* c, int* nmodes, double* period, nsk_vec* A, nsk_vec* B) {
+  if (!c) return fail(NSK_EINVAL, "bad argument");
+  if (c->parent) return fail(NSK_EINVAL, "nsk_get_orbit_modes: not on a shard: use nsk_group_get_orbit_modes");
+  return get_orbit_modes(c, nmodes, period, A, B);
+}
+
+// ---- the Fourier form on element shards: every rank keeps the modes of its own elements, [2M+1][ndim][nloc of the shard], and
+// its own table of cos / sin factors (group_run_map); group_step reconstructs per rank in front of the convection kernel.
+static void shard_steady_back(nsk_ctx* c) {                     // a stored orbit ends: back to the steady arrays
+  Dev& d = c->d;
+  if (!d.bf_stride) return;
+  if (c->ndim == 3) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; }
+  else { d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5]; }
+  d.bf_stride = 0;
+  invalidate_graphs(c);
+}
+// amp[0 .. 2M] = bm1s-weighted L2 norms of A_0, A_1, B_1, .. over ALL ranks: per rank one pass of k_mode_norm2 over its mode
+// arrays and the fixed-order row totals, then the squares are added over the ranks (virtual ranks: on the host in rank order;
+// a transport: nsk_allreduce_host) -- every rank gets the same values, no mode leaves the device
+static int group_mode_amp(std::vector<nsk_ctx*>& G, int M, double* amp) {
+  const int nm = 2 * M + 1;
+  nsk_ctx* c0 = G[0];
+  std::vector<double> loc(1024);
+  for (int o = 0; o < nm; o += 1024) {
+    const int m = std::min(1024, nm - o);
+    std::vector<double> sum(m, 0.0);
+    for (nsk_ctx* c : G) {
+      const size_t nv = (size_t)c->ndim * (size_t)c->nloc;
+      hipLaunchKernelGGL(k_mode_norm2, dim3(c->kblk, m), dim3(256), 0, c->stream, (const double*)(c->forb_modes + (size_t)o * nv), c->d.bm1s, c->nloc, c->ndim, c->kpart, c->kblk);
+      hipLaunchKernelGGL(k_tot2, dim3(m), dim3(256), 0, c->stream, (const double*)c->kpart, c->kblk, c->kout, (const int*)nullptr);
+      HIPCHK(hipMemcpyAsync(loc.data(), c->kout, m * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      for (int k = 0; k < m; ++k) sum[k] += loc[k];
+    }
+    if (G.size() == 1 && (c0->comm || c0->host_allred)) { int rc = nsk_allreduce_host(c0, sum.data(), m); if (rc) return rc; }
+    for (int k = 0; k < m; ++k) amp[o + k] = std::sqrt(sum[k]);
+  }
+  return 0;
+}
+
+// nsk_set_orbit_fourier for the ranks of this process: the integration of nsk_group_set_orbit, every rank adding its own
+// elements' field into its own mode arrays in front of every step (k_orbit_dft reads the stepper's field with its stride cs:
+// no scratch copy, no snapshot, no per-step constants).
+int nsk_group_set_orbit_fourier(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, int nmodes, nsk_vec* end, double* amp) {
+  if (!shards || n < 1 || !q0) return fail(NSK_EINVAL, "bad argument");
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  for (int r = 0; r < n; ++r)
+    if (!G[r] || !q0[r] || !G[r]->parent) return fail(NSK_EINVAL, "needs shard contexts");
+  if (nmodes < 0) return fail(NSK_EINVAL, "nsk_group_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2");
+  const int nd = G[0]->ndim, nm = 2 * nmodes + 1;
+  int rc;
+  for (nsk_ctx* c : G) shard_steady_back(c);
+  if ((rc = group_set_baseflow(G, (const double* const*)q0))) return rc;          // dt, nsteps: CFL maximum over all ranks
+  const int nsteps = G[0]->nsteps;
+  if (nmodes > nsteps / 2) return fail(NSK_EINVAL, "nsk_group_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2 (" + std::to_string(nsteps / 2) + ")");
+  const std::vector<double> w = forb_dft_rows(nsteps, nmodes);
+  std::vector<double*> dftw(G.size(), nullptr);                 // per rank: [nsteps][nm] coefficient rows of k_orbit_dft
+  auto four_end = [&]() {
+    for (size_t r = 0; r < G.size(); ++r) if (dftw[r]) { nsk_vec v = dftw[r]; nsk_vec_free(G[r], 1, &v); dftw[r] = nullptr; }
+  };
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r]; Dev& d = c->d;
+    for (int k = 0; k < 6; ++k) if (c->orbit[k]) { nsk_vec v = c->orbit[k]; nsk_vec_free(c, 1, &v); c->orbit[k] = nullptr; }
+    c->orbit_steps = 0;
+    if ((rc = forb_alloc(c, nmodes)) || (rc = dalloc(c, &dftw[r], w.size()))) { four_end(); return rc; }
+    HIPCHK(hipMemcpy(dftw[r], w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    double* vr = const_cast<double*>(d.spng_vr);
+    if (!vr && (rc = dalloc(c, &vr, nd * d.cs))) { four_end(); return rc; }
+    const double* q = (const double*)q0[r];
+    for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(vr + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    d.spng_vr = vr; d.nl_spng_str = spng_str;
+    if (!d.bstep && (rc = dalloc(c, &d.bstep, 4))) { four_end(); return rc; }
+    HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
+    for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d.p, q + nd * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  }
+  for (int istep = 1; istep <= nsteps; ++istep) {
+    for (size_t r = 0; r < G.size(); ++r) {
+      nsk_ctx* c = G[r]; Dev& d = c->d;
+      const long long nv = (long long)nd * d.nloc;
+      hipLaunchKernelGGL(k_orbit_dft, dim3((unsigned)std::min<long long>((nv + 255) / 256, 4096)), dim3(256), 0, c->stream, c->forb_modes, (const double*)d.u,
+                         (const double*)(dftw[r] + (size_t)(istep - 1) * nm), nm, d.nloc, d.cs, nd);
+    }
+    if ((rc = group_step(G, istep, 2))) { four_end(); return rc; }
+  }
+  Stats h;
+  HIPCHK(hipMemcpyAsync(&h, G[0]->d.stats, sizeof(Stats), hipMemcpyDeviceToHost, G[0]->stream));
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r]; Dev& d = c->d;
+    if (end && end[r]) {
+      double* f = (double*)end[r];
+      for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(f + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(hipMemcpyAsync(f + nd * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+  }
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  four_end();
+  if (h.unconverged > 0) return fail(NSK_ENOCONV, "inner solve hit its iteration cap while integrating the base-flow orbit (sharded)");
+  for (nsk_ctx* c : G) if ((rc = forb_activate(c, nmodes, c->endtime, nullptr))) return rc;
+  return amp ? group_mode_amp(G, nmodes, amp) : 0;
+}
+
+// nsk_set_orbit_modes for the ranks of this process; A, B rank-major: A[r * (nmodes + 1) + k], B[r * nmodes + k - 1]
+int nsk_group_set_orbit_modes(nsk_ctx** shards, int n, int nmodes, double period, const nsk_vec* A, const nsk_vec* B) {
+  if (!shards || n < 1 || !A || nmodes < 0 || (nmodes > 0 && !B)) return fail(NSK_EINVAL, "bad argument");
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  for (int r = 0; r < n; ++r) if (!G[r] || !G[r]->parent) return fail(NSK_EINVAL, "needs shard contexts");
+  if (!(period > 0.0)) return fail(NSK_EINVAL, "nsk_group_set_orbit_modes: period must be positive");
+  for (int r = 0; r < n; ++r)
+    for (int k = 0; k <= nmodes; ++k)
+      if (!A[(size_t)r * (nmodes + 1) + k] || (k < nmodes && !B[(size_t)r * nmodes + k])) return fail(NSK_EINVAL, "nsk_group_set_orbit_modes: null mode vector");
+  // the modes first (A or B may be the vectors nsk_group_get_orbit_modes filled from the arrays replaced here: staged through new arrays)
+  std::vector<double*> fresh(G.size(), nullptr);
+  auto drop = [&]() { for (size_t r = 0; r < G.size(); ++r) if (fresh[r]) { nsk_vec v = fresh[r]; nsk_vec_free(G[r], 1, &v); fresh[r] = nullptr; } };
+  std::vector<const double*> u0(G.size());
+  int rc;
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r];
+    const long long nv = (long long)c->ndim * c->nloc;
+    const nsk_vec* Ar = A + r * (nmodes + 1);
+    const nsk_vec* Br = nmodes ? B + r * nmodes : nullptr;
+    if ((rc = dalloc(c, &fresh[r], (size_t)(2 * nmodes + 1) * nv))) { drop(); return rc; }
+    for (int k = 0; k <= nmodes; ++k) {
+      HIPCHK(hipMemcpyAsync(fresh[r] + (size_t)(k ? 2 * k - 1 : 0) * nv, Ar[k], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      if (k) HIPCHK(hipMemcpyAsync(fresh[r] + (size_t)(2 * k) * nv, Br[k - 1], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(hipMemsetAsync(c->scratch, 0, c->nstate * sizeof(double), c->stream));
+    for (int k = 0; k <= nmodes; ++k)                           // U(0) = sum_k A_k
+      hipLaunchKernelGGL(k_axpby, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, c->scratch, 1.0, (const double*)Ar[k], 1.0, nv);
+    u0[r] = c->scratch;
+  }
+  for (nsk_ctx* c : G) shard_steady_back(c);
+  if ((rc = group_set_baseflow(G, u0.data()))) { drop(); return rc; }             // dt, nsteps: CFL maximum over all ranks
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r];
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->forb_modes) { nsk_vec v = c->forb_modes; nsk_vec_free(c, 1, &v); }
+    c->forb_modes = fresh[r]; c->forb_modes_cap = (size_t)(2 * nmodes + 1) * (size_t)c->ndim * (size_t)c->nloc;
+    fresh[r] = nullptr;
+    if ((rc = forb_activate(c, nmodes, period, nullptr))) { drop(); return rc; }
+  }
+  return 0;
+}
+
+// nsk_get_orbit_modes per rank; A, B rank-major as above, or both NULL: count and period only
+int nsk_group_get_orbit_modes(nsk_ctx** shards, int n, int* nmodes, double* period, nsk_vec* A, nsk_vec* B) {
+  if (!shards || n < 1) return fail(NSK_EINVAL, "bad argument");
+  for (int r = 0; r < n; ++r) if (!shards[r] || !shards[r]->parent) return fail(NSK_EINVAL, "needs shard contexts");
+  for (int r = 0; r < n; ++r) if (!shards[r]->d.forb) return fail(NSK_EINVAL, "nsk_group_get_orbit_modes: no Fourier orbit is active");
+  const int M = shards[0]->d.forb_M;
+  for (int r = 0; r < n; ++r) {
+    if (shards[r]->d.forb_M != M) return fail(NSK_EINVAL, "nsk_group_get_orbit_modes: the ranks hold different numbers of modes");
+    const int rc = get_orbit_modes(shards[r], nmodes, period, A ? A + (size_t)r * (M + 1) : nullptr, B ? B + (size_t)r * M : nullptr);
+    if (rc) return rc;
+  }
   return 0;
 }
 

@@ -2848,6 +2848,24 @@ __global__ __launch_bounds__(256) void k_orbit_dft(double* __restrict__ fm, cons
   }
 }
 
+// Amplitudes of the temporal modes on element shards (amp_real / amp_img, core/fourier.f:46-53): one pass over the mode arrays
+// fm[m][ndim][nloc] of one rank, workgroup (x, m) adds w_l |mode m at node l|^2 over its share of the nodes into part[m][x]
+// (nblk = gridDim.x partials per mode; k_tot2 adds each row in fixed order, the caller sums over the ranks).
+__global__ __launch_bounds__(256) void k_mode_norm2(const double* __restrict__ fm, const double* __restrict__ w, long long nloc, int ndim,
+                                                    double* __restrict__ part, int nblk) {
+  __shared__ double sred[16];
+  const int tid = threadIdx.x, m = blockIdx.y;
+  const double* __restrict__ a = fm + (size_t)m * (size_t)ndim * (size_t)nloc;
+  double v[1] = {0.0};
+  for (long long l = (long long)blockIdx.x * 256 + tid; l < nloc; l += (long long)nblk * 256) {
+    double t = a[l] * a[l] + a[nloc + l] * a[nloc + l];
+    if (ndim == 3) t += a[2 * nloc + l] * a[2 * nloc + l];
+    v[0] += w[l] * t;
+  }
+  block_reduce<1>(v, sred, tid, 256);
+  if (tid == 0) part[(size_t)m * nblk + blockIdx.x] = v[0];
+}
+
 // scale by 1/sqrt(*nrm2) read from device memory (krylov_normalize without a host round trip)
 __global__ void k_scale_rsqrt(double* __restrict__ y, const double* __restrict__ nrm2, long long n) {
   const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;

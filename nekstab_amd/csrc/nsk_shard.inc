@@ -583,6 +583,9 @@ static int group_step(std::vector<nsk_ctx*>& G, int istep, int adjoint) {
   DISPATCH_N(c0->key, {
     constexpr int NT = Cfg<N>::NT;
     FORALL {
+      if (c->d.forb && adjoint != 2)  // Fourier orbit: the base flow of this step into the rank's steady slot (hexahedra: cUr is the 12-constant array)
+        hipLaunchKernelGGL(k_baseflow_fourier<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, c->d, (double*)c->d.cUr, (double*)c->d.cUs,
+                           (double*)c->d.GUx, (double*)c->d.GUy, (double*)c->d.GVx, (double*)c->d.GVy);
       if (c->key == 108 && adjoint != 2 && c->mfma_convect)
         hipLaunchKernelGGL(nsk::k3::k_convect_mfma8, dim3(c->nel), dim3(512), 0, c->stream, c->d, (const double*)c->d.u, c->d.bf, adjoint);
       else if (c->key == 110 && adjoint != 2 && c->mfma_convect)
@@ -773,6 +776,16 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
   const bool graph = group_graph_ok(G);
   if (graph)
     for (nsk_ctx* c : G) if (c->stream != G[0]->stream) return fail(NSK_EINVAL, "ranks of one process must share a stream");
+  // Fourier orbit: every rank owns its table of cos / sin factors (its own orbit_phase); before any capture, and a rebuilt
+  // table (address, row count) makes the group's graphs stale -- the members' kernels live in the graphs G[0] holds
+  if (adjoint != 2)
+    for (nsk_ctx* c : G)
+      if (c->d.forb) {
+        bool rebuilt = false;
+        int rc = forb_trig_ensure(c, &rebuilt);
+        if (rc) return rc;
+        if (rebuilt) invalidate_graphs(G[0]);
+      }
   for (;;) {
     if (graph)
       for (int k = 0; k < NCLS; ++k) { int rc = group_ensure_graph(G, k, adjoint); if (rc) return rc; }
@@ -783,8 +796,8 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
       for (int cc = 0; cc < c->ndim; ++cc)
         HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q[r] + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
       HIPCHK(hipMemcpyAsync(d.p, q[r] + c->ndim * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      if (d.bf_stride) {                                     // time-periodic base flow: step counter of the stored orbit
-        if (adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
+      if (d.bf_stride || d.forb) {                           // time-periodic base flow: step counter of the stored orbit / row of the trig table
+        if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
         HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
       }
     }

@@ -9,7 +9,8 @@ The device keeps an orbit as ``A_0, A_1, B_1, .., A_M, B_M`` (``nsk_set_orbit_fo
 ``np_dft_modes`` / ``np_reconstruct`` restate that convention in numpy: they are the yardstick of the device kernels
 (k_orbit_dft, k_baseflow_fourier).  ``write_modes`` / ``read_modes`` move the modes of a context to and from the
 reference's ``fRe`` / ``fIm`` field files (fourier_decomposition, core/fourier.f:67-85), ``amplitude_report`` is its 99 %
-criterion for choosing M (:63-68).
+criterion for choosing M (:63-68).  The context may be a ``NekStabHip`` or a ``sharded.ShardGroup`` (whole-mesh fields on the
+host, every rank keeps its own elements' part).
 """
 from __future__ import annotations
 

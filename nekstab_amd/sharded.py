@@ -202,7 +202,7 @@ class ShardGroup:
         self.part = np.ascontiguousarray(partition_rcb(case, nranks) if part is None else part, dtype=np.int32)
         self.nsteps, self.dt = full.nsteps, full.dt
         ndim = int(getattr(case, "ndim", 2))
-        self.nel, self.lx1, self.lx2 = case.nel, full.lx1, full.lx2
+        self.ndim, self.nel, self.lx1, self.lx2 = ndim, case.nel, full.lx1, full.lx2
         self.npres, self.nvel = case.nel * self.lx2 ** ndim, case.nel * self.lx1 ** ndim
         self.elems = [np.where(self.part == r)[0] for r in range(nranks)]
         self.ctx = []
@@ -326,6 +326,41 @@ class ShardGroup:
         ea = (C.c_void_p * self.R)(*[p.value for p in end.parts]) if end is not None else None
         self._chk(self.lib.nsk_group_set_orbit(self._arr, self.R, qa, float(spng_str), ea))
         self._refresh_info()
+
+    # ---- the orbit as temporal Fourier modes, every rank keeping its own elements' (nsk_group_set_orbit_fourier, ..)
+    def set_orbit_fourier(self, q0, nmodes, spng_str=0.0, end=None):
+        """The integration of ``set_orbit``, keeping the lowest ``nmodes`` harmonics per shard.  Returns the 2 nmodes + 1
+        bm1-weighted L2 norms of A_0, A_1, B_1, .. over all ranks."""
+        amp = np.zeros(2 * max(int(nmodes), 0) + 1)
+        qa = (C.c_void_p * self.R)(*[p.value for p in q0.parts])
+        ea = (C.c_void_p * self.R)(*[p.value for p in end.parts]) if end is not None else None
+        self._chk(self.lib.nsk_group_set_orbit_fourier(self._arr, self.R, qa, float(spng_str), int(nmodes), ea, amp.ctypes.data_as(_dp)))
+        self._refresh_info()
+        return amp
+
+    def _rank_major(self, vecs):
+        return (C.c_void_p * max(self.R * len(vecs), 1))(*[v.parts[r].value for r in range(self.R) for v in vecs])
+
+    def set_orbit_modes(self, A, B, period):
+        """Fourier orbit from mode vectors A = [A_0 .. A_M], B = [B_1 .. B_M] (sharded state vectors)."""
+        M = len(B)
+        if len(A) != M + 1:
+            raise ValueError("set_orbit_modes: A needs len(B) + 1 vectors")
+        self._chk(self.lib.nsk_group_set_orbit_modes(self._arr, self.R, M, float(period), self._rank_major(A), self._rank_major(B) if M else None))
+        self._refresh_info()
+
+    def get_orbit_modes(self, A=None, B=None):
+        """(nmodes, period) of the active Fourier orbit; with A (nmodes + 1 vectors) and B (nmodes) the modes are copied out."""
+        m, per = C.c_int(), C.c_double()
+        if A is not None:
+            self._chk(self.lib.nsk_group_get_orbit_modes(self._arr, self.R, C.byref(m), C.byref(per), None, None))
+            if len(A) != m.value + 1 or len(B or []) != m.value:
+                raise ValueError("get_orbit_modes: needs %d + %d vectors" % (m.value + 1, m.value))
+        aa = self._rank_major(A) if A is not None else None
+        bb = self._rank_major(B) if B is not None else None
+        self._chk(self.lib.nsk_group_get_orbit_modes(self._arr, self.R, C.byref(m), C.byref(per), aa, bb))
+        self._refresh_info()
+        return m.value, per.value
 
     def stats(self):
         from .capi import NskStats
@@ -514,6 +549,36 @@ class ShardRank:
         ea = (C.c_void_p * 1)(end.value) if end is not None else None
         self._chk(self.lib.nsk_group_set_orbit(self._one, 1, qa, float(spng_str), ea))
         self._refresh_info()
+
+    # ---- the orbit as temporal Fourier modes of this rank's elements; the amplitudes are summed over the communicator
+    def set_orbit_fourier(self, q0, nmodes, spng_str=0.0, end=None):
+        amp = np.zeros(2 * max(int(nmodes), 0) + 1)
+        qa = (C.c_void_p * 1)(q0.value)
+        ea = (C.c_void_p * 1)(end.value) if end is not None else None
+        self._chk(self.lib.nsk_group_set_orbit_fourier(self._one, 1, qa, float(spng_str), int(nmodes), ea, amp.ctypes.data_as(_dp)))
+        self._refresh_info()
+        return amp
+
+    def set_orbit_modes(self, A, B, period):
+        M = len(B)
+        if len(A) != M + 1:
+            raise ValueError("set_orbit_modes: A needs len(B) + 1 vectors")
+        aa = (C.c_void_p * (M + 1))(*[v.value for v in A])
+        bb = (C.c_void_p * max(M, 1))(*[v.value for v in B])
+        self._chk(self.lib.nsk_group_set_orbit_modes(self._one, 1, M, float(period), aa, bb if M else None))
+        self._refresh_info()
+
+    def get_orbit_modes(self, A=None, B=None):
+        m, per = C.c_int(), C.c_double()
+        if A is not None:
+            self._chk(self.lib.nsk_group_get_orbit_modes(self._one, 1, C.byref(m), C.byref(per), None, None))
+            if len(A) != m.value + 1 or len(B or []) != m.value:
+                raise ValueError("get_orbit_modes: needs %d + %d vectors" % (m.value + 1, m.value))
+        aa = (C.c_void_p * len(A))(*[v.value for v in A]) if A is not None else None
+        bb = (C.c_void_p * max(len(B), 1))(*[v.value for v in B]) if B is not None else None
+        self._chk(self.lib.nsk_group_get_orbit_modes(self._one, 1, C.byref(m), C.byref(per), aa, bb))
+        self._refresh_info()
+        return m.value, per.value
 
     def stats(self):
         from .capi import NskStats
