@@ -288,6 +288,9 @@ typedef struct {
   long long absorb_maps;                    /* maps since init whose time steps ran without a k_proj_update launch: the update of the pressure projection
                                                space applied by its next readers (option "proj_absorb"; one flush launch per map).  0 wherever the option
                                                does not apply: hexahedra, shards, host-checked meshes, fuse2 = 0, nproj = 0 */
+  long long convfuse_steps;                 /* time steps since init that ran convection and the velocity right-hand side in ONE launch (k_convect_rhs, option
+                                               "conv_fuse") instead of k_convect + k_rhs (a redone map counts again).  0 wherever the option does not apply:
+                                               hexahedra, shards, forced maps, the persistent velocity solve */
 } nsk_stats;
 int nsk_get_stats(nsk_ctx* ctx, nsk_stats* s);
 

@@ -143,6 +143,7 @@ struct nsk_ctx {
   int tail_off_h = 0, tail_off_p = 0;    // heads = median + these (options "tail_off_h" / "tail_off_p": tests push work into the tails with negative values)
   long long tail_maps = 0;
   long long absorb_maps = 0;             // maps run with the deferred update of the projection space (option "proj_absorb")
+  long long convfuse_steps = 0;          // time steps run with convection and the velocity right-hand side in one launch (option "conv_fuse")
   long long sb_maps = 0, sb_steps = 0, sb_launch_h = 0, sb_launch_p = 0;     // maps / time steps run on per-step budgets and their budgeted launches (diagnostics)
   bool last_map_per_step = false;        // the map just run took the per-step budgets
   std::map<std::array<int, 4>, hipGraphExec_t> gcache;         // (adjoint, class, nh, np) -> captured step
@@ -153,6 +154,7 @@ struct nsk_ctx {
   int skip_close = 1;                   // no closing launch behind a pressure tail that covers the merged range (option "skip_close", NSK_SKIP_CLOSE; measured +0.3 %)
   int sb_pct = 90;                      // per-step budgets behind the safety-net tail: percentile of the window's counts (100 = the largest, rounds 5 to mid-6; option "sb_pct", NSK_SB_PCT; 90 measured +0.6 %, with skip_close +1.3 %: profiles/r06_ab_fuse2.txt)
   int proj_absorb = -1;                 // the update of the pressure projection space of step s applied by its first readers in step s + 1 (k_pres_rhs, k_proj_apply_e) instead of a k_proj_update launch per step: -1 = where the solve starts inside A_0 (absorb_on), 0 = never, 1 = the same as -1 (contexts without that start ignore it); option "proj_absorb"
+  int conv_fuse = -1;                   // convection and the velocity right-hand side in one launch (k_convect_rhs) instead of k_convect + k_rhs: -1 = where allowed (convfuse_on), 0 = never, 1 = the same as -1 (every other context ignores it); option "conv_fuse"
   bool up_host = false;                 // steps with the deferred update are queued and no flush behind them yet (flush_proj)
   int fuse2_start = 1;                  // ... and the solve's start inside its first launch (k_proj_apply_e; no k_gmres_update(-1) launch); option "fuse2_start", NSK_FUSE2_START
   int fuse2 = 1;                        // round 6: the merged iteration in TWO launches (k_schwarz_uc, k_divgs_t; option "fuse2", NSK_FUSE2); 0 = the three launches of rounds 3-5
@@ -1069,6 +1071,24 @@ static bool absorb_on(const nsk_ctx* c) {
   if (!(fuse2_on(c) && c->fuse2_start && d.nproj_max > 0 && d.nproj_max <= MAXPROJ)) return false;
   return c->max_pres > 0 && std::min(c->merged_iters, c->gmres_cycle) > 0;
 }
+// Convection and the velocity right-hand side in one launch (option "conv_fuse"): quadrilaterals on one rank whose velocity solve
+// is launched per iteration, no forcing added between the two halves.  Everything else -- hexahedra, shards, forced maps, the
+// persistent form, the operator tests -- keeps k_convect + k_rhs, whatever the option says.  Host-checked (eager) steps take it too.
+static bool convfuse_on(const nsk_ctx* c) {
+  if (c->conv_fuse == 0 || c->ndim != 2 || c->parent || c->d.nranks > 1 || c->fused || c->force || c->in_test) return false;
+  return true;
+}
+template <int N>
+static void launch_convect_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool absorb) {      // (quadrilaterals only: convfuse_on)
+  if (c->ndim != 2) return;
+  if (absorb) hipLaunchKernelGGL((nsk::k2::k_convect_rhs<N, true>), dim3(c->nblk + 1), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
+  else hipLaunchKernelGGL((nsk::k2::k_convect_rhs<N, false>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
+}
+template <int N>
+static void launch_pres_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, int helm_par, int check_helm) {      // (quadrilaterals only: the plain k_pres_rhs with Dev::bstep_late)
+  if (c->ndim != 2) return;
+  hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, false>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
+}
 // A map ends, or something is about to read, copy or reset the space: the update its last step left behind goes in with the
 // standalone kernel (one launch per map), and the context looks as it does without the option.
 static int flush_proj(nsk_ctx* c) {
@@ -1481,13 +1501,19 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
   // the bookkeeping workgroup, k_pres_rhs / k_proj_apply_e apply the last step's update, no k_proj_update launch
   const bool absorb = in_map && absorb_on(c);
   Dev da = d; da.absorb = absorb ? 1 : 0;
+  // one launch for convection + right-hand side (convfuse_on); it reads *bstep in every workgroup, so this step's k_pres_rhs
+  // advances it (once per step in every launch mode: budgets, tails, eager, captured)
+  const bool cfuse = convfuse_on(c);
+  if (cfuse) da.bstep_late = ((d.bf_stride || d.forb) && adjoint != 2) ? 1 : 0;
+  if (cfuse && !in_map) c->convfuse_steps++;            // (the steps of a map are counted by run_map: a captured step is replayed)
   int nh = hc ? c->max_helm : (nh_over > 0 ? nh_over : c->cur_helm[sc.cls]);
   DISPATCH_N(c->key, {
     constexpr int NT = Cfg<N>::NT;
     if (d.forb && adjoint != 2)       // Fourier orbit: the base flow of this step into the steady slot (hexahedra: cUr is the 12-constant array)
       hipLaunchKernelGGL(k_baseflow_fourier<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (double*)d.cUr, (double*)d.cUs,
                          (double*)d.GUx, (double*)d.GUy, (double*)d.GVx, (double*)d.GVy);
-    if (c->key == 108 && adjoint != 2 && c->mfma_convect)
+    if (cfuse) { }                  // (below: k_convect_rhs)
+    else if (c->key == 108 && adjoint != 2 && c->mfma_convect)
       hipLaunchKernelGGL(nsk::k3::k_convect_mfma8, dim3(c->nel), dim3(512), 0, c->stream, d, (const double*)d.u, d.bf, adjoint);
     else if (c->key == 110 && adjoint != 2 && c->mfma_convect)
       hipLaunchKernelGGL(nsk::k3::k_convect_mfma<10>, dim3(c->nel), dim3(512), 0, c->stream, d, (const double*)d.u, d.bf, adjoint);
@@ -1502,7 +1528,8 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       HIPCHK(hipMemsetAsync(c->sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
       launch_fused<N>(c, sc);
     } else {
-      if (absorb) launch_rhs_absorb<N>(c, da, sc);
+      if (cfuse) launch_convect_rhs<N>(c, da, sc, absorb);
+      else if (absorb) launch_rhs_absorb<N>(c, da, sc);
       else hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc);
       if (tail) nh = std::max(1, std::min(nh, c->max_helm - 1));      // HEAD launches; the persistent tail runs launches nh .. max_helm-1
       for (int it = 0; it < nh; ++it) {
@@ -1517,6 +1544,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       }
       if (tail) { launch_helm_tail<N>(c, d, sc, nh, c->max_helm); nh = c->max_helm; }
       if (absorb) launch_pres_rhs_absorb<N>(c, da, sc, (nh - 1) & 1, nh - 1);
+      else if (cfuse) launch_pres_rhs<N>(c, da, sc, (nh - 1) & 1, nh - 1);
       else hipLaunchKernelGGL(k_pres_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc, (nh - 1) & 1, nh - 1);
     }
   });
@@ -1687,6 +1715,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
     HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
   }
   if (absorb_on(c)) { c->up_host = true; c->absorb_maps++; }
+  if (convfuse_on(c)) c->convfuse_steps += c->nsteps;
   for (int istep = 1; istep <= c->nsteps; ++istep) {
     if (per_step) {
       HIPCHK(hipGraphLaunch(plan[istep - 1], c->stream));
@@ -2517,6 +2546,11 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
     int rc = flush_proj(c); if (rc) return rc;
     c->proj_absorb = (int)value;
   }
+  else if (n == "conv_fuse") {
+    if (value != -1.0 && value != 0.0 && value != 1.0) return fail(NSK_EINVAL, "conv_fuse: -1, 0 or 1");
+    c->conv_fuse = (int)value;
+    invalidate_graphs(c);
+  }
   else if (n == "fuse2_start") { c->fuse2_start = (int)value; invalidate_graphs(c); }
   else if (n == "sb_pct") { c->sb_pct = (int)value; }
   else if (n == "skip_close") { c->skip_close = (int)value; invalidate_graphs(c); }
@@ -2680,6 +2714,7 @@ int nsk_get_stats(nsk_ctx* c, nsk_stats* s) {
   s->step_budget_maps = c->sb_maps;
   s->tail_maps = c->tail_maps;
   s->absorb_maps = c->absorb_maps;
+  s->convfuse_steps = c->convfuse_steps;
   s->zero_arrays = (long long)c->d.zmask | ((long long)c->d.bfmask << 12);
   s->step_budget_helm_mean = c->sb_maps ? (double)c->sb_launch_h / ((double)c->sb_steps) : 0.0;
   s->step_budget_pres_mean = c->sb_maps ? (double)c->sb_launch_p / ((double)c->sb_steps) : 0.0;
@@ -3823,6 +3858,19 @@ int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
         if (n == "convect_mfma" && c->key == 108) hipLaunchKernelGGL(nsk::k3::k_convect_mfma8, dim3(c->nel), dim3(512), 0, c->stream, d, (const double*)d.u, d.bf, 0);
         else if (n == "convect_mfma") hipLaunchKernelGGL(nsk::k3::k_convect_mfma<10>, dim3(c->nel), dim3(512), 0, c->stream, d, (const double*)d.u, d.bf, 0);
         else hipLaunchKernelGGL(k_convect<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)d.u, d.bf, 0);
+      }
+      HIPCHK(hipEventRecord(e1, c->stream));
+    });
+  } else if (n == "convect_rhs") {
+    // convection + velocity right-hand side in one launch (k_convect_rhs, the plain instantiation) on the state the last map left
+    if (c->ndim != 2) return fail(NSK_EINVAL, "k_convect_rhs: quadrilateral contexts");
+    const StepCoef sc = make_coef(c, 17, 0);
+    if (d.bf_stride || d.forb) HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));      // (the first slot; this kernel does not advance it)
+    HIPCHK(hipStreamSynchronize(c->stream));
+    DISPATCH_N(c->key, {
+      for (int r = 0; r < reps + 3; ++r) {
+        if (r == 3) HIPCHK(hipEventRecord(e0, c->stream));
+        launch_convect_rhs<N>(c, d, sc, false);
       }
       HIPCHK(hipEventRecord(e1, c->stream));
     });

@@ -384,123 +384,207 @@ struct BasisRegs {
 // ---------------------------------------------------------------------------
 // K1: forcing + dealiased convection  -> bf (mass weighted)
 //   makeufp + advabp / advabp_adjoint  [UPSTREAM perturb.f], sponge term of
-//   nekStab_forcing (core/utils.f:172-177).  One element per workgroup, one
-//   thread per dealiasing node.
+//   nekStab_forcing (core/utils.f:172-177).
 // ---------------------------------------------------------------------------
+// The body, shared by k_convect (EL = 1: one element per workgroup of NTD threads, one thread per dealiasing node) and
+// k_convect_rhs (EL = EPB elements per workgroup of Cfg<N>::NT threads: the stages loop over the workgroup's EL x ND^2 fine
+// nodes).  Two halves: `issue` puts every global operand in registers -- the caller sends its own loads behind them, all before
+// the first wait --, `run` is the five tensor stages and leaves the forcing at GLL node (el, nd) = (tid / NN, tid % NN) of the
+// workgroup in the registers of that thread.  FUSED: barriers that order LDS only (the caller's loads stay in flight), and the
+// back-projection reuses the tile of the forward interpolation.
+template <int N, int EL, int NT, bool FUSED>
+struct Convect {
+  using C = Cfg<N>;
+  static constexpr int NN = C::NN, ND = C::ND, NDD = C::NDD, NI = N * ND;
+  static constexpr int KF = (EL * NDD + NT - 1) / NT, KI = (EL * NI + NT - 1) / NT, KJ = (NI + NT - 1) / NT, KD = (NDD + NT - 1) / NT;
+  static_assert(EL * NN <= NT, "one thread per GLL node of the workgroup");
+  double u0 = 0, u1 = 0, sp0 = 0, bm0 = 0;
+  double cc[KF][6];
+  double jd[KJ], dd[KD];
+
+  // e0: first element of the workgroup; elements at and behind d.nel do nothing
+  __device__ __forceinline__ void issue(const Dev& d, const double* __restrict__ uin, int adjoint, long long e0, int tid) {
+    const int el = tid / NN, nd = tid % NN;
+    const bool act = el < EL && e0 + el < d.nel;
+    // the field first (the first barrier waits for it; loads return in issue order), then the pointwise operands of the
+    // fine-mesh product and of the sponge term, which are used after two and four barriers and depend on nothing
+    if (act) { u0 = uin[(e0 + el) * NN + nd]; u1 = uin[d.cs + (e0 + el) * NN + nd]; }
+#pragma unroll
+    for (int r = 0; r < KF; ++r) {
+#pragma unroll
+      for (int m = 0; m < 6; ++m) cc[r][m] = 0;
+      const int k = tid + r * NT, fe = k / NDD;
+      if (k < EL * NDD && e0 + fe < d.nel) {
+        const long long q = e0 * NDD + k;
+        if (adjoint == 2) { cc[r][0] = d.rxd[q]; cc[r][1] = d.ryd[q]; cc[r][2] = d.sxd[q]; cc[r][3] = d.syd[q]; }
+        else {
+          const long long qb = q + (d.bf_stride ? (long long)(*d.bstep) * d.bf_stride : 0);
+          cc[r][0] = d.cUr[qb]; cc[r][1] = d.cUs[qb]; cc[r][2] = d.GUx[qb]; cc[r][3] = d.GUy[qb]; cc[r][4] = d.GVx[qb]; cc[r][5] = d.GVy[qb];
+        }
+      }
+    }
+    if (act) { sp0 = d.spng[(e0 + el) * NN + nd]; bm0 = d.bm1[(e0 + el) * NN + nd]; }     // (multiplied where they are used: no wait here)
+#pragma unroll
+    for (int r = 0; r < KJ; ++r) jd[r] = (tid + r * NT < NI) ? d.Jd[tid + r * NT] : 0.0;
+#pragma unroll
+    for (int r = 0; r < KD; ++r) dd[r] = (tid + r * NT < NDD) ? d.Dd[tid + r * NT] : 0.0;
+  }
+
+  static __device__ __forceinline__ void sync() {
+    if constexpr (FUSED) lds_barrier(); else __syncthreads();
+  }
+
+  // b0, b1: the forcing at this thread's GLL node (threads with tid / NN >= EL or an element behind the mesh: unspecified)
+  __device__ __forceinline__ void run(const Dev& d, int adjoint, long long e0, int tid, double& b0, double& b1) {
+    __shared__ double sJ[NI], sDd[NDD];
+    __shared__ double su[2][EL * NN], st[2][EL * NI], sf[2][EL * NDD], so[2][EL * NDD], sq_[FUSED ? 1 : 2 * EL * NI];
+    double* sq0 = FUSED ? &st[0][0] : &sq_[0];          // (the forward tile is dead after the second stage)
+    double* sq1 = sq0 + EL * NI;
+    const int el = tid / NN, nd = tid % NN;
+    const bool act = el < EL && e0 + el < d.nel;
+#pragma unroll
+    for (int r = 0; r < KJ; ++r) if (tid + r * NT < NI) sJ[tid + r * NT] = jd[r];
+#pragma unroll
+    for (int r = 0; r < KD; ++r) if (tid + r * NT < NDD) sDd[tid + r * NT] = dd[r];
+    if (act) { su[0][tid] = u0; su[1][tid] = u1; }
+    sync();
+    // interpolate in r: st[c][j][a] = sum_i Jd[a][i] u[j][i]
+#pragma unroll
+    for (int r = 0; r < KI; ++r) {
+      const int k = tid + r * NT, fe = k / NI, t = k % NI;
+      if (k < EL * NI && e0 + fe < d.nel) {
+        const int j = t / ND, a = t % ND;
+        const double *x0 = &su[0][fe * NN], *x1 = &su[1][fe * NN];
+        double s0 = 0, s1 = 0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+          const double w = sJ[a * N + i];
+          s0 += w * x0[j * N + i];
+          s1 += w * x1[j * N + i];
+        }
+        st[0][k] = s0; st[1][k] = s1;
+      }
+    }
+    sync();
+#pragma unroll
+    for (int r = 0; r < KF; ++r) {
+      const int k = tid + r * NT, fe = k / NDD, t = k % NDD;
+      if (k < EL * NDD && e0 + fe < d.nel) {
+        const int b = t / ND, a = t % ND;
+        const double *x0 = &st[0][fe * NI], *x1 = &st[1][fe * NI];
+        double s0 = 0, s1 = 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          const double w = sJ[b * N + j];
+          s0 += w * x0[j * ND + a];
+          s1 += w * x1[j * ND + a];
+        }
+        sf[0][k] = s0; sf[1][k] = s1;
+      }
+    }
+    sync();
+#pragma unroll
+    for (int r = 0; r < KF; ++r) {
+      const int k = tid + r * NT, fe = k / NDD, t = k % NDD;
+      if (k < EL * NDD && e0 + fe < d.nel) {
+        const int b = t / ND, a = t % ND;
+        const double *f0 = &sf[0][fe * NDD], *f1 = &sf[1][fe * NDD];
+        const double c0 = cc[r][0], c1 = cc[r][1], c2 = cc[r][2], c3 = cc[r][3], c4 = cc[r][4], c5 = cc[r][5];
+        double ur = 0, us = 0, vr = 0, vs = 0;
+#pragma unroll
+        for (int kk = 0; kk < ND; ++kk) {
+          const double dr = sDd[a * ND + kk], ds = sDd[b * ND + kk];
+          ur += dr * f0[b * ND + kk]; us += ds * f0[kk * ND + a];
+          vr += dr * f1[b * ND + kk]; vs += ds * f1[kk * ND + a];
+        }
+        const double uf = f0[t], vf = f1[t];
+        double ox, oy;
+        {
+          // The pointwise products with their roundings spelled out: which product of  a b + c d  the compiler fuses depends on
+          // the code around it, and both kernels that call this body must give what k_convect gave when it stood alone.
+#pragma clang fp contract(off)
+          if (adjoint == 2) {      // full equations: (u.grad) u   [UPSTREAM advab], newton_krylov's nonlinear map
+            const double cr = __builtin_fma(c0, uf, c1 * vf), cs = __builtin_fma(c2, uf, c3 * vf);           // rxd, ryd, sxd, syd
+            ox = __builtin_fma(cr, ur, cs * us);
+            oy = __builtin_fma(cr, vr, cs * vs);
+          } else {
+            // base-flow constants (steady, or slot `*bstep` of the stored periodic orbit: Floquet, core/matvec.f:200-236):
+            // c0..c5 = cUr, cUs, GUx, GUy, GVx, GVy
+            const double conv_u = __builtin_fma(c0, ur, c1 * us), conv_v = __builtin_fma(c0, vr, c1 * vs);   // (U.grad) u'
+            const double ux = uf * c2;
+            if (!adjoint) {          // + (u'.grad) U
+              ox = __builtin_fma(vf, c3, conv_u + ux);
+              oy = __builtin_fma(vf, c5, __builtin_fma(uf, c4, conv_v));
+            } else {                 // (grad U)^T u' - (U.grad) u'
+              ox = __builtin_fma(vf, c4, ux) - conv_u;
+              oy = __builtin_fma(uf, c3, vf * c5) - conv_v;
+            }
+          }
+        }
+        so[0][k] = ox; so[1][k] = oy;
+      }
+    }
+    sync();
+    // project back: sq[c][b][i] = sum_a Jd[a][i] so[b][a]
+#pragma unroll
+    for (int r = 0; r < KI; ++r) {
+      const int k = tid + r * NT, fe = k / NI, t = k % NI;
+      if (k < EL * NI && e0 + fe < d.nel) {
+        const int bb = t / N, i = t % N;
+        const double *o0 = &so[0][fe * NDD], *o1 = &so[1][fe * NDD];
+        double s0 = 0, s1 = 0;
+#pragma unroll
+        for (int aa = 0; aa < ND; ++aa) {
+          const double w = sJ[aa * N + i];
+          s0 += w * o0[bb * ND + aa];
+          s1 += w * o1[bb * ND + aa];
+        }
+        sq0[k] = s0; sq1[k] = s1;
+      }
+    }
+    sync();
+    if (act) {
+      const int j = nd / N, i = nd % N;
+      const double *q0 = sq0 + el * NI, *q1 = sq1 + el * NI;
+      double s0 = 0, s1 = 0;
+#pragma unroll
+      for (int bb = 0; bb < ND; ++bb) {
+        const double w = sJ[bb * N + j];
+        s0 += w * q0[bb * N + i];
+        s1 += w * q1[bb * N + i];
+      }
+      const long long l = (e0 + el) * NN + nd;
+      {
+#pragma clang fp contract(off)
+        const double sb = sp0 * bm0;
+        if (adjoint == 2) {      // DNS sponge: spng_fun (u_ref - u) spng_str   (core/utils.f:165-170)
+          const double k = sb * d.nl_spng_str;
+          b0 = ((k != 0.0) ? k * (d.spng_vr[l] - u0) : 0.0) - s0;
+          b1 = ((k != 0.0) ? k * (d.spng_vr[d.cs + l] - u1) : 0.0) - s1;
+        } else {
+          b0 = -__builtin_fma(sb, u0, s0);
+          b1 = -__builtin_fma(sb, u1, s1);
+        }
+      }
+    }
+  }
+};
+
+// one element per workgroup, one thread per dealiasing node
 template <int N>
 __global__ __launch_bounds__(Cfg<N>::NTD) void k_convect(Dev d, const double* __restrict__ uin,
                                                          double* __restrict__ bf, int adjoint) {
-  using C = Cfg<N>;
-  constexpr int NN = C::NN, ND = C::ND, NDD = C::NDD, NT = C::NTD;
-  __shared__ double sJ[ND * N], sDd[ND * ND];
-  __shared__ double su[2][NN], st[2][N * ND], sf[2][NDD], so[2][NDD], sq[2][ND * N];
+  constexpr int NN = Cfg<N>::NN;
   const int tid = threadIdx.x;
   const long long e = blockIdx.x;
-  // the field first (the first barrier waits for it; loads return in issue order), then the pointwise operands of the
-  // fine-mesh product and of the sponge term, which are used after two and four barriers and depend on nothing
-  double u0 = 0, u1 = 0;
-  if (tid < NN) { u0 = uin[e * NN + tid]; u1 = uin[d.cs + e * NN + tid]; }
-  double c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, sp0 = 0, bm0 = 0;
-  if (tid < NDD) {
-    const long long q = e * NDD + tid;
-    if (adjoint == 2) { c0 = d.rxd[q]; c1 = d.ryd[q]; c2 = d.sxd[q]; c3 = d.syd[q]; }
-    else {
-      const long long qb = q + (d.bf_stride ? (long long)(*d.bstep) * d.bf_stride : 0);
-      c0 = d.cUr[qb]; c1 = d.cUs[qb]; c2 = d.GUx[qb]; c3 = d.GUy[qb]; c4 = d.GVx[qb]; c5 = d.GVy[qb];
-    }
-  }
-  if (tid < NN) { sp0 = d.spng[e * NN + tid]; bm0 = d.bm1[e * NN + tid]; }     // (multiplied where they are used: no wait here)
-  for (int k = tid; k < ND * N; k += NT) sJ[k] = d.Jd[k];
-  for (int k = tid; k < NDD; k += NT) sDd[k] = d.Dd[k];
-  if (tid < NN) { su[0][tid] = u0; su[1][tid] = u1; }
-  __syncthreads();
-  // interpolate in r: st[c][j][a] = sum_i Jd[a][i] u[j][i]
-  if (tid < N * ND) {
-    const int j = tid / ND, a = tid % ND;
-    double s0 = 0, s1 = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      const double w = sJ[a * N + i];
-      s0 += w * su[0][j * N + i];
-      s1 += w * su[1][j * N + i];
-    }
-    st[0][tid] = s0; st[1][tid] = s1;
-  }
-  __syncthreads();
-  const int b = tid / ND, a = tid % ND;
-  const bool fact = tid < NDD;
-  if (fact) {
-    double s0 = 0, s1 = 0;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-      const double w = sJ[b * N + j];
-      s0 += w * st[0][j * ND + a];
-      s1 += w * st[1][j * ND + a];
-    }
-    sf[0][tid] = s0; sf[1][tid] = s1;
-  }
-  __syncthreads();
-  if (fact) {
-    double ur = 0, us = 0, vr = 0, vs = 0;
-#pragma unroll
-    for (int k = 0; k < ND; ++k) {
-      const double dr = sDd[a * ND + k], ds = sDd[b * ND + k];
-      ur += dr * sf[0][b * ND + k]; us += ds * sf[0][k * ND + a];
-      vr += dr * sf[1][b * ND + k]; vs += ds * sf[1][k * ND + a];
-    }
-    const double uf = sf[0][tid], vf = sf[1][tid];
-    double ox, oy;
-    if (adjoint == 2) {      // full equations: (u.grad) u   [UPSTREAM advab], newton_krylov's nonlinear map
-      const double cr = c0 * uf + c1 * vf, cs = c2 * uf + c3 * vf;           // rxd, ryd, sxd, syd
-      ox = cr * ur + cs * us;
-      oy = cr * vr + cs * vs;
-    } else {
-      // base-flow constants (steady, or slot `*bstep` of the stored periodic orbit: Floquet, core/matvec.f:200-236):
-      // c0..c5 = cUr, cUs, GUx, GUy, GVx, GVy
-      const double conv_u = c0 * ur + c1 * us, conv_v = c0 * vr + c1 * vs;   // (U.grad) u'
-      if (!adjoint) {          // + (u'.grad) U
-        ox = conv_u + uf * c2 + vf * c3;
-        oy = conv_v + uf * c4 + vf * c5;
-      } else {                 // (grad U)^T u' - (U.grad) u'
-        ox = uf * c2 + vf * c4 - conv_u;
-        oy = uf * c3 + vf * c5 - conv_v;
-      }
-    }
-    so[0][tid] = ox; so[1][tid] = oy;
-  }
-  __syncthreads();
-  // project back: sq[c][b][i] = sum_a Jd[a][i] so[b][a]
-  if (tid < ND * N) {
-    const int bb = tid / N, i = tid % N;
-    double s0 = 0, s1 = 0;
-#pragma unroll
-    for (int aa = 0; aa < ND; ++aa) {
-      const double w = sJ[aa * N + i];
-      s0 += w * so[0][bb * ND + aa];
-      s1 += w * so[1][bb * ND + aa];
-    }
-    sq[0][tid] = s0; sq[1][tid] = s1;
-  }
-  __syncthreads();
+  Convect<N, 1, Cfg<N>::NTD, false> cv;
+  cv.issue(d, uin, adjoint, e, tid);
+  double b0 = 0, b1 = 0;
+  cv.run(d, adjoint, e, tid, b0, b1);
   if (tid < NN) {
-    const int j = tid / N, i = tid % N;
-    double s0 = 0, s1 = 0;
-#pragma unroll
-    for (int bb = 0; bb < ND; ++bb) {
-      const double w = sJ[bb * N + j];
-      s0 += w * sq[0][bb * N + i];
-      s1 += w * sq[1][bb * N + i];
-    }
     const long long l = e * NN + tid;
-    const double sb = sp0 * bm0;
-    if (adjoint == 2) {      // DNS sponge: spng_fun (u_ref - u) spng_str   (core/utils.f:165-170)
-      const double k = sb * d.nl_spng_str;
-      bf[l] = ((k != 0.0) ? k * (d.spng_vr[l] - su[0][tid]) : 0.0) - s0;
-      bf[d.cs + l] = ((k != 0.0) ? k * (d.spng_vr[d.cs + l] - su[1][tid]) : 0.0) - s1;
-    } else {
-      bf[l] = -(sb * su[0][tid] + s0);
-      bf[d.cs + l] = -(sb * su[1][tid] + s1);
-    }
+    bf[l] = b0;
+    bf[d.cs + l] = b1;
   }
 }
 
@@ -698,27 +782,35 @@ __device__ inline void proj_book(const Dev& d, const StepCoef& sc) {
 // K2: makextp + makebdfp + lagfieldp + extrapprp + cresvipp  [UPSTREAM perturb.f]
 //   r_loc = EXT(bf) + BDF lags + D^T p* - H u^n   (unassembled)
 // ---------------------------------------------------------------------------
-// AB: the instantiation of the steps with the deferred update of the projection space -- one workgroup more, the bookkeeping
-// workgroup proj_book; every other launch keeps the plain one
-template <int N, bool AB = false>
-__global__ __launch_bounds__(Cfg<N>::NT) void k_rhs(Dev d, StepCoef sc) {
-  using C = Cfg<N>;
-  constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NT = C::NT, NM = N * M;
-  __shared__ double sD[NN], sDt[NN], sJ12[NM], sD12[NM];
-  __shared__ double su[2 * EPB * NN], st1[2 * EPB * NN], st2[2 * EPB * NN];
-  __shared__ double sP[4 * EPB * MM], sB[4 * EPB * NM];
-  const int tid = threadIdx.x, el = tid / NN, nd = tid % NN;
-  const long long e = (long long)blockIdx.x * EPB + el;
-  const bool act = (el < EPB) && (e < d.nel);
-  const int j = nd / N, i = nd % N;
-  const long long l = e * NN + nd, nl = d.cs;
-  static_assert(NT >= NN, "one basis entry per thread");
-  if constexpr (AB) {
-    if (blockIdx.x == (unsigned)d.nblk) { proj_book<NT>(d, sc); return; }     // the extra workgroup of the deferred update
+// The body, shared by k_rhs and k_convect_rhs, in three parts.  RhsRegs::issue: every global operand of a node into registers
+// (FUSED: not the convected field and the mass matrix, which the convection half has loaded, and not bf, which it computes).
+// rhs_block0: the once-per-step scalars of workgroup 0.  rhs_body: the arithmetic, the lag shifts and the two tile operators.
+template <int N, bool FUSED>
+struct RhsRegs {
+  double un[2] = {0, 0}, dl1[2] = {0, 0}, dl2[2] = {0, 0}, dl3[2] = {0, 0}, bn[2] = {0, 0}, e1[2] = {0, 0}, e2[2] = {0, 0}, l1[2] = {0, 0}, l2[2] = {0, 0};
+  double pn = 0, plg = 0, m0 = 0, m1 = 0, m2 = 0, m3 = 0, bm = 0, g1 = 0, g2 = 0, g4 = 0;
+  __device__ __forceinline__ void issue(const Dev& d, long long l, long long q, bool pl) {
+    const long long nl = d.cs;
+    if constexpr (!FUSED) bm = d.bm1[l];
+    g1 = d.g1[l]; g2 = d.g2[l]; g4 = d.g4[l];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const long long lc = c * nl + l;
+      if constexpr (!FUSED) un[c] = d.u[lc];
+      dl1[c] = d.dulag[lc]; dl2[c] = d.dulag[2 * nl + lc]; dl3[c] = d.dulag[4 * nl + lc];
+      if constexpr (!FUSED) bn[c] = d.bf[lc];
+      e1[c] = d.exlag[lc]; e2[c] = d.exlag[2 * nl + lc];
+      l1[c] = d.ulag[lc]; l2[c] = d.ulag[2 * nl + lc];
+    }
+    if (pl) { pn = d.p[q]; plg = d.plag[q]; m0 = d.w2rx[q]; m1 = d.w2sx[q]; m2 = d.w2ry[q]; m3 = d.w2sy[q]; }
   }
-  BasisRegs<N> br;
-  br.issue(d, tid, true, true);
-  if ((d.bf_stride || d.forb) && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;     // next step reads the next orbit slot / trig row
+};
+
+// BSTEP: this launch advances the orbit slot / trig row (k_convect_rhs reads it in every workgroup and leaves the increment to
+// a later launch of the step, k_pres_rhs: Dev::bstep_late -- no launch reads a scalar it writes)
+template <bool AB, bool BSTEP>
+__device__ __forceinline__ void rhs_block0(const Dev& d, const StepCoef& sc, int tid) {
+  if (BSTEP && (d.bf_stride || d.forb) && sc.adjoint != 2 && blockIdx.x == 0 && tid == 0) *d.bstep += 1;     // next step reads the next orbit slot / trig row
   if (d.stepctr && blockIdx.x == 0 && tid == 0) *d.stepctr += 1;                          // per-step iteration record (rec_step_iters)
   if (d.nproj_max > 0 && !AB && blockIdx.x == 0 && tid == 0) {
     GmresScal* G = d.gsc;
@@ -738,46 +830,49 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_rhs(Dev d, StepCoef sc) {
     }
     if (d.proj_reset && sc.cls == 0) { G->pcnt = 0; G->nproj = 0; }      // first step of a map: the space of the last map is stale
   }
-  double u[2] = {0, 0}, bfv[2] = {0, 0}, bm = 0, g1 = 0, g2 = 0, g4 = 0;
+}
+
+template <int N, bool FUSED>
+__device__ __forceinline__ void rhs_body(const Dev& d, const StepCoef& sc, const RhsRegs<N, FUSED>& R, const BasisRegs<N>& br,
+                                         bool act, int tid, int el, int nd, long long e) {
+  using C = Cfg<N>;
+  constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NM = N * M;
+  __shared__ double sD[NN], sDt[NN], sJ12[NM], sD12[NM];
+  __shared__ double su[2 * EPB * NN], st1[2 * EPB * NN], st2[2 * EPB * NN];
+  __shared__ double sP[4 * EPB * MM], sB[4 * EPB * NM];
+  const int j = nd / N, i = nd % N;
+  const long long l = e * NN + nd, nl = d.cs;
+  const double bm = R.bm, g1 = R.g1, g2 = R.g2, g4 = R.g4;
+  double u[2] = {0, 0}, bfv[2] = {0, 0};
   if (act) {
-    // every load first, then the arithmetic and the lag shifts: a store between two loads pins their order (the compiler must
-    // assume the arrays alias), and each pinned load is one more round trip
+    // the roundings of the sums of products spelled out (see Convect::run): the SECOND product of a sum is rounded, the first and
+    // every further one fused -- what k_rhs gave when it stood alone
+#pragma clang fp contract(off)
     const bool pl = nd < MM;
     const long long q = e * MM + nd;
-    double un[2], dl1[2], dl2[2], dl3[2], bn[2], e1[2], e2[2], l1[2], l2[2];
-    double pn = 0, plg = 0, m0 = 0, m1 = 0, m2 = 0, m3 = 0;
-    bm = d.bm1[l]; g1 = d.g1[l]; g2 = d.g2[l]; g4 = d.g4[l];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       const long long lc = c * nl + l;
-      un[c] = d.u[lc];
-      dl1[c] = d.dulag[lc]; dl2[c] = d.dulag[2 * nl + lc]; dl3[c] = d.dulag[4 * nl + lc];
-      bn[c] = d.bf[lc];
-      e1[c] = d.exlag[lc]; e2[c] = d.exlag[2 * nl + lc];
-      l1[c] = d.ulag[lc]; l2[c] = d.ulag[2 * nl + lc];
-    }
-    if (pl) { pn = d.p[q]; plg = d.plag[q]; m0 = d.w2rx[q]; m1 = d.w2sx[q]; m2 = d.w2ry[q]; m3 = d.w2sy[q]; }
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const long long lc = c * nl + l;
-      u[c] = un[c] + sc.xg[0] * dl1[c] + sc.xg[1] * dl2[c] + sc.xg[2] * dl3[c];   // u^n + du0 (extrapolated guess)
+      u[c] = __builtin_fma(sc.xg[2], R.dl3[c], __builtin_fma(sc.xg[1], R.dl2[c], __builtin_fma(sc.xg[0], R.dl1[c], R.un[c])));   // u^n + du0 (extrapolated guess)
       su[(c * EPB + el) * NN + nd] = u[c];
-      double b = sc.ab[0] * bn[c] + sc.ab[1] * e1[c] + sc.ab[2] * e2[c];      // makextp
-      d.exlag[2 * nl + lc] = e1[c];
-      d.exlag[lc] = bn[c];
-      b += bm * (sc.bd[1] * un[c] + sc.bd[2] * l1[c] + sc.bd[3] * l2[c]) * sc.invdt;   // makebdfp
-      d.ulag[2 * nl + lc] = l1[c];                                   // lagfieldp
-      d.ulag[lc] = un[c];
+      double b = __builtin_fma(sc.ab[2], R.e2[c], __builtin_fma(sc.ab[0], R.bn[c], sc.ab[1] * R.e1[c]));      // makextp
+      d.exlag[2 * nl + lc] = R.e1[c];
+      d.exlag[lc] = R.bn[c];
+      const double lag = __builtin_fma(sc.bd[3], R.l2[c], __builtin_fma(sc.bd[1], R.un[c], sc.bd[2] * R.l1[c]));
+      b = __builtin_fma(bm * lag, sc.invdt, b);                          // makebdfp
+      d.ulag[2 * nl + lc] = R.l1[c];                                   // lagfieldp
+      d.ulag[lc] = R.un[c];
       bfv[c] = b;
     }
     if (pl) {                                                        // extrapprp
-      const double pe = (sc.pxt == 0.0) ? pn : ((sc.pxt == 1.0) ? 2.0 * pn - plg : pn + sc.pxt * (pn - plg));
+      const double pn = R.pn, plg = R.plg;
+      const double pe = (sc.pxt == 0.0) ? pn : ((sc.pxt == 1.0) ? __builtin_fma(2.0, pn, -plg) : __builtin_fma(sc.pxt, pn - plg, pn));
       d.plag[q] = pn;
       d.pext[q] = pe;
-      sP[(0 * EPB + el) * MM + nd] = pe * m0;
-      sP[(1 * EPB + el) * MM + nd] = pe * m1;
-      sP[(2 * EPB + el) * MM + nd] = pe * m2;
-      sP[(3 * EPB + el) * MM + nd] = pe * m3;
+      sP[(0 * EPB + el) * MM + nd] = pe * R.m0;
+      sP[(1 * EPB + el) * MM + nd] = pe * R.m1;
+      sP[(2 * EPB + el) * MM + nd] = pe * R.m2;
+      sP[(3 * EPB + el) * MM + nd] = pe * R.m3;
     }
   }
   br.commit(sD, sDt, sJ12, sD12, tid);
@@ -787,12 +882,67 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_rhs(Dev d, StepCoef sc) {
   double au[2];
   axhelm_tiles<N, EPB, 2>(sD, sDt, su, st1, st2, act, el, j, i, g1, g2, g4, au);
   if (act) {
+#pragma clang fp contract(off)
     const double bx = bfv[0] + gx, by = bfv[1] + gy;                 // rhs of H u* = b
+    const double hb = sc.h2 * bm;
     d.bloc[l] = bx;
     d.bloc[nl + l] = by;
-    d.rloc[l] = bx - (d.nu * au[0] + sc.h2 * bm * u[0]);
-    d.rloc[nl + l] = by - (d.nu * au[1] + sc.h2 * bm * u[1]);
+    d.rloc[l] = bx - __builtin_fma(d.nu, au[0], hb * u[0]);
+    d.rloc[nl + l] = by - __builtin_fma(d.nu, au[1], hb * u[1]);
   }
+}
+
+// AB: the instantiation of the steps with the deferred update of the projection space -- one workgroup more, the bookkeeping
+// workgroup proj_book; every other launch keeps the plain one
+template <int N, bool AB = false>
+__global__ __launch_bounds__(Cfg<N>::NT) void k_rhs(Dev d, StepCoef sc) {
+  using C = Cfg<N>;
+  constexpr int NN = C::NN, MM = C::MM, EPB = C::EPB, NT = C::NT;
+  const int tid = threadIdx.x, el = tid / NN, nd = tid % NN;
+  const long long e = (long long)blockIdx.x * EPB + el;
+  const bool act = (el < EPB) && (e < d.nel);
+  static_assert(NT >= NN, "one basis entry per thread");
+  if constexpr (AB) {
+    if (blockIdx.x == (unsigned)d.nblk) { proj_book<NT>(d, sc); return; }     // the extra workgroup of the deferred update
+  }
+  BasisRegs<N> br;
+  br.issue(d, tid, true, true);
+  rhs_block0<AB, true>(d, sc, tid);
+  // every load first, then the arithmetic and the lag shifts: a store between two loads pins their order (the compiler must
+  // assume the arrays alias), and each pinned load is one more round trip
+  RhsRegs<N, false> R;
+  if (act) R.issue(d, e * NN + nd, e * MM + nd, nd < MM);
+  rhs_body<N, false>(d, sc, R, br, act, tid, el, nd, e);
+}
+
+// ---------------------------------------------------------------------------
+// K1 + K2 in one launch (option "conv_fuse"): the workgroups of k_rhs run the convection of their EPB elements first and hand
+// the forcing to the right-hand side in registers -- the thread that ends the back-projection at a GLL node is the thread that
+// extrapolates it.  One trip to memory for the operands of both halves, no bf written or read (exlag[0] keeps the value), and
+// with AB the bookkeeping workgroup runs next to element workgroups that are longer than it is.  Same bodies as the two
+// kernels => the same bits.  *bstep is read here by every workgroup and advanced by this step's k_pres_rhs (Dev::bstep_late).
+// ---------------------------------------------------------------------------
+template <int N, bool AB = false>
+__global__ __launch_bounds__(Cfg<N>::NT) void k_convect_rhs(Dev d, StepCoef sc) {
+  using C = Cfg<N>;
+  constexpr int NN = C::NN, MM = C::MM, EPB = C::EPB, NT = C::NT;
+  const int tid = threadIdx.x, el = tid / NN, nd = tid % NN;
+  const long long e0 = (long long)blockIdx.x * EPB, e = e0 + el;
+  const bool act = (el < EPB) && (e < d.nel);
+  if constexpr (AB) {
+    if (blockIdx.x == (unsigned)d.nblk) { proj_book<NT>(d, sc); return; }     // the extra workgroup of the deferred update
+  }
+  // every load of both halves before the first wait, the convection's first; workgroup 0's scalars (stores) behind them
+  Convect<N, EPB, NT, true> cv;
+  cv.issue(d, d.u, sc.adjoint, e0, tid);
+  BasisRegs<N> br;
+  br.issue(d, tid, true, true);
+  RhsRegs<N, true> R;
+  if (act) R.issue(d, e * NN + nd, e * MM + nd, nd < MM);
+  rhs_block0<AB, false>(d, sc, tid);
+  cv.run(d, sc.adjoint, e0, tid, R.bn[0], R.bn[1]);
+  R.un[0] = cv.u0; R.un[1] = cv.u1; R.bm = cv.bm0;
+  rhs_body<N, true>(d, sc, R, br, act, tid, el, nd, e);
 }
 
 // ---------------------------------------------------------------------------
@@ -1029,6 +1179,7 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_rhs(Dev d, StepCoef sc, int
     if (tid < MAXPROJ) ucf = Gu->up_cf[tid];
     upd = Gu->up_apply != 0; ures = Gu->up_restart != 0; unp = Gu->up_np; us = Gu->up_s; uas = Gu->up_as;
   }
+  if (d.bstep_late && blockIdx.x == 0 && tid == 0) *d.bstep += 1;     // next step reads the next orbit slot / trig row (the steps of k_convect_rhs; every other k_rhs does it)
   if (check_helm && blockIdx.x == 0) {       // last partials -> final residual of the velocity solve
     double s[8];
     if (d.nranks > 1 || d.use_tot) {

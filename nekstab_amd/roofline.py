@@ -21,7 +21,7 @@ def _zero_counts(zero_arrays, ndim):
 
 
 def per_step_bytes(*, nel, lx1, ndim=2, nvert=0, coarse_lda=0, patch_stride=0, nproj=0, helm_iters=0.0, pres_iters=0.0,
-                   pres_jsum=None, coarse_bytes=None, gs_lag=1, zero_arrays=0, fuse2=0, tc_cols=20, proj_absorb=0):
+                   pres_jsum=None, coarse_bytes=None, gs_lag=1, zero_arrays=0, fuse2=0, tc_cols=20, proj_absorb=0, conv_fuse=0):
     """Algorithmic bytes of ONE time step, by kernel family.  ``helm_iters`` / ``pres_iters``: mean iterations per step
     (all velocity components advance together in one CG iteration).  Hexahedra (``ndim = 3``): ``pres_jsum`` = mean per step of
     the sum over the GMRES columns of their basis index j (nsk_stats.total_pres_jsum / total_steps; the Gram-Schmidt bytes
@@ -29,7 +29,9 @@ def per_step_bytes(*, nel, lx1, ndim=2, nvert=0, coarse_lda=0, patch_stride=0, n
     sequence (two basis reads per column) or the classic one (four).  ``zero_arrays``: nsk_stats.zero_arrays -- arrays that vanish on
     every node are not inputs of the kernels (Nek5000 skips them on its undeformed elements the same way) and are not counted.
     ``proj_absorb``: the update of the projection space is applied by its next readers (option "proj_absorb", nsk_stats.absorb_maps
-    > 0): no pass over the space for the update -- delta, E delta in and the two new vectors out are what is left of it."""
+    > 0): no pass over the space for the update -- delta, E delta in and the two new vectors out are what is left of it.
+    ``conv_fuse``: convection and the right-hand side run in one launch (option "conv_fuse", nsk_stats.convfuse_steps > 0): the
+    forcing bf goes from one to the other in registers -- neither its write (K1) nor its read (K2) is counted."""
     zm, zg, zb = _zero_counts(zero_arrays, ndim)
     d = ndim
     N, M, ND = lx1, lx1 - 2, 3 * lx1 // 2
@@ -38,10 +40,11 @@ def per_step_bytes(*, nel, lx1, ndim=2, nvert=0, coarse_lda=0, patch_stride=0, n
     nmet2 = d * d - zm                  # Gauss-mesh metrics per pressure point
     out = {}
     # K1 convection + sponge: u' (d), spng, bm1, bf out (d) on P; base-flow constants on the dealiasing mesh: 2-D 6, 3-D 12
-    out["K1 convect"] = f * (P * (2 * d + 2) + Pd * (6 if d == 2 else 12 - zb))
+    nbf = 0 if conv_fuse else d
+    out["K1 convect"] = f * (P * (d + 2 + nbf) + Pd * (6 if d == 2 else 12 - zb))
     # K2 rhs: u (d), dulag (3d), bf (d), exlag rw (2d + 2d), ulag rw (2d + 2d), bm1, G factors (3 | 6); p, plag rw, pext, metrics on P2; rloc, bloc out (2d)
     ng = 3 if d == 2 else 6 - zg
-    out["K2 rhs"] = f * (P * (d + 3 * d + d + 4 * d + 4 * d + 1 + ng + 2 * d) + P2 * (4 + nmet2))
+    out["K2 rhs"] = f * (P * (d + 3 * d + nbf + 4 * d + 4 * d + 1 + ng + 2 * d) + P2 * (4 + nmet2))
     # K3+K4+K5 one CG iteration of one component: SURVEY 8(d) table: 148 B/pt (2-D), 172 B/pt (3-D)
     out["K3 helm iteration (x n_helm x d)"] = (148.0 if d == 2 else 172.0 - f * zg) * P * d * helm_iters
     # K4' pressure rhs: hx (d), dulag rw (3d + 3d), u rw (2d); metrics, V0 out, PX reads on P2
@@ -124,5 +127,7 @@ def matvec_bytes(stats_total, nsteps, **geom):
         geom = dict(geom, pres_jsum=stats_total.get("total_pres_jsum", 0) / steps, coarse_bytes=stats_total.get("coarse_bytes_per_solve", 0.0))
     if stats_total.get("absorb_maps", 0) > 0:
         geom = dict(geom, proj_absorb=1)
+    if stats_total.get("convfuse_steps", 0) > 0:
+        geom = dict(geom, conv_fuse=1)
     per = per_step_bytes(helm_iters=stats_total["total_helm_iters"] / steps, pres_iters=stats_total["total_pres_iters"] / steps, **geom)
     return nsteps * sum(per.values()), per
