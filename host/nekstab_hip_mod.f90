@@ -440,6 +440,48 @@ module nekstab_hip
       type(c_ptr), value :: A
       type(c_ptr), value :: B
     end function
+    ! eigenmode post-processing on shards (uparam(1) = 4.x under the element decomposition): every vector argument is a
+    ! type(c_ptr) array of n handles, rank r's at (r + 1); parts / prod: c_null_ptr or c_loc of a rank-major type(c_ptr) array
+    ! (4 n / ndim n handles); diss: c_null_ptr or c_loc of n handles; gamma_delta(2), integrals(10): sums over all ranks
+    integer(c_int) function nsk_group_biorthogonalize(shards, n, dRe, dIm, aRe, aIm, gamma_delta) &
+        bind(c, name='nsk_group_biorthogonalize')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: dRe, dIm, aRe, aIm
+      real(c_double), dimension(*) :: gamma_delta
+    end function
+    integer(c_int) function nsk_group_wavemaker(shards, n, dRe, dIm, aRe, aIm, wm) bind(c, name='nsk_group_wavemaker')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: dRe, dIm, aRe, aIm, wm
+    end function
+    integer(c_int) function nsk_group_bf_sensitivity(shards, n, dRe, dIm, aRe, aIm, sr, si, parts) &
+        bind(c, name='nsk_group_bf_sensitivity')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: dRe, dIm, aRe, aIm, sr, si
+      type(c_ptr), value :: parts
+    end function
+    integer(c_int) function nsk_group_energy_budget(shards, n, ub, dRe, dIm, prod, diss, integrals) &
+        bind(c, name='nsk_group_energy_budget')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: ub, dRe, dIm
+      type(c_ptr), value :: prod
+      type(c_ptr), value :: diss
+      real(c_double), dimension(*) :: integrals
+    end function
+    integer(c_int) function nsk_group_forced_map(shards, n, mode, f, q, force) bind(c, name='nsk_group_forced_map')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      integer(c_int), value :: mode
+      type(c_ptr), dimension(*) :: f, q, force
+    end function
     integer(c_int) function nsk_shard_release_parent(parent) bind(c, name='nsk_shard_release_parent')
       import
       type(c_ptr), value :: parent

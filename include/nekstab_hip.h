@@ -215,8 +215,9 @@ int nsk_basis_gemv(nsk_ctx* ctx, const nsk_vec* Q, int k, const double* y_re,
 int nsk_seed_noise(nsk_ctx* ctx, nsk_vec v);
 
 /* ---- sensitivity post-processing (core/sensitivity.f; uparam(1) = 4.2, 4.3, 4.41 / 4.42) and the energy budget (4.1) ----
- * Single-rank full-mesh contexts, quadrilaterals and hexahedra; shard and rank-local contexts return NSK_EINVAL.
- * Inner products are the bm1s-weighted velocity products of nsk_dot. */
+ * Single-rank full-mesh contexts, quadrilaterals and hexahedra; shard and rank-local contexts return NSK_EINVAL here and take
+ * the nsk_group_* twins declared behind the sharding entries below (same fields, same files, under the element decomposition of
+ * every other entry).  Inner products are the bm1s-weighted velocity products of nsk_dot. */
 /* biorthogonalize (core/sensitivity.f:428-504), in place: d <- d / ||d|| (||d||^2 = ||dRe||^2 + ||dIm||^2; the whole vector is
  * scaled), then with <a, d> = gamma + i delta: a <- a / (gamma - i delta), so that <a, d> = 1 afterwards.  gamma_delta (optional)
  * receives {gamma, delta}. */
@@ -340,6 +341,27 @@ int nsk_group_set_orbit(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, n
 int nsk_group_set_orbit_fourier(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, int nmodes, nsk_vec* end, double* amp);
 int nsk_group_set_orbit_modes(nsk_ctx** shards, int n, int nmodes, double period, const nsk_vec* A, const nsk_vec* B);
 int nsk_group_get_orbit_modes(nsk_ctx** shards, int n, int* nmodes, double* period, nsk_vec* A, nsk_vec* B);
+/* Eigenmode post-processing on shards (uparam(1) = 4.0 / 4.1 / 4.2 / 4.3 / 4.41 / 4.42 under the element decomposition): the
+ * twins of nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity, nsk_energy_budget and nsk_forced_map for the ranks living in
+ * this process -- same argument checks, NULL rules and outputs, every vector argument an array of n handles (rank r's at [r];
+ * n = 1 with a transport attached: one process per GPU).  Shards of full-mesh and of rank-local parents alike, before and after
+ * nsk_shard_release_parent (every shard keeps the GLL coordinates of its own elements); other contexts: NSK_EINVAL ("needs
+ * shard contexts").
+ *   parts: NULL or 4 n handles, RANK-MAJOR: parts[4 r + k], k = tr, ti, pr, pi;  prod: NULL or ndim n handles, prod[ndim r + c]
+ *   (the layout of nsk_group_set_orbit_modes);  diss: NULL or n handles.
+ *   gamma_delta, integrals[10] and the norms inside biorthogonalize / energy_budget are sums over ALL ranks: every rank reduces
+ *   on the device in a fixed order, the ranks are added in rank order (virtual ranks) or by the transport's all-reduce; every
+ *   rank receives the same values and two calls on virtual ranks give the same bits.
+ *   Averaging over shared nodes (dsavg) exchanges halos: nsk_group_bf_sensitivity makes 4 ndim exchanges of ndim components,
+ *   nsk_group_energy_budget two per mode component (ndim components, then 1); the production terms are element-local.
+ *   nsk_group_forced_map: NSK_DIRECT / NSK_ADJOINT, force[r] != f[r] on every rank; eager sharded steps -- the captured step
+ *   graphs and the launch budgets of the unforced maps are neither used nor changed; force = 0 gives the bits of the eager
+ *   nsk_group_matvec. */
+int nsk_group_biorthogonalize(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, double* gamma_delta);
+int nsk_group_wavemaker(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* wm);
+int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* sr, nsk_vec* si, nsk_vec* parts);
+int nsk_group_energy_budget(nsk_ctx** shards, int n, nsk_vec* ub, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* prod, nsk_vec* diss, double* integrals);
+int nsk_group_forced_map(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec* q, nsk_vec* force);
 /* Once a process has cut its shard(s): free every device array of the parent that shards do not share (element-major geometry,
  * preconditioner factors, state, work arrays and ALL vectors allocated on the parent -- their handles become invalid).  The 1-D
  * bases and the replicated coarse operator stay.  The parent then only answers nsk_info / nsk_get_stats / nsk_finalize

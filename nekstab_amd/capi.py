@@ -104,6 +104,11 @@ SYMBOLS = {
     "nsk_group_set_orbit_fourier": (C.c_int, [_vpp, C.c_int, _vpp, C.c_double, C.c_int, _vpp, _dp]),
     "nsk_group_set_orbit_modes": (C.c_int, [_vpp, C.c_int, C.c_int, C.c_double, _vpp, _vpp]),
     "nsk_group_get_orbit_modes": (C.c_int, [_vpp, C.c_int, _ip, _dp, _vpp, _vpp]),
+    "nsk_group_biorthogonalize": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, _vpp, _dp]),
+    "nsk_group_wavemaker": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, _vpp, _vpp]),
+    "nsk_group_bf_sensitivity": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, _vpp, _vpp, _vpp, _vpp]),
+    "nsk_group_energy_budget": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, _vpp, _vpp, _dp]),
+    "nsk_group_forced_map": (C.c_int, [_vpp, C.c_int, C.c_int, _vpp, _vpp, _vpp]),
     "nsk_comm_init_host": (C.c_int, [_vp, _vp, _vp, _vp]),
     "nsk_shard_release_parent": (C.c_int, [_vp]),
     "nsk_comm_unique_id": (C.c_int, [_vp]),

@@ -191,7 +191,7 @@ struct nsk_ctx {
   double* scratch = nullptr;            // one state vector
   const double* xyz = nullptr;          // GLL coordinates [ndim][nloc] (nsk_seed_noise)
   const double* force = nullptr;        // steady body force [ndim][nloc] of the running forced map (nsk_forced_map; eager steps only), else null
-  double* budget_wrk = nullptr;         // nsk_energy_budget: divergence field [nloc], per-workgroup partials, 10 sums (first call; freed with the context)
+  double* budget_wrk = nullptr;         // nsk_energy_budget: divergence field [nloc; shards: cs], per-workgroup partials, 10 sums (first call; freed with the context)
   double* rc_big = nullptr;             // coarse restriction for nvert > 3072
   Dev d{};
   Stats hstats{};
@@ -3437,7 +3437,7 @@ int nsk_seed_noise(nsk_ctx* c, nsk_vec v) {
 static int sens_ctx_ok(nsk_ctx* c, const char* who) {
   if (!c) return fail(NSK_EINVAL, std::string(who) + ": bad argument");
   if (c->parent || c->local || c->released || c->d.nranks > 1)
-    return fail(NSK_EINVAL, std::string(who) + ": single-rank full-mesh contexts only (sharded sensitivity is not supported)");
+    return fail(NSK_EINVAL, std::string(who) + ": single-rank full-mesh contexts only (shards: use nsk_group_" + std::string(who).substr(4) + ")");
   return 0;
 }
 
@@ -3484,6 +3484,21 @@ int nsk_wavemaker(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm
   return 0;
 }
 
+// element-local gradient of the velocity-mesh field f into g (ndim fields of component stride gs): k_sens_grad of the context's lx1
+static int sens_grad(nsk_ctx* c, const double* f, double* g, long long gs) {
+  switch (c->key) {
+    case 6: nsk::sens::launch_sens_grad<6, 2>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
+    case 8: nsk::sens::launch_sens_grad<8, 2>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
+    case 10: nsk::sens::launch_sens_grad<10, 2>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
+    case 12: nsk::sens::launch_sens_grad<12, 2>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
+    case 106: nsk::sens::launch_sens_grad<6, 3>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
+    case 108: nsk::sens::launch_sens_grad<8, 3>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
+    case 110: nsk::sens::launch_sens_grad<10, 3>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
+    default: return fail(NSK_EINVAL, "unsupported lx1");
+  }
+  return 0;
+}
+
 int nsk_bf_sensitivity(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec sr, nsk_vec si, nsk_vec* parts) {
   int rc = sens_ctx_ok(c, "nsk_bf_sensitivity");
   if (rc) return rc;
@@ -3513,20 +3528,11 @@ int nsk_bf_sensitivity(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_ve
   for (int kind = 0; kind < 4; ++kind)
     for (int comp = 0; comp < c->ndim; ++comp) {
       const double* f = m[kind] + (size_t)comp * c->nloc;
-      switch (c->key) {
-        case 6: nsk::sens::launch_sens_grad<6, 2>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
-        case 8: nsk::sens::launch_sens_grad<8, 2>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
-        case 10: nsk::sens::launch_sens_grad<10, 2>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
-        case 12: nsk::sens::launch_sens_grad<12, 2>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
-        case 106: nsk::sens::launch_sens_grad<6, 3>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
-        case 108: nsk::sens::launch_sens_grad<8, 3>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
-        case 110: nsk::sens::launch_sens_grad<10, 3>(c->stream, c->nel, c->d.D, c->xyz, f, c->scratch, c->nloc); break;
-        default: return fail(NSK_EINVAL, "unsupported lx1");
-      }
+      if ((rc = sens_grad(c, f, c->scratch, c->nloc))) return rc;
       nsk::sens::SensAcc a = acc[kind];
       a.comp = comp;
-      if (c->ndim == 2) hipLaunchKernelGGL(nsk::sens::k_sens_acc<2>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, a);
-      else hipLaunchKernelGGL(nsk::sens::k_sens_acc<3>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, a);
+      if (c->ndim == 2) hipLaunchKernelGGL(nsk::sens::k_sens_acc<2>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, c->nloc, a);
+      else hipLaunchKernelGGL(nsk::sens::k_sens_acc<3>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, c->nloc, a);
     }
   if (parts) {
     const long long nv = (long long)c->ndim * c->nloc;
@@ -3556,9 +3562,9 @@ static void energy_budget_launch(nsk_ctx* c, const double* ub, const double* uR,
   const double wd = 0.5 * c->d.nu * s;                           // param(2) / param(1) = 1 / Re
   for (int k = 0; k < 2 * NDIM; ++k) {                           // u_R,x  u_I,x  u_R,y  u_I,y [ u_R,z  u_I,z ]
     const double* a = ((k & 1) ? uI : uR) + (size_t)(k >> 1) * n;
-    nsk::sens::launch_sens_grad<N, NDIM>(c->stream, c->nel, c->d.D, c->xyz, a, c->scratch, n);
+    nsk::sens::launch_sens_grad<N, NDIM>(c->stream, c->nel, c->d.D, c->xyz, a, c->scratch, n, n);
     hipLaunchKernelGGL((nsk::sens::k_budget_div<N, NDIM>), dim3(c->nel), dim3(nsk::sens::SensCfg<N, NDIM>::NT), 0, c->stream, c->d,
-                       c->xyz, (const double*)c->scratch, div);
+                       c->xyz, (const double*)c->scratch, n, div);
     hipLaunchKernelGGL(nsk::sens::k_budget_diss, dim3(nb), dim3(256), 0, c->stream, c->d, (const double*)div, a, diss, wd, k == 0 ? 1 : 0,
                        dpart + (size_t)k * nb);
   }
@@ -3624,6 +3630,293 @@ int nsk_forced_map(nsk_ctx* c, int mode, nsk_vec fv, nsk_vec qv, nsk_vec force) 
   rc = run_map_adaptive(c, mode, (double*)fv, (const double*)qv);
   c->use_graph = use_graph;
   c->force = nullptr;
+  return rc;
+}
+
+// ---- the same post-processing on element shards, for the ranks living in this process (uparam(1) = 4.x under the MPI
+// decomposition of everything else).  n shards together, every vector argument an array of n handles (rank r's at [r]); n = 1
+// with a host or RCCL transport attached: one process per GPU.  dsavg on a shard: the field at component stride Dev::cs
+// (ghost slots behind its nloc entries), halo exchange (xchg_vel_at), gather, times the shard's minv (sliced from the parent:
+// the global multiplicity).  The exchanged work array is nsk_ctx::wv1 (ndim * cs doubles; the kernel-test hooks' buffer,
+// which no map reads or writes), so a map that follows finds its own work arrays as the last map left them.
+static int sens_group_ok(nsk_ctx** shards, int n, const char* who) {
+  if (!shards || n < 1 || n > 16) return fail(NSK_EINVAL, std::string(who) + ": bad argument");
+  for (int r = 0; r < n; ++r) {
+    if (!shards[r]) return fail(NSK_EINVAL, std::string(who) + ": bad argument");
+    if (!shards[r]->parent) return fail(NSK_EINVAL, std::string(who) + ": needs shard contexts");
+    if (shards[r]->key != shards[0]->key) return fail(NSK_EINVAL, std::string(who) + ": the shards differ in lx1");
+  }
+  return 0;
+}
+// out[k] = sum over ALL ranks of the m per-rank values vals[r * m + k]: rank order for the ranks of this process, the
+// transport's all-reduce between processes -- every rank receives the same values
+static int group_sum(std::vector<nsk_ctx*>& G, const double* vals, int m, double* out) {
+  for (int k = 0; k < m; ++k) {
+    double t = 0.0;
+    for (size_t r = 0; r < G.size(); ++r) t += vals[r * m + k];
+    out[k] = t;
+  }
+  if (G.size() == 1 && (G[0]->comm || G[0]->host_allred)) return nsk_allreduce_host(G[0], out, m);
+  return 0;
+}
+// the nq inner products (p_k, q_k) over all ranks (each rank: k_dots + k_reduce_final, fixed order)
+static int group_dots(std::vector<nsk_ctx*>& G, int nq, const nsk_vec* const* p, const nsk_vec* const* q, double* out) {
+  std::vector<double> loc(G.size() * (size_t)nq, 0.0);
+  for (size_t r = 0; r < G.size(); ++r)
+    for (int k = 0; k < nq; ++k) { int rc = nsk_dot(G[r], p[k][r], q[k][r], &loc[r * nq + k]); if (rc) return rc; }
+  return group_sum(G, loc.data(), nq, out);
+}
+
+int nsk_group_biorthogonalize(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, double* gamma_delta) {
+  int rc = sens_group_ok(shards, n, "nsk_group_biorthogonalize");
+  if (rc) return rc;
+  if (!dRe || !dIm || !aRe || !aIm) return fail(NSK_EINVAL, "nsk_group_biorthogonalize: four distinct vectors needed");
+  for (int r = 0; r < n; ++r)
+    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !distinct({dRe[r], dIm[r], aRe[r], aIm[r]}))
+      return fail(NSK_EINVAL, "nsk_group_biorthogonalize: four distinct vectors needed");
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  double nn[2];
+  { const nsk_vec* p[2] = {dRe, dIm}; if ((rc = group_dots(G, 2, p, p, nn))) return rc; }
+  if (!(nn[0] + nn[1] > 0.0)) return fail(NSK_EINVAL, "nsk_group_biorthogonalize: the direct mode is zero");
+  const double s = 1.0 / std::sqrt(nn[0] + nn[1]);
+  for (int r = 0; r < n; ++r) if ((rc = nsk_scal(G[r], dRe[r], s)) || (rc = nsk_scal(G[r], dIm[r], s))) return rc;
+  double v[4];                                                   // rr, ii, ri, ir
+  { const nsk_vec* p[4] = {aRe, aIm, aRe, aIm}; const nsk_vec* q[4] = {dRe, dIm, dIm, dRe}; if ((rc = group_dots(G, 4, p, q, v))) return rc; }
+  const double gamma = v[0] + v[1], delta = v[2] - v[3], den = gamma * gamma + delta * delta;
+  if (!(den > 0.0)) return fail(NSK_EINVAL, "nsk_group_biorthogonalize: the adjoint mode is orthogonal to the direct mode");
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    hipLaunchKernelGGL(nsk::sens::k_cdiv, dim3((unsigned)((c->nstate + 255) / 256)), dim3(256), 0, c->stream, (double*)aRe[r], (double*)aIm[r],
+                       gamma / den, delta / den, c->nstate);
+  }
+  HIPCHK(hipGetLastError());
+  if (gamma_delta) { gamma_delta[0] = gamma; gamma_delta[1] = delta; }
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int nsk_group_wavemaker(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* wm) {
+  int rc = sens_group_ok(shards, n, "nsk_group_wavemaker");
+  if (rc) return rc;
+  if (!dRe || !dIm || !aRe || !aIm || !wm) return fail(NSK_EINVAL, "nsk_group_wavemaker: bad argument");
+  for (int r = 0; r < n; ++r) {
+    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !wm[r]) return fail(NSK_EINVAL, "nsk_group_wavemaker: bad argument");
+    if (wm[r] == dRe[r] || wm[r] == dIm[r] || wm[r] == aRe[r] || wm[r] == aIm[r])
+      return fail(NSK_EINVAL, "nsk_group_wavemaker: the output may not be one of the modes");
+  }
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = shards[r];
+    HIPCHK(hipMemsetAsync(wm[r], 0, c->nstate * sizeof(double), c->stream));
+    hipLaunchKernelGGL(nsk::sens::k_wavemaker, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream, (const double*)dRe[r],
+                       (const double*)dIm[r], (const double*)aRe[r], (const double*)aIm[r], (double*)wm[r], c->nloc, c->ndim);
+  }
+  HIPCHK(hipGetLastError());
+  for (int r = 0; r < n; ++r) HIPCHK(hipStreamSynchronize(shards[r]->stream));
+  return 0;
+}
+
+// parts: NULL or 4 n handles, rank-major (parts[4 r + k], k = tr, ti, pr, pi).  4 ndim halo exchanges of ndim components each.
+int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* sr, nsk_vec* si, nsk_vec* parts) {
+  int rc = sens_group_ok(shards, n, "nsk_group_bf_sensitivity");
+  if (rc) return rc;
+  if (!dRe || !dIm || !aRe || !aIm || !sr || !si) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: bad argument");
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  const int nd = G[0]->ndim;
+  for (int r = 0; r < n; ++r) {
+    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !sr[r] || !si[r]) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: bad argument");
+    const nsk_vec* pr = parts ? parts + 4 * r : nullptr;
+    if (pr && (!pr[0] || !pr[1] || !pr[2] || !pr[3])) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: parts needs four vectors per rank");
+    if (!G[r]->xyz || !G[r]->wv1) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: context holds no coordinates");
+    std::vector<const void*> all = {dRe[r], dIm[r], aRe[r], aIm[r], sr[r], si[r]};
+    if (pr) all.insert(all.end(), pr, pr + 4);
+    if (!distinct(all)) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: inputs and outputs must be distinct vectors");
+  }
+  struct Rank { double* outs[6]; double *tR, *tI, *pR, *pI; const double* m[4]; };
+  std::vector<Rank> R(n);
+  double* base[16];
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    Rank& k = R[r];
+    const nsk_vec* pr = parts ? parts + 4 * r : nullptr;
+    k.outs[0] = (double*)sr[r]; k.outs[1] = (double*)si[r];
+    for (int q = 0; q < 4; ++q) k.outs[2 + q] = pr ? (double*)pr[q] : nullptr;
+    for (double* o : k.outs) if (o) HIPCHK(hipMemsetAsync(o, 0, c->nstate * sizeof(double), c->stream));
+    k.tR = pr ? k.outs[2] : k.outs[0]; k.tI = pr ? k.outs[3] : k.outs[1];
+    k.pR = pr ? k.outs[4] : k.outs[0]; k.pI = pr ? k.outs[5] : k.outs[1];
+    k.m[0] = (const double*)dRe[r]; k.m[1] = (const double*)dIm[r]; k.m[2] = (const double*)aRe[r]; k.m[3] = (const double*)aIm[r];
+    base[r] = c->wv1;
+  }
+  // kinds, weights and term order: nsk_bf_sensitivity
+  for (int kind = 0; kind < 4; ++kind)
+    for (int comp = 0; comp < nd; ++comp) {
+      for (int r = 0; r < n; ++r)
+        if ((rc = sens_grad(G[r], R[r].m[kind] + (size_t)comp * G[r]->nloc, G[r]->wv1, G[r]->d.cs))) return rc;
+      if ((rc = xchg_vel_at(G, base, nd))) return rc;
+      for (int r = 0; r < n; ++r) {
+        nsk_ctx* c = G[r];
+        const Rank& k = R[r];
+        const nsk::sens::SensAcc acc[4] = {
+            {k.m[2], k.m[3], k.tR, k.tI, -1.0, -1.0, comp, 0},
+            {k.m[3], k.m[2], k.tR, k.tI, -1.0, 1.0, comp, 0},
+            {k.m[0], k.m[1], k.pR, k.pI, 1.0, -1.0, comp, 1},
+            {k.m[1], k.m[0], k.pR, k.pI, 1.0, 1.0, comp, 1}};
+        const unsigned grid = (unsigned)((c->nloc + 255) / 256);
+        if (nd == 2) hipLaunchKernelGGL(nsk::sens::k_sens_acc<2>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->wv1, c->d.cs, acc[kind]);
+        else hipLaunchKernelGGL(nsk::sens::k_sens_acc<3>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->wv1, c->d.cs, acc[kind]);
+      }
+    }
+  if (parts)
+    for (int r = 0; r < n; ++r) {
+      nsk_ctx* c = G[r];
+      const long long nv = (long long)nd * c->nloc;
+      const unsigned gv = (unsigned)((nv + 255) / 256);
+      hipLaunchKernelGGL(nsk::sens::k_add3, dim3(gv), dim3(256), 0, c->stream, R[r].outs[0], (const double*)R[r].tR, (const double*)R[r].pR, nv);
+      hipLaunchKernelGGL(nsk::sens::k_add3, dim3(gv), dim3(256), 0, c->stream, R[r].outs[1], (const double*)R[r].tI, (const double*)R[r].pI, nv);
+    }
+  HIPCHK(hipGetLastError());
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// budget workspace of a shard: divergence field [cs] (ghost slots: it is averaged a second time), [9][nel] production partials,
+// [2 ndim][ceil(nloc / 256)] dissipation partials, 10 sums
+static size_t budget_wrk_size(const nsk_ctx* c) {
+  const long long nb = (c->nloc + 255) / 256;
+  return (size_t)(c->d.cs + 9LL * c->nel + 2LL * c->ndim * nb + 10);
+}
+extern "C++" {
+// nsk_energy_budget's launches on the ranks of G: 2 halo exchanges per mode component (ndim gradient components, then the
+// divergence); the production terms are element-local.  ub, uR, uI, prod (rank-major, may be null), diss (entries may be null) per rank.
+template <int N, int NDIM>
+static int energy_budget_group_launch(std::vector<nsk_ctx*>& G, const nsk_vec* ub, const nsk_vec* uR, const nsk_vec* uI, const nsk_vec* prod,
+                                      const nsk_vec* diss, double s) {
+  const int n = (int)G.size();
+  double *gbase[16], *dbase[16];
+  int rc;
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    double* ppart = c->budget_wrk + c->d.cs;
+    const nsk_vec* pr = prod ? prod + (size_t)NDIM * r : nullptr;
+    nsk::sens::BudgetProd bp{{pr ? (double*)pr[0] : nullptr, pr ? (double*)pr[1] : nullptr, pr && NDIM == 3 ? (double*)pr[NDIM - 1] : nullptr}};
+    hipLaunchKernelGGL((nsk::sens::k_budget_prod<N, NDIM>), dim3(c->nel), dim3(nsk::sens::SensCfg<N, NDIM>::NT), 0, c->stream, c->d.D,
+                       c->xyz, (const double*)ub[r], (const double*)uR[r], (const double*)uI[r], c->d.bm1, bp, -0.5 * s, ppart, c->nloc);
+    gbase[r] = c->wv1; dbase[r] = c->budget_wrk;
+  }
+  for (int k = 0; k < 2 * NDIM; ++k) {                           // u_R,x  u_I,x  u_R,y  u_I,y [ u_R,z  u_I,z ]
+    for (int r = 0; r < n; ++r) {
+      nsk_ctx* c = G[r];
+      const double* a = (const double*)((k & 1) ? uI[r] : uR[r]) + (size_t)(k >> 1) * c->nloc;
+      nsk::sens::launch_sens_grad<N, NDIM>(c->stream, c->nel, c->d.D, c->xyz, a, c->wv1, c->nloc, c->d.cs);
+    }
+    if ((rc = xchg_vel_at(G, gbase, NDIM))) return rc;
+    for (nsk_ctx* c : G)
+      hipLaunchKernelGGL((nsk::sens::k_budget_div<N, NDIM>), dim3(c->nel), dim3(nsk::sens::SensCfg<N, NDIM>::NT), 0, c->stream, c->d,
+                         c->xyz, (const double*)c->wv1, c->d.cs, c->budget_wrk);
+    if ((rc = xchg_vel_at(G, dbase, 1))) return rc;
+    for (int r = 0; r < n; ++r) {
+      nsk_ctx* c = G[r];
+      const int nb = (int)((c->nloc + 255) / 256);
+      const double* a = (const double*)((k & 1) ? uI[r] : uR[r]) + (size_t)(k >> 1) * c->nloc;
+      double* dpart = c->budget_wrk + c->d.cs + 9 * (size_t)c->nel;
+      hipLaunchKernelGGL(nsk::sens::k_budget_diss, dim3(nb), dim3(256), 0, c->stream, c->d, (const double*)c->budget_wrk, a,
+                         diss ? (double*)diss[r] : nullptr, 0.5 * c->d.nu * s, k == 0 ? 1 : 0, dpart + (size_t)k * nb);
+    }
+  }
+  for (nsk_ctx* c : G) {
+    const int nb = (int)((c->nloc + 255) / 256);
+    double* ppart = c->budget_wrk + c->d.cs;
+    double* dpart = ppart + 9 * (size_t)c->nel;
+    double* out = dpart + 2 * NDIM * (size_t)nb;
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)ppart, 9, c->nel, out);
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)dpart, 1, 2 * NDIM * nb, out + 9);
+  }
+  return 0;
+}
+}  // extern "C++"
+
+// prod: NULL or ndim n handles, rank-major (prod[ndim r + c]); diss: NULL or n handles.  integrals[10]: sums over all ranks.
+int nsk_group_energy_budget(nsk_ctx** shards, int n, nsk_vec* ub, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* prod, nsk_vec* diss, double* integrals) {
+  int rc = sens_group_ok(shards, n, "nsk_group_energy_budget");
+  if (rc) return rc;
+  if (!ub || !dRe || !dIm || !integrals) return fail(NSK_EINVAL, "nsk_group_energy_budget: bad argument (ub, dRe, dIm and integrals are required)");
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  const int nd = G[0]->ndim, key = G[0]->key;
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    if (!ub[r] || !dRe[r] || !dIm[r]) return fail(NSK_EINVAL, "nsk_group_energy_budget: bad argument (ub, dRe, dIm and integrals are required)");
+    if (prod) for (int k = 0; k < nd; ++k) if (!prod[(size_t)nd * r + k]) return fail(NSK_EINVAL, "nsk_group_energy_budget: prod needs ndim vectors per rank");
+    if (diss && !diss[r]) return fail(NSK_EINVAL, "nsk_group_energy_budget: diss needs one vector per rank");
+    if (!c->xyz || !c->wv1) return fail(NSK_EINVAL, "nsk_group_energy_budget: context holds no coordinates");
+    std::vector<const void*> outs;
+    if (prod) outs.insert(outs.end(), prod + (size_t)nd * r, prod + (size_t)nd * (r + 1));
+    if (diss) outs.push_back(diss[r]);
+    for (const void* o : outs)
+      if (o == ub[r] || o == dRe[r] || o == dIm[r]) return fail(NSK_EINVAL, "nsk_group_energy_budget: an output may not be one of the inputs");
+    if (!distinct(outs)) return fail(NSK_EINVAL, "nsk_group_energy_budget: the outputs must be distinct vectors");
+  }
+  if (key != 6 && key != 8 && key != 10 && key != 12 && key != 106 && key != 108 && key != 110)
+    return fail(NSK_EINVAL, "nsk_group_energy_budget: unsupported lx1");
+  double nn[2];                                                  // alpha^2 over all ranks
+  { const nsk_vec* p[2] = {dRe, dIm}; if ((rc = group_dots(G, 2, p, p, nn))) return rc; }
+  if (!(nn[0] + nn[1] > 0.0)) return fail(NSK_EINVAL, "nsk_group_energy_budget: the direct mode is zero");
+  const double s = 1.0 / (nn[0] + nn[1]);
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    if (!c->budget_wrk && (rc = dalloc(c, &c->budget_wrk, budget_wrk_size(c)))) return rc;
+    const long long nv = (long long)nd * c->nloc;
+    if (prod) for (int k = 0; k < nd; ++k) HIPCHK(hipMemsetAsync((double*)prod[(size_t)nd * r + k] + nv, 0, (c->nstate - nv) * sizeof(double), c->stream));
+    if (diss) HIPCHK(hipMemsetAsync((double*)diss[r] + c->nloc, 0, (c->nstate - c->nloc) * sizeof(double), c->stream));
+  }
+  switch (key) {
+    case 6: rc = energy_budget_group_launch<6, 2>(G, ub, dRe, dIm, prod, diss, s); break;
+    case 8: rc = energy_budget_group_launch<8, 2>(G, ub, dRe, dIm, prod, diss, s); break;
+    case 10: rc = energy_budget_group_launch<10, 2>(G, ub, dRe, dIm, prod, diss, s); break;
+    case 12: rc = energy_budget_group_launch<12, 2>(G, ub, dRe, dIm, prod, diss, s); break;
+    case 106: rc = energy_budget_group_launch<6, 3>(G, ub, dRe, dIm, prod, diss, s); break;
+    case 108: rc = energy_budget_group_launch<8, 3>(G, ub, dRe, dIm, prod, diss, s); break;
+    default: rc = energy_budget_group_launch<10, 3>(G, ub, dRe, dIm, prod, diss, s); break;
+  }
+  if (rc) return rc;
+  HIPCHK(hipGetLastError());
+  std::vector<double> loc((size_t)10 * n);
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    const double* out = c->budget_wrk + budget_wrk_size(c) - 10;
+    HIPCHK(hipMemcpyAsync(&loc[(size_t)10 * r], out, 10 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  return group_sum(G, loc.data(), 10, integrals);
+}
+
+// nsk_forced_map on shards: eager sharded steps with k_add_force behind the convection kernel of every rank (group_step).  The
+// captured sharded step graphs and the launch budgets belong to the unforced maps: neither is touched.
+int nsk_group_forced_map(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec* q, nsk_vec* force) {
+  int rc = sens_group_ok(shards, n, "nsk_group_forced_map");
+  if (rc) return rc;
+  if (!f || !q || !force) return fail(NSK_EINVAL, "nsk_group_forced_map: bad argument");
+  if (mode != NSK_DIRECT && mode != NSK_ADJOINT) return fail(NSK_EINVAL, "nsk_group_forced_map: mode must be NSK_DIRECT or NSK_ADJOINT");
+  for (int r = 0; r < n; ++r) {
+    if (!f[r] || !q[r] || !force[r]) return fail(NSK_EINVAL, "nsk_group_forced_map: bad argument");
+    if (force[r] == f[r]) return fail(NSK_EINVAL, "nsk_group_forced_map: the force may not be the output vector");
+  }
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  struct Keep { int use_graph, freeze, helm[NCLS], pres[NCLS]; };
+  std::vector<Keep> keep(n);
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    keep[r].use_graph = c->use_graph; keep[r].freeze = c->budget_freeze;
+    for (int k = 0; k < NCLS; ++k) { keep[r].helm[k] = c->cur_helm[k]; keep[r].pres[k] = c->cur_pres[k]; }
+    c->force = (const double*)force[r];
+    c->use_graph = 0;                                            // group_graph_ok: eager
+    c->budget_freeze = 1;                                        // (a forced map that outgrows the budgets doubles them for its redo; put back below)
+  }
+  rc = group_run_map(G, mode == NSK_ADJOINT ? 1 : 0, (double* const*)f, (const double* const*)q);
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    c->force = nullptr;
+    c->use_graph = keep[r].use_graph; c->budget_freeze = keep[r].freeze;
+    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
+  }
   return rc;
 }
 

@@ -7,6 +7,8 @@
 // the metrics derived in the kernel from the GLL coordinates), k_sens_acc averages it over shared nodes (dsavg through the
 // gather tables of the dssum) and adds its products with the other modes' values into the outputs.  Scratch: ndim
 // velocity-sized fields (the context's state-sized scratch vector); nothing is kept between calls.
+// On an element shard (nsk_group_* entries) the gradient fields carry ghost slots behind their nloc entries (component stride
+// Dev::cs) and are exchanged between k_sens_grad and the gathering kernel; the kernels take that stride as an argument.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,11 +24,14 @@ struct SensCfg {
   static constexpr int NT = ((NP + 63) / 64) * 64;
 };
 
-// g[i * nloc + l] = d f / d x_i at the element-local node l (no averaging): (r_x f_r + s_x f_s [+ t_x f_t]) with the
+// g[i * gs + l] = d f / d x_i at the element-local node l (no averaging): (r_x f_r + s_x f_s [+ t_x f_t]) with the
 // inverse mapping from the coordinates' own derivatives (Nek5000 gradm1: cofactors over the Jacobian).  One workgroup per element.
+// gs: component stride of g -- nloc on a full-mesh context, nloc + ghost slots (Dev::cs) on a shard, whose gradient is
+// exchanged (k_halo_pack / k_halo_unpack fill g[i * gs + nloc ..]) before it is gathered.
 template <int N, int NDIM>
 __global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_sens_grad(const double* __restrict__ D, const double* __restrict__ xyz,
-                                                                    const double* __restrict__ f, double* __restrict__ g, long long nloc) {
+                                                                    const double* __restrict__ f, double* __restrict__ g, long long nloc,
+                                                                    long long gs) {
   constexpr int NP = SensCfg<N, NDIM>::NP;
   __shared__ double sD[N * N];
   __shared__ double sf[NP], sx[NP], sy[NP], sz[NDIM == 3 ? NP : 1];
@@ -61,27 +66,30 @@ __global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_sens_grad(const doub
   if constexpr (NDIM == 2) {
     const double jinv = 1.0 / (xr * ys - xs * yr);
     g[l] = (ys * fr - yr * fs) * jinv;                      // r_x = y_s / J, s_x = -y_r / J
-    g[nloc + l] = (xr * fs - xs * fr) * jinv;               // r_y = -x_s / J, s_y = x_r / J
+    g[gs + l] = (xr * fs - xs * fr) * jinv;                 // r_y = -x_s / J, s_y = x_r / J
   } else {
     const double c_rx = ys * zt - yt * zs, c_ry = xt * zs - xs * zt, c_rz = xs * yt - xt * ys;
     const double c_sx = yt * zr - yr * zt, c_sy = xr * zt - xt * zr, c_sz = xt * yr - xr * yt;
     const double c_tx = yr * zs - ys * zr, c_ty = xs * zr - xr * zs, c_tz = xr * ys - xs * yr;
     const double jinv = 1.0 / (xr * c_rx + yr * c_ry + zr * c_rz);
     g[l] = (c_rx * fr + c_sx * fs + c_tx * ft) * jinv;
-    g[nloc + l] = (c_ry * fr + c_sy * fs + c_ty * ft) * jinv;
-    g[2 * nloc + l] = (c_rz * fr + c_sz * fs + c_tz * ft) * jinv;
+    g[gs + l] = (c_ry * fr + c_sy * fs + c_ty * ft) * jinv;
+    g[2 * gs + l] = (c_rz * fr + c_sz * fs + c_tz * ft) * jinv;
   }
 }
 
 template <int N, int NDIM>
-inline void launch_sens_grad(hipStream_t st, int nel, const double* D, const double* xyz, const double* f, double* g, long long nloc) {
-  hipLaunchKernelGGL((k_sens_grad<N, NDIM>), dim3(nel), dim3(SensCfg<N, NDIM>::NT), 0, st, D, xyz, f, g, nloc);
+inline void launch_sens_grad(hipStream_t st, int nel, const double* D, const double* xyz, const double* f, double* g, long long nloc,
+                             long long gs) {
+  hipLaunchKernelGGL((k_sens_grad<N, NDIM>), dim3(nel), dim3(SensCfg<N, NDIM>::NT), 0, st, D, xyz, f, g, nloc, gs);
 }
 
 // Accumulation of one mode component's averaged gradient G_i = dsavg(g_i) (sensitivity.f:215-256, Marquet et al. 2008):
 //   transport (the mode is direct, component j):      outR_i += wR sR_j G_i,         outI_i += wI sI_j G_i
 //   production (the mode is adjoint, component i):     outR_i += wR sum_j sR_j G_j,   outI_i += wI sum_j sI_j G_j
-// s* are velocity fields with component stride nloc (the other mode's values), out* the output vectors.
+// s* are velocity fields with component stride nloc (the other mode's values), out* the output vectors; g has component
+// stride gs (as k_sens_grad wrote it; on a shard its ghost slots hold the peers' partial sums and Dev::minv is the global
+// multiplicity, so the gather below is the dsavg over ALL ranks).
 struct SensAcc {
   const double *sR, *sI;
   double *outR, *outI;
@@ -90,14 +98,14 @@ struct SensAcc {
 };
 
 template <int NDIM>
-__global__ void k_sens_acc(const Dev d, const double* __restrict__ g, const SensAcc a) {
+__global__ void k_sens_acc(const Dev d, const double* __restrict__ g, long long gs, const SensAcc a) {
   const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= d.nloc) return;
   const long long n = d.nloc;
   const double mi = d.minv[l];
   double G[NDIM];
 #pragma unroll
-  for (int q = 0; q < NDIM; ++q) G[q] = gs_gather(g + q * n, d, l) * mi;
+  for (int q = 0; q < NDIM; ++q) G[q] = gs_gather(g + q * gs, d, l) * mi;
   if (!a.production) {
     const double cr = a.wR * a.sR[a.comp * n + l], ci = a.wI * a.sI[a.comp * n + l];
 #pragma unroll
@@ -278,10 +286,12 @@ __global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_budget_prod(const do
   }
 }
 
-// div[l] = sum_i d/dx_i dsavg(g_i) at the element-local node l (g: ndim gradient fields, stride nloc).  One workgroup per element.
+// div[l] = sum_i d/dx_i dsavg(g_i) at the element-local node l (g: ndim gradient fields, stride gs as k_sens_grad wrote them).
+// One workgroup per element.  On a shard div has room for the ghost slots behind its nloc entries: it is averaged again.
 template <int N, int NDIM>
 __global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_budget_div(const Dev d, const double* __restrict__ xyz,
-                                                                     const double* __restrict__ g, double* __restrict__ div) {
+                                                                     const double* __restrict__ g, long long gs,
+                                                                     double* __restrict__ div) {
   constexpr int NP = SensCfg<N, NDIM>::NP;
   __shared__ double sD[N * N];
   __shared__ double sf[NP], sx[NP], sy[NP], sz[NDIM == 3 ? NP : 1];
@@ -297,7 +307,7 @@ __global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_budget_div(const Dev
 #pragma unroll
   for (int a = 0; a < NDIM; ++a) {
     if (a) __syncthreads();
-    if (act) sf[tid] = gs_gather(g + a * nloc, d, l) * mi;
+    if (act) sf[tid] = gs_gather(g + a * gs, d, l) * mi;
     __syncthreads();
     if (!act) continue;
     double fd[NDIM];

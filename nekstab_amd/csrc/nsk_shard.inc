@@ -280,6 +280,10 @@ static int shard_fill(nsk_ctx* c, nsk_ctx* P, const int* part, int rank, int nra
   }
 #undef SL
   if ((rc = slice_rows(pd.dinv, (size_t)P->nloc, 3, NN, &d.dinv))) return rc;
+  // GLL coordinates of the shard's own elements (k_sens_grad / k_budget_prod derive the inverse mapping from them): memory of
+  // the shard, so the post-processing entries outlive nsk_shard_release_parent
+  c->xyz = nullptr;
+  if (P->xyz && (rc = slice_rows(P->xyz, (size_t)P->nloc, nd, NN, &c->xyz))) return rc;
   // coarse: this rank's element corners per *global* vertex
   if (nd == 2) {
     std::vector<int> vtab((size_t)P->nvert * CVT, -1), fill(P->nvert, 0);
@@ -372,11 +376,15 @@ static int hs_allreduce(nsk_ctx* c, double* dbuf, int n) {
 // xs != nullptr: the whole exchange (pack, transport, unpack) runs on that stream instead of the ranks' own (halo / interior
 // overlap: the caller orders it against the compute stream with events)
 // ar / nar: an all-reduce (sum over ranks, in place) that rides in the same RCCL group as the halo messages (fused_allreduce_ok)
-static int xchg_vel(std::vector<nsk_ctx*>& G, double* nsk::Dev::*field, long long extra, int ncomp, hipStream_t xs = nullptr, double* ar = nullptr, int nar = 0) {
+// xchg_vel_at: the field of rank G[r] is base[r] (ncomp <= 4 components of stride Dev::cs, ghost slots behind the nloc entries of
+// each) -- any array of that shape, not only a member of Dev (the post-processing entries exchange their own work arrays)
+static int xchg_vel_at(std::vector<nsk_ctx*>& G, double* const* base, int ncomp, hipStream_t xs = nullptr, double* ar = nullptr, int nar = 0) {
   auto S = [&](nsk_ctx* c) { return xs ? xs : c->stream; };
   // send / receive buffers: [peer][component][entry] (k_halo_pack), so every peer gets ONE contiguous message per exchange
-  for (nsk_ctx* c : G)
-    if (c->nvh) hipLaunchKernelGGL(k_halo_pack, dim3((c->nvh + 255) / 256), dim3(256), 0, S(c), (const double*)(c->d.*field + extra * c->d.cs), c->d.cs, ncomp, c->vh_off, c->vh_idx, c->vh_seg, c->nvh, c->vsend);
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r];
+    if (c->nvh) hipLaunchKernelGGL(k_halo_pack, dim3((c->nvh + 255) / 256), dim3(256), 0, S(c), (const double*)base[r], c->d.cs, ncomp, c->vh_off, c->vh_idx, c->vh_seg, c->nvh, c->vsend);
+  }
   if (G.size() == 1 && G[0]->host_xchg) {                    // host-staged
     nsk_ctx* c = G[0];
     const size_t tot = (size_t)ncomp * c->nvh;
@@ -421,9 +429,17 @@ static int xchg_vel(std::vector<nsk_ctx*>& G, double* nsk::Dev::*field, long lon
                               (size_t)ncomp * c->vh_pcnt[pi] * sizeof(double), hipMemcpyDeviceToDevice, S(c)));
       }
   }
-  for (nsk_ctx* c : G)
-    if (c->nvh) hipLaunchKernelGGL(k_halo_unpack, dim3((c->nvh + 255) / 256), dim3(256), 0, S(c), c->d.*field + extra * c->d.cs, c->d.cs, c->d.nloc, ncomp, c->vh_seg, c->nvh, (const double*)c->vrecv);
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r];
+    if (c->nvh) hipLaunchKernelGGL(k_halo_unpack, dim3((c->nvh + 255) / 256), dim3(256), 0, S(c), base[r], c->d.cs, c->d.nloc, ncomp, c->vh_seg, c->nvh, (const double*)c->vrecv);
+  }
   return 0;
+}
+static int xchg_vel(std::vector<nsk_ctx*>& G, double* nsk::Dev::*field, long long extra, int ncomp, hipStream_t xs = nullptr, double* ar = nullptr, int nar = 0) {
+  double* base[16];                                          // (nranks <= 16: shard_create)
+  if (G.size() > 16) return fail(NSK_EINVAL, "more than 16 ranks in one process");
+  for (size_t r = 0; r < G.size(); ++r) base[r] = G[r]->d.*field + extra * G[r]->d.cs;
+  return xchg_vel_at(G, base, ncomp, xs, ar, nar);
 }
 
 static int xchg_pres(std::vector<nsk_ctx*>& G, int j, hipStream_t xs = nullptr, double* ar = nullptr, int nar = 0) {      // ghost part of the GMRES basis vector V[j]; xs, ar: as xchg_vel
@@ -594,6 +610,8 @@ static int group_step(std::vector<nsk_ctx*>& G, int istep, int adjoint) {
         hipLaunchKernelGGL(nsk::k3::k_convect_mfma_nl<10>, dim3(c->nel), dim3(1024), 0, c->stream, c->d, (const double*)c->d.u, c->d.bf);
       else
         hipLaunchKernelGGL(k_convect<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, c->d, (const double*)c->d.u, c->d.bf, adjoint);
+      if (c->force)                     // forced map (nsk_group_forced_map; eager steps only): + B f of the rank's own elements, as step()
+        hipLaunchKernelGGL(nsk::sens::k_add_force, dim3((unsigned)((c->d.nloc + 255) / 256)), dim3(256), 0, c->stream, c->d.bf, c->d.cs, c->d.bm1, c->force, c->d.nloc, c->ndim);
       hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, c->d, sc);
     }
     if ((rc = xchg_vel(G, &Dev::rloc, 0, nd)) || (rc = xchg_vel(G, &Dev::bloc, 0, nd))) return rc;

@@ -8,7 +8,8 @@
     postprocess                      4.0   energy_budget, wave_maker, bf_sensitivity in the reference's order (core/usr_extra.f)
 
 The fields are computed on the device (nsk_energy_budget, nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity,
-nsk_forced_map); delta_forcing is pointwise and stays on the host.  Output files carry the reference's prefixes (KIN, wm_, tr_,
+nsk_forced_map; on element shards their nsk_group_* twins: every driver below takes a ``sharded.ShardGroup`` in place of the
+single-rank context and writes the same files); delta_forcing is pointwise and stays on the host.  Output files carry the reference's prefixes (KIN, wm_, tr_,
 ti_, pr_, pi_, sr_, si_, fsr, fsi, dfr) so that nekStab's own scripts read them.  ``np_*`` functions are the numpy
 restatement the device is tested against.
 

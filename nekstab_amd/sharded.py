@@ -14,7 +14,7 @@ import os
 
 import numpy as np
 
-from .capi import NekStabHip, NskError, _dp
+from .capi import NSK_ADJOINT, NekStabHip, NskError, _dp
 
 
 def partition_rcb(case, nranks: int) -> np.ndarray:
@@ -204,6 +204,10 @@ class ShardGroup:
         ndim = int(getattr(case, "ndim", 2))
         self.ndim, self.nel, self.lx1, self.lx2 = ndim, case.nel, full.lx1, full.lx2
         self.npres, self.nvel = case.nel * self.lx2 ** ndim, case.nel * self.lx1 ** ndim
+        # whole-mesh GLL coordinates: what the file output of the post-processing drivers (sensitivity._write) reads from its backend
+        self._keep = dict(x=np.asarray(case.x, dtype=np.float64), y=np.asarray(case.y, dtype=np.float64))
+        if ndim == 3:
+            self._keep["z"] = np.asarray(case.z, dtype=np.float64)
         self.elems = [np.where(self.part == r)[0] for r in range(nranks)]
         self.ctx = []
         for r in range(nranks):
@@ -361,6 +365,41 @@ class ShardGroup:
         self._chk(self.lib.nsk_group_get_orbit_modes(self._arr, self.R, C.byref(m), C.byref(per), aa, bb))
         self._refresh_info()
         return m.value, per.value
+
+    # ---- eigenmode post-processing on the shards (nsk_group_biorthogonalize, ..): the signatures of NekStabHip, so that the
+    # drivers of nekstab_amd/sensitivity.py take a ShardGroup as they take a single-rank context
+    def _per_rank(self, v):
+        return (C.c_void_p * self.R)(*[p.value for p in v.parts])
+
+    def biorthogonalize(self, dRe, dIm, aRe, aIm):
+        """In place: ||d|| = 1 and <a, d> = 1 over all ranks.  Returns (gamma, delta), the inner product before."""
+        gd = np.zeros(2)
+        self._chk(self.lib.nsk_group_biorthogonalize(self._arr, self.R, *[self._per_rank(v) for v in (dRe, dIm, aRe, aIm)], gd.ctypes.data_as(_dp)))
+        return float(gd[0]), float(gd[1])
+
+    def wavemaker(self, dRe, dIm, aRe, aIm, wm):
+        self._chk(self.lib.nsk_group_wavemaker(self._arr, self.R, *[self._per_rank(v) for v in (dRe, dIm, aRe, aIm, wm)]))
+
+    def bf_sensitivity(self, dRe, dIm, aRe, aIm, sr, si, parts=None):
+        """sr, si (and the four terms ``parts`` = [tr, ti, pr, pi]) of the base-flow sensitivity; gradients averaged over ALL ranks."""
+        if parts is not None and len(parts) != 4:
+            raise ValueError("bf_sensitivity: parts needs 4 vectors")
+        arr = self._rank_major(parts) if parts is not None else None
+        self._chk(self.lib.nsk_group_bf_sensitivity(self._arr, self.R, *[self._per_rank(v) for v in (dRe, dIm, aRe, aIm, sr, si)], arr))
+
+    def energy_budget(self, ub, dRe, dIm, prod=None, diss=None):
+        """The 10 integrals of the stability energy budget over all ranks; ``prod`` = ndim vectors, ``diss`` = one (optional)."""
+        if prod is not None and len(prod) != self.ndim:
+            raise ValueError("energy_budget: prod needs %d vectors" % self.ndim)
+        out = np.zeros(10)
+        self._chk(self.lib.nsk_group_energy_budget(self._arr, self.R, *[self._per_rank(v) for v in (ub, dRe, dIm)],
+                                                   self._rank_major(prod) if prod is not None else None,
+                                                   self._per_rank(diss) if diss is not None else None, out.ctypes.data_as(_dp)))
+        return out
+
+    def forced_map(self, f, q, force, mode=NSK_ADJOINT):
+        """f = linearised map of q under the steady body force ``force`` (eager sharded steps)."""
+        self._chk(self.lib.nsk_group_forced_map(self._arr, self.R, int(mode), *[self._per_rank(v) for v in (f, q, force)]))
 
     def stats(self):
         from .capi import NskStats
@@ -579,6 +618,37 @@ class ShardRank:
         self._chk(self.lib.nsk_group_get_orbit_modes(self._one, 1, C.byref(m), C.byref(per), aa, bb))
         self._refresh_info()
         return m.value, per.value
+
+    # ---- eigenmode post-processing of this rank's elements (nsk_group_* with n = 1; halos and sums over the transport);
+    # the fields come back through download_local
+    def _one_of(self, *vecs):
+        return [(C.c_void_p * 1)(v.value) for v in vecs]
+
+    def biorthogonalize(self, dRe, dIm, aRe, aIm):
+        gd = np.zeros(2)
+        self._chk(self.lib.nsk_group_biorthogonalize(self._one, 1, *self._one_of(dRe, dIm, aRe, aIm), gd.ctypes.data_as(_dp)))
+        return float(gd[0]), float(gd[1])
+
+    def wavemaker(self, dRe, dIm, aRe, aIm, wm):
+        self._chk(self.lib.nsk_group_wavemaker(self._one, 1, *self._one_of(dRe, dIm, aRe, aIm, wm)))
+
+    def bf_sensitivity(self, dRe, dIm, aRe, aIm, sr, si, parts=None):
+        if parts is not None and len(parts) != 4:
+            raise ValueError("bf_sensitivity: parts needs 4 vectors")
+        arr = (C.c_void_p * 4)(*[v.value for v in parts]) if parts is not None else None
+        self._chk(self.lib.nsk_group_bf_sensitivity(self._one, 1, *self._one_of(dRe, dIm, aRe, aIm, sr, si), arr))
+
+    def energy_budget(self, ub, dRe, dIm, prod=None, diss=None):
+        if prod is not None and len(prod) != self.ndim:
+            raise ValueError("energy_budget: prod needs %d vectors" % self.ndim)
+        arr = (C.c_void_p * len(prod))(*[v.value for v in prod]) if prod is not None else None
+        out = np.zeros(10)
+        self._chk(self.lib.nsk_group_energy_budget(self._one, 1, *self._one_of(ub, dRe, dIm), arr,
+                                                   self._one_of(diss)[0] if diss is not None else None, out.ctypes.data_as(_dp)))
+        return out
+
+    def forced_map(self, f, q, force, mode=NSK_ADJOINT):
+        self._chk(self.lib.nsk_group_forced_map(self._one, 1, int(mode), *self._one_of(f, q, force)))
 
     def stats(self):
         from .capi import NskStats
