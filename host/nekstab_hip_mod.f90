@@ -296,6 +296,14 @@ module nekstab_hip
       type(c_ptr), value :: diss
       real(c_double), dimension(*) :: integrals
     end function
+    ! comp_vort3 of outpost_ks' Rv files (core/eigensolvers.f:632): w = vorticity of q's velocity, mass-weighted average over
+    ! shared nodes; 2-D (omega, 0), 3-D the curl; q is read only and may not be w
+    integer(c_int) function nsk_vorticity(ctx, q, w) bind(c, name='nsk_vorticity')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: q
+      type(c_ptr), value :: w
+    end function
     integer(c_int) function nsk_clone(ctx, lane) bind(c, name='nsk_clone')
       import
       type(c_ptr), value :: ctx
@@ -481,6 +489,12 @@ module nekstab_hip
       integer(c_int), value :: n
       integer(c_int), value :: mode
       type(c_ptr), dimension(*) :: f, q, force
+    end function
+    integer(c_int) function nsk_group_vorticity(shards, n, q, w) bind(c, name='nsk_group_vorticity')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: q, w
     end function
     integer(c_int) function nsk_shard_release_parent(parent) bind(c, name='nsk_shard_release_parent')
       import

@@ -249,6 +249,14 @@ int nsk_forced_map(nsk_ctx* ctx, int mode, nsk_vec f, nsk_vec q, nsk_vec force);
  * reference's comment says "normalize to unit-norm" where its code multiplies by alpha (postproc.f:703-707; the two agree when
  * alpha = 1).  A zero mode returns NSK_EINVAL. */
 int nsk_energy_budget(nsk_ctx* ctx, nsk_vec ub, nsk_vec dRe, nsk_vec dIm, nsk_vec* prod, nsk_vec diss, double* integrals);
+/* comp_vort3 as outpost_ks calls it for the Rv files (core/eigensolvers.f:629-637): w = the vorticity of q's velocity.  The
+ * element-local curl (metrics derived from the GLL coordinates) is multiplied by the unassembled mass bm1, summed over
+ * co-located nodes and divided by the assembled mass -- a mass-weighted average, not dsavg, and WITHOUT the Dirichlet mask:
+ * wall nodes keep their vorticity.  Layout of w: 2-D vx = dv/dx - du/dy, vy = 0; 3-D (vx, vy, vz) = curl; pressure and scalar
+ * slots 0.  q is read only; w == q: NSK_EINVAL.  The sums run in a fixed order (no atomics): two calls give the same bits.
+ * The assembled unmasked mass (one double per velocity node) is built at a context's first call and kept until nsk_finalize;
+ * nothing else is allocated, no captured step graph or launch budget is touched. */
+int nsk_vorticity(nsk_ctx* ctx, nsk_vec q, nsk_vec w);
 
 /* ---- lanes: independent maps in flight at once on one GPU ----
  * nsk_clone gives a context a second LANE: its own stream, time-stepper state, solver work arrays and projection space; geometry,
@@ -342,7 +350,7 @@ int nsk_group_set_orbit_fourier(nsk_ctx** shards, int n, nsk_vec* q0, double spn
 int nsk_group_set_orbit_modes(nsk_ctx** shards, int n, int nmodes, double period, const nsk_vec* A, const nsk_vec* B);
 int nsk_group_get_orbit_modes(nsk_ctx** shards, int n, int* nmodes, double* period, nsk_vec* A, nsk_vec* B);
 /* Eigenmode post-processing on shards (uparam(1) = 4.0 / 4.1 / 4.2 / 4.3 / 4.41 / 4.42 under the element decomposition): the
- * twins of nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity, nsk_energy_budget and nsk_forced_map for the ranks living in
+ * twins of nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity, nsk_energy_budget, nsk_forced_map and nsk_vorticity for the ranks living in
  * this process -- same argument checks, NULL rules and outputs, every vector argument an array of n handles (rank r's at [r];
  * n = 1 with a transport attached: one process per GPU).  Shards of full-mesh and of rank-local parents alike, before and after
  * nsk_shard_release_parent (every shard keeps the GLL coordinates of its own elements); other contexts: NSK_EINVAL ("needs
@@ -356,12 +364,17 @@ int nsk_group_get_orbit_modes(nsk_ctx** shards, int n, int* nmodes, double* peri
  *   nsk_group_energy_budget two per mode component (ndim components, then 1); the production terms are element-local.
  *   nsk_group_forced_map: NSK_DIRECT / NSK_ADJOINT, force[r] != f[r] on every rank; eager sharded steps -- the captured step
  *   graphs and the launch budgets of the unforced maps are neither used nor changed; force = 0 gives the bits of the eager
- *   nsk_group_matvec. */
+ *   nsk_group_matvec.
+ *   nsk_group_vorticity: q and w hold n handles each (a NULL entry, or w[r] == q[r]: NSK_EINVAL); ONE halo exchange per call
+ *   carrying every curl component (1 in 2-D, 3 in 3-D) in one message per peer.  The divisor is the mass assembled over ALL
+ *   ranks: the first call of a group builds it with one further exchange of one component, every shard keeps it (one double per
+ *   velocity node) until it is finalised. */
 int nsk_group_biorthogonalize(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, double* gamma_delta);
 int nsk_group_wavemaker(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* wm);
 int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* sr, nsk_vec* si, nsk_vec* parts);
 int nsk_group_energy_budget(nsk_ctx** shards, int n, nsk_vec* ub, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* prod, nsk_vec* diss, double* integrals);
 int nsk_group_forced_map(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec* q, nsk_vec* force);
+int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w);
 /* Once a process has cut its shard(s): free every device array of the parent that shards do not share (element-major geometry,
  * preconditioner factors, state, work arrays and ALL vectors allocated on the parent -- their handles become invalid).  The 1-D
  * bases and the replicated coarse operator stay.  The parent then only answers nsk_info / nsk_get_stats / nsk_finalize

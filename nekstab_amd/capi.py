@@ -109,6 +109,7 @@ SYMBOLS = {
     "nsk_group_bf_sensitivity": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, _vpp, _vpp, _vpp, _vpp]),
     "nsk_group_energy_budget": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, _vpp, _vpp, _dp]),
     "nsk_group_forced_map": (C.c_int, [_vpp, C.c_int, C.c_int, _vpp, _vpp, _vpp]),
+    "nsk_group_vorticity": (C.c_int, [_vpp, C.c_int, _vpp, _vpp]),
     "nsk_comm_init_host": (C.c_int, [_vp, _vp, _vp, _vp]),
     "nsk_shard_release_parent": (C.c_int, [_vp]),
     "nsk_comm_unique_id": (C.c_int, [_vp]),
@@ -122,6 +123,7 @@ SYMBOLS = {
     "nsk_bf_sensitivity": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vpp]),
     "nsk_forced_map": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "nsk_energy_budget": (C.c_int, [_vp, _vp, _vp, _vp, _vpp, _vp, _dp]),
+    "nsk_vorticity": (C.c_int, [_vp, _vp, _vp]),
     "nsk_bench_kernel": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),
     "nsk_get_step_iters": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nsk_get_stats": (C.c_int, [_vp, C.POINTER(NskStats)]),
@@ -438,6 +440,11 @@ class NekStabHip:
         out = np.zeros(10)
         self._chk(self.lib.nsk_energy_budget(self.ctx, ub, dRe, dIm, arr, diss, _p(out)))
         return out
+
+    def vorticity(self, w, q):
+        """w = vorticity of q's velocity (nsk_vorticity; comp_vort3 of the reference's Rv files): mass-weighted average over
+        shared nodes, no Dirichlet mask.  2-D: (omega, 0); 3-D: the curl; pressure and scalar slots of w are 0.  q is read only."""
+        self._chk(self.lib.nsk_vorticity(self.ctx, q, w))
 
     # Lanes (nsk_clone) hold their solver settings BY VALUE: a setter called after lanes exist acts on every lane, so that
     # matvec_batch / band_arnoldi never apply different operators on different lanes (ADVICE r3).

@@ -192,6 +192,7 @@ struct nsk_ctx {
   const double* xyz = nullptr;          // GLL coordinates [ndim][nloc] (nsk_seed_noise)
   const double* force = nullptr;        // steady body force [ndim][nloc] of the running forced map (nsk_forced_map; eager steps only), else null
   double* budget_wrk = nullptr;         // nsk_energy_budget: divergence field [nloc; shards: cs], per-workgroup partials, 10 sums (first call; freed with the context)
+  double* vort_mass = nullptr;          // nsk_vorticity: the assembled, unmasked mass [nloc] (first call; freed with the context)
   double* rc_big = nullptr;             // coarse restriction for nvert > 3072
   Dev d{};
   Stats hstats{};
@@ -3616,6 +3617,45 @@ int nsk_energy_budget(nsk_ctx* c, nsk_vec ub, nsk_vec dRe, nsk_vec dIm, nsk_vec*
   return 0;
 }
 
+// comp_vort3 (the Rv files of outpost_ks, core/eigensolvers.f:629-637): k_vort writes bm1 x curl of q's velocity into g (1 or 3
+// fields of component stride gs), k_vort_avg gathers it, divides by the assembled unmasked mass and fills w
+static int vort_curl(nsk_ctx* c, const double* q, double* g, long long gs) {
+  switch (c->key) {
+    case 6: nsk::sens::launch_vort<6, 2>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
+    case 8: nsk::sens::launch_vort<8, 2>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
+    case 10: nsk::sens::launch_vort<10, 2>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
+    case 12: nsk::sens::launch_vort<12, 2>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
+    case 106: nsk::sens::launch_vort<6, 3>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
+    case 108: nsk::sens::launch_vort<8, 3>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
+    case 110: nsk::sens::launch_vort<10, 3>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
+    default: return fail(NSK_EINVAL, "nsk_vorticity: unsupported lx1");
+  }
+  return 0;
+}
+static void vort_avg(nsk_ctx* c, const double* g, long long gs, double* w) {
+  const unsigned grid = (unsigned)((c->nstate + 255) / 256);
+  if (c->ndim == 2) hipLaunchKernelGGL(nsk::sens::k_vort_avg<2>, dim3(grid), dim3(256), 0, c->stream, c->d, g, gs, (const double*)c->vort_mass, w, (long long)c->nstate);
+  else hipLaunchKernelGGL(nsk::sens::k_vort_avg<3>, dim3(grid), dim3(256), 0, c->stream, c->d, g, gs, (const double*)c->vort_mass, w, (long long)c->nstate);
+}
+
+int nsk_vorticity(nsk_ctx* c, nsk_vec q, nsk_vec w) {
+  int rc = sens_ctx_ok(c, "nsk_vorticity");
+  if (rc) return rc;
+  if (!q || !w) return fail(NSK_EINVAL, "nsk_vorticity: bad argument");
+  if (q == w) return fail(NSK_EINVAL, "nsk_vorticity: the output may not be the input vector");
+  if (!c->xyz || !c->scratch) return fail(NSK_EINVAL, "nsk_vorticity: context holds no coordinates");
+  const unsigned grid = (unsigned)((c->nloc + 255) / 256);
+  if (!c->vort_mass) {                                           // once per context: nloc doubles, kept until nsk_finalize
+    if ((rc = dalloc(c, &c->vort_mass, (size_t)c->nloc))) return rc;
+    hipLaunchKernelGGL(nsk::sens::k_vort_mass, dim3(grid), dim3(256), 0, c->stream, c->d, c->d.bm1, c->vort_mass);
+  }
+  if ((rc = vort_curl(c, (const double*)q, c->scratch, c->nloc))) return rc;
+  vort_avg(c, c->scratch, c->nloc, (double*)w);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 int nsk_forced_map(nsk_ctx* c, int mode, nsk_vec fv, nsk_vec qv, nsk_vec force) {
   int rc = sens_ctx_ok(c, "nsk_forced_map");
   if (rc) return rc;
@@ -3886,6 +3926,44 @@ int nsk_group_energy_budget(nsk_ctx** shards, int n, nsk_vec* ub, nsk_vec* dRe, 
   }
   for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
   return group_sum(G, loc.data(), 10, integrals);
+}
+
+// nsk_vorticity on shards: ONE halo exchange per call, all curl components in one message per peer (the exchanged array is wv1,
+// as in nsk_group_bf_sensitivity).  The divisor is the mass assembled over ALL ranks: built at a group's first call (bm1 into
+// wv1, one exchange of one component, gather) and kept by every shard until it is finalised.
+int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w) {
+  int rc = sens_group_ok(shards, n, "nsk_group_vorticity");
+  if (rc) return rc;
+  if (!q || !w) return fail(NSK_EINVAL, "nsk_group_vorticity: bad argument");
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  const int key = G[0]->key;
+  for (int r = 0; r < n; ++r) {
+    if (!q[r] || !w[r]) return fail(NSK_EINVAL, "nsk_group_vorticity: bad argument (q and w need one vector per rank)");
+    if (q[r] == w[r]) return fail(NSK_EINVAL, "nsk_group_vorticity: the output may not be the input vector");
+    if (!G[r]->xyz || !G[r]->wv1) return fail(NSK_EINVAL, "nsk_group_vorticity: context holds no coordinates");
+  }
+  if (key != 6 && key != 8 && key != 10 && key != 12 && key != 106 && key != 108 && key != 110)
+    return fail(NSK_EINVAL, "nsk_group_vorticity: unsupported lx1");
+  double* base[16];
+  for (int r = 0; r < n; ++r) base[r] = G[r]->wv1;
+  bool have = true;
+  for (nsk_ctx* c : G) have = have && c->vort_mass;
+  if (!have) {
+    for (nsk_ctx* c : G) {
+      if (!c->vort_mass && (rc = dalloc(c, &c->vort_mass, (size_t)c->nloc))) return rc;
+      HIPCHK(hipMemcpyAsync(c->wv1, c->d.bm1, c->nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    if ((rc = xchg_vel_at(G, base, 1))) return rc;
+    for (nsk_ctx* c : G)
+      hipLaunchKernelGGL(nsk::sens::k_vort_mass, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream, c->d, (const double*)c->wv1, c->vort_mass);
+  }
+  for (int r = 0; r < n; ++r)
+    if ((rc = vort_curl(G[r], (const double*)q[r], G[r]->wv1, G[r]->d.cs))) return rc;
+  if ((rc = xchg_vel_at(G, base, G[0]->ndim == 3 ? 3 : 1))) return rc;
+  for (int r = 0; r < n; ++r) vort_avg(G[r], G[r]->wv1, G[r]->d.cs, (double*)w[r]);
+  HIPCHK(hipGetLastError());
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 // nsk_forced_map on shards: eager sharded steps with k_add_force behind the convection kernel of every rank (group_step).  The

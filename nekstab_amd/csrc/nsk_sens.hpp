@@ -334,5 +334,85 @@ __global__ void __launch_bounds__(256) k_budget_diss(const Dev d, const double* 
   if (tid == 0) part[blockIdx.x] = v[0];
 }
 
+// ---- comp_vort3 (the Rv files of outpost_ks, core/eigensolvers.f:629-637) ------------------------------------------------
+// Vorticity of the velocity of a state vector, averaged over shared nodes with the MASS as weight: element-local curl times the
+// unassembled bm1, summed over co-located nodes, divided by the assembled bm1 -- NOT dsavg (multiplicity) and without the
+// Dirichlet mask (Dev::binv carries it: it would zero the wall nodes, where a mode's vorticity is largest).  Two launches:
+// k_vort (all derivatives of all components in one pass over the element) and k_vort_avg (gather, divide, fill the output).
+
+// g[c * gs + l] = bm1[l] * curl(u)_c at the element-local node l: one field in 2-D (dv/dx - du/dy), three in 3-D.
+// u: velocity with component stride nloc; gs: component stride of g (nloc, or Dev::cs on a shard: ghost slots behind).
+// One workgroup per element; D, the ndim velocity components and the ndim coordinates in LDS, metrics derived here.
+template <int N, int NDIM>
+__global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_vort(const double* __restrict__ D, const double* __restrict__ xyz,
+                                                               const double* __restrict__ u, const double* __restrict__ bm1,
+                                                               double* __restrict__ g, long long nloc, long long gs) {
+  constexpr int NP = SensCfg<N, NDIM>::NP;
+  __shared__ double sD[N * N];
+  __shared__ double su[NDIM][NP], sx[NP], sy[NP], sz[NDIM == 3 ? NP : 1];
+  const int tid = threadIdx.x;
+  const long long e0 = (long long)blockIdx.x * NP, l = e0 + tid;
+  const bool act = tid < NP;
+  elem_load_geom<N, NDIM>(D, xyz, e0, nloc, tid, sD, sx, sy, sz);
+  if (act) {
+#pragma unroll
+    for (int c = 0; c < NDIM; ++c) su[c][tid] = u[c * nloc + l];
+  }
+  __syncthreads();
+  if (!act) return;
+  double m[NDIM][NDIM];
+  elem_inv_metric<N, NDIM>(sD, sx, sy, sz, tid, m);
+  double du[NDIM][NDIM];                                       // du[c][a] = d u_c / d x_a
+#pragma unroll
+  for (int c = 0; c < NDIM; ++c) {
+    double fd[NDIM];
+    elem_ref_deriv<N, NDIM>(sD, su[c], tid, fd);
+#pragma unroll
+    for (int a = 0; a < NDIM; ++a) {
+      double s = 0.0;
+#pragma unroll
+      for (int q = 0; q < NDIM; ++q) s += m[q][a] * fd[q];
+      du[c][a] = s;
+    }
+  }
+  const double b = bm1[l];
+  if constexpr (NDIM == 2) {
+    g[l] = b * (du[1][0] - du[0][1]);
+  } else {
+    g[l] = b * (du[2][1] - du[1][2]);
+    g[gs + l] = b * (du[0][2] - du[2][0]);
+    g[2 * gs + l] = b * (du[1][0] - du[0][1]);
+  }
+}
+
+template <int N, int NDIM>
+inline void launch_vort(hipStream_t st, int nel, const double* D, const double* xyz, const double* u, const double* bm1, double* g,
+                        long long nloc, long long gs) {
+  hipLaunchKernelGGL((k_vort<N, NDIM>), dim3(nel), dim3(SensCfg<N, NDIM>::NT), 0, st, D, xyz, u, bm1, g, nloc, gs);
+}
+
+// the assembled, UNMASKED mass: out[l] = sum of bm1 over the nodes co-located with l (f: bm1, on a shard with the peers'
+// partial sums in the ghost slots behind its nloc entries)
+__global__ void k_vort_mass(const Dev d, const double* __restrict__ f, double* __restrict__ out) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l < d.nloc) out[l] = gs_gather(f, d, l);
+}
+
+// w = the state vector whose velocity is dssum(g) / mass: 2-D (omega, 0), 3-D (omega_x, omega_y, omega_z); pressure and scalar
+// slots 0.  One thread per entry of w (nstate of them); the gather adds in ascending order of the co-located nodes, no atomics.
+template <int NDIM>
+__global__ void k_vort_avg(const Dev d, const double* __restrict__ g, long long gs, const double* __restrict__ mass,
+                           double* __restrict__ w, long long nstate) {
+  constexpr int NC = NDIM == 3 ? 3 : 1;
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= nstate) return;
+  if (l < d.nloc) {
+    const double mi = mass[l];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) w[c * d.nloc + l] = gs_gather(g + c * gs, d, l) / mi;
+  }
+  if (l >= NC * d.nloc) w[l] = 0.0;
+}
+
 }  // namespace sens
 }  // namespace nsk

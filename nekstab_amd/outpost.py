@@ -6,6 +6,7 @@ them unchanged.
   Spectre_NS<op>.dat       (3E15.7)  Re/Im log(mu)/T, residual      :593-595
   Spectre_NS<op>_conv.dat  (2E15.7)  converged & outposted <= maxmodes   :601-604
   <op>Re<session>0.f0000i / <op>Im...  eigenmode i = Q y_i, |Re|^2+|Im|^2 = 1 (bm1s), time = i  :607-642
+  <op>Rv<session>0.f0000i  vorticity of the real part of eigenmode i (comp_vort3; ``ifvor=True``)   :629-637
   Spectre_<op>.info        key=value manifest of the run (mesh, uparam, solver, eigensolver)   :664-717
 """
 from __future__ import annotations
@@ -70,7 +71,11 @@ def read_info(path):
 
 
 def outpost_ks(be, res, case, outdir, *, evop="d", sampling_period=1.0, eigen_tol=1e-6, maxmodes=20,
-               session="1cyl", wdsize=4, schur_tgt=0, schur_del=0.10, uparam=None, tol_pres=None, tol_vel=None, nranks=1):
+               session="1cyl", wdsize=4, schur_tgt=0, schur_del=0.10, uparam=None, tol_pres=None, tol_vel=None, nranks=1,
+               ifvor=False):
+    """``ifvor``: also write, for every converged mode, ``<evop>Rv<session>0.f0000i`` = the vorticity of its real part
+    (comp_vort3 + outpost(vort, 'Rv') with ifpo = ifto = .false., core/eigensolvers.f:629-637: read code XU, time / istep / wdsize
+    of the Re file), computed on the device (``be.vorticity``).  Returns the Re / Im paths, then the Rv paths."""
     os.makedirs(outdir, exist_ok=True)
     k = res.H.shape[1]
     lam = log_transform(res.vals, sampling_period)
@@ -78,7 +83,8 @@ def outpost_ks(be, res, case, outdir, *, evop="d", sampling_period=1.0, eigen_to
     nekio.write_spectre(os.path.join(outdir, f"Spectre_NS{evop}.dat"), lam, res.residual)
     conv = []
     re, im = be.alloc(2)
-    written = []
+    vor = be.alloc(1) if ifvor else []
+    written, written_rv = [], []
     for i in range(k):
         if res.residual[i] < eigen_tol and len(conv) < maxmodes:
             conv.append(lam[i])
@@ -89,9 +95,15 @@ def outpost_ks(be, res, case, outdir, *, evop="d", sampling_period=1.0, eigen_to
                 f = os.path.join(outdir, "%s%s%s0.f%05d" % (evop, tag, session, idx))
                 nekio.write_fld(f, x=x, u=u, p=p1, time=float(i + 1), istep=be.nsteps + 1, wdsize=wdsize)
                 written.append(f)
+            if ifvor:
+                be.vorticity(vor[0], re)
+                x, u, _ = state_to_fields(be, case, vor[0])
+                f = os.path.join(outdir, "%sRv%s0.f%05d" % (evop, session, idx))
+                nekio.write_fld(f, x=x, u=u, time=float(i + 1), istep=be.nsteps + 1, wdsize=wdsize)
+                written_rv.append(f)
     nekio.write_spectre(os.path.join(outdir, f"Spectre_NS{evop}_conv.dat"), np.array(conv))
     write_info(os.path.join(outdir, f"Spectre_{evop}.info"), be, case, res, evop=evop, sampling_period=sampling_period,
                eigen_tol=eigen_tol, schur_tgt=schur_tgt, schur_del=schur_del, outposted=len(conv), uparam=uparam,
                tol_pres=tol_pres, tol_vel=tol_vel, nranks=nranks)
-    be.free([re, im])
-    return written
+    be.free([re, im] + vor)
+    return written + written_rv

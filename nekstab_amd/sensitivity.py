@@ -11,7 +11,8 @@ The fields are computed on the device (nsk_energy_budget, nsk_biorthogonalize, n
 nsk_forced_map; on element shards their nsk_group_* twins: every driver below takes a ``sharded.ShardGroup`` in place of the
 single-rank context and writes the same files); delta_forcing is pointwise and stays on the host.  Output files carry the reference's prefixes (KIN, wm_, tr_,
 ti_, pr_, pi_, sr_, si_, fsr, fsi, dfr) so that nekStab's own scripts read them.  ``np_*`` functions are the numpy
-restatement the device is tested against.
+restatement the device is tested against; ``np_vorticity`` is that of nsk_vorticity (comp_vort3, the Rv files that
+``outpost.outpost_ks(..., ifvor=True)`` writes).
 
 Three departures from the reference, all deliberate:
   * in 3-D the transport term uses d v / d z where core/sensitivity.f:219, 222, 228, 231 read d w / d z (Marquet's formula;
@@ -176,6 +177,20 @@ def np_energy_budget(geom: NpGeom, ub, dRe, dIm, nu):
             integrals[3 * c + j] = np.sum(geom.bm1 * prod[c, j])
     integrals[9] = np.sum(geom.bm1 * diss)
     return dict(prod=prod, diss=diss, integrals=integrals)
+
+
+def np_vorticity(geom: NpGeom, u):
+    """comp_vort3 as outpost_ks calls it (core/eigensolvers.f:632) on a velocity field [ndim, nel, ...]: element-local curl,
+    times the unassembled mass bm1, summed over co-located nodes, divided by the assembled mass (no Dirichlet mask).
+    Returns [1, nel, ...] in 2-D (d v / d x - d u / d y) and [3, nel, ...] in 3-D."""
+    G = [geom.grad(np.asarray(u[c], dtype=np.float64)) for c in range(geom.ndim)]          # G[c][a] = d u_c / d x_a
+    if geom.ndim == 2:
+        curl = [G[1][0] - G[0][1]]
+    else:
+        curl = [G[2][1] - G[1][2], G[0][2] - G[2][0], G[1][0] - G[0][1]]
+    dssum = lambda f: np.bincount(geom.gid.ravel(), weights=f.ravel(), minlength=geom.nglob)[geom.gid]
+    mass = dssum(geom.bm1)
+    return np.array([dssum(c * geom.bm1) / mass for c in curl])
 
 
 def delta_forcing(ub, fsr, fsi, alpha=1.0):

@@ -401,6 +401,10 @@ class ShardGroup:
         """f = linearised map of q under the steady body force ``force`` (eager sharded steps)."""
         self._chk(self.lib.nsk_group_forced_map(self._arr, self.R, int(mode), *[self._per_rank(v) for v in (f, q, force)]))
 
+    def vorticity(self, w, q):
+        """w = vorticity of q's velocity, mass-averaged over ALL ranks (nsk_group_vorticity: one halo exchange per call)."""
+        self._chk(self.lib.nsk_group_vorticity(self._arr, self.R, self._per_rank(q), self._per_rank(w)))
+
     def stats(self):
         from .capi import NskStats
         st = NskStats()
@@ -649,6 +653,9 @@ class ShardRank:
 
     def forced_map(self, f, q, force, mode=NSK_ADJOINT):
         self._chk(self.lib.nsk_group_forced_map(self._one, 1, int(mode), *self._one_of(f, q, force)))
+
+    def vorticity(self, w, q):
+        self._chk(self.lib.nsk_group_vorticity(self._one, 1, *self._one_of(q, w)))
 
     def stats(self):
         from .capi import NskStats
