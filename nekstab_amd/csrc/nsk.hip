@@ -54,6 +54,18 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
     case 110: { using namespace nsk::k3; constexpr int N = 10; __VA_ARGS__; } break;           \
     default: return fail(NSK_EINVAL, "unsupported lx1");                                        \
   }
+// the same keys for nsk::sens, whose kernels take lx1 and the dimension as template arguments N, NDIM
+#define DISPATCH_SENS(n, ...)                                                                   \
+  switch (n) {                                                                                  \
+    case 6: { constexpr int N = 6, NDIM = 2; __VA_ARGS__; } break;                              \
+    case 8: { constexpr int N = 8, NDIM = 2; __VA_ARGS__; } break;                              \
+    case 10: { constexpr int N = 10, NDIM = 2; __VA_ARGS__; } break;                            \
+    case 12: { constexpr int N = 12, NDIM = 2; __VA_ARGS__; } break;                            \
+    case 106: { constexpr int N = 6, NDIM = 3; __VA_ARGS__; } break;                            \
+    case 108: { constexpr int N = 8, NDIM = 3; __VA_ARGS__; } break;                            \
+    case 110: { constexpr int N = 10, NDIM = 3; __VA_ARGS__; } break;                           \
+    default: return fail(NSK_EINVAL, "unsupported lx1");                                        \
+  }
 
 struct nsk_ctx {
   int N = 0, NN = 0, M = 0, MM = 0, ND = 0, NDD = 0, EPB = 0, NT = 0, NTD = 0;
@@ -2151,6 +2163,15 @@ int nsk_group_set_baseflow(nsk_ctx** shards, int n, nsk_vec* q) {
   return group_set_baseflow(G, (const double* const*)q);
 }
 
+// a stored orbit ends: the base-flow pointers go back to the steady arrays (the caller decides about the captured graphs)
+static void steady_back(nsk_ctx* c) {
+  Dev& d = c->d;
+  if (!d.bf_stride) return;
+  if (c->ndim == 3) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; }
+  else { d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5]; }
+  d.bf_stride = 0;
+}
+
 // Time-periodic base flow on element shards (nsk_set_orbit for the ranks of this process): the full equations are integrated
 // over one period by the sharded stepper and every rank stores the base-flow constants of its own elements per step.
 int nsk_group_set_orbit(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, nsk_vec* end) {
@@ -2161,13 +2182,6 @@ int nsk_group_set_orbit(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, n
   const int nd = G[0]->ndim;
   // quadrilaterals: six arrays of nel*lxd^2 per step; hexahedra: one array of 12*nel*lxd^3 per step behind Dev::bfc (= cUr)
   const int narr = nd == 3 ? 1 : 6;
-  auto steady_back = [&](nsk_ctx* c) {
-    Dev& d = c->d;
-    if (!d.bf_stride) return;
-    if (nd == 3) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; }
-    else { d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5]; }
-    d.bf_stride = 0;
-  };
   int rc;
   for (nsk_ctx* c : G) steady_back(c);
   if ((rc = group_set_baseflow(G, (const double* const*)q0))) return rc;
@@ -2932,7 +2946,7 @@ static int set_orbit_impl(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end,
   auto four_end = [&]() { if (dftw) { nsk_vec v = dftw; nsk_vec_free(c, 1, &v); dftw = nullptr; } };
   if (c->ndim == 3) {
     // hexahedra: the twelve dealiasing-mesh constants of every time step of the orbit, [nsteps][12][nfine] behind Dev::bfc
-    if (d.bf_stride) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; d.bf_stride = 0; }
+    steady_back(c);
     int rc = nsk_set_baseflow(c, q0v);                          // dt, nsteps from the CFL of the initial field
     if (rc) return rc;
     const long long nfine = d.nfine;
@@ -2977,10 +2991,7 @@ static int set_orbit_impl(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end,
     invalidate_graphs(c);
     return 0;
   }
-  if (d.bf_stride) {                                            // back to the steady arrays first
-    d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5];
-    d.bf_stride = 0;
-  }
+  steady_back(c);                                               // back to the steady arrays first
   int rc = nsk_set_baseflow(c, q0v);                            // dt, nsteps from the CFL of the initial field
   if (rc) return rc;
   const long long nfine = (long long)c->nel * c->NDD;
@@ -3054,7 +3065,6 @@ int nsk_set_orbit_modes(nsk_ctx* c, int nmodes, double period, const nsk_vec* A,
   { const int rc = forb_refuse(c, "nsk_set_orbit_modes"); if (rc) return rc; }
   if (!(period > 0.0)) return fail(NSK_EINVAL, "nsk_set_orbit_modes: period must be positive");
   for (int k = 0; k <= nmodes; ++k) if (!A[k] || (k < nmodes && !B[k])) return fail(NSK_EINVAL, "nsk_set_orbit_modes: null mode vector");
-  Dev& d = c->d;
   const long long nv = (long long)c->ndim * c->nloc;
   // the modes first (A or B may be the vectors nsk_get_orbit_modes filled from the arrays replaced here: staged through a new array)
   double* fresh = nullptr;
@@ -3067,11 +3077,7 @@ int nsk_set_orbit_modes(nsk_ctx* c, int nmodes, double period, const nsk_vec* A,
   HIPCHK(hipMemsetAsync(c->scratch, 0, c->nstate * sizeof(double), c->stream));
   for (int k = 0; k <= nmodes; ++k)                             // U(0) = sum_k A_k
     hipLaunchKernelGGL(k_axpby, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, c->scratch, 1.0, (const double*)A[k], 1.0, nv);
-  if (d.bf_stride) {                                            // back to the steady arrays first (as nsk_set_orbit)
-    if (c->ndim == 3) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; }
-    else { d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5]; }
-    d.bf_stride = 0;
-  }
+  steady_back(c);                                               // back to the steady arrays first (as nsk_set_orbit)
   if ((rc = nsk_set_baseflow(c, c->scratch))) { nsk_vec v = fresh; nsk_vec_free(c, 1, &v); return rc; }
   HIPCHK(hipStreamSynchronize(c->stream));
   if (c->forb_modes) { nsk_vec v = c->forb_modes; nsk_vec_free(c, 1, &v); }
@@ -3108,12 +3114,9 @@ int nsk_get_orbit_modes(nsk_ctx* c, int* nmodes, double* period, nsk_vec* A, nsk
 
 // ---- the Fourier form on element shards: every rank keeps the modes of its own elements, [2M+1][ndim][nloc of the shard], and
 // its own table of cos / sin factors (group_run_map); group_step reconstructs per rank in front of the convection kernel.
-static void shard_steady_back(nsk_ctx* c) {                     // a stored orbit ends: back to the steady arrays
-  Dev& d = c->d;
-  if (!d.bf_stride) return;
-  if (c->ndim == 3) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; }
-  else { d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5]; }
-  d.bf_stride = 0;
+static void shard_steady_back(nsk_ctx* c) {                     // steady_back, and the captured graphs read the old pointers
+  if (!c->d.bf_stride) return;
+  steady_back(c);
   invalidate_graphs(c);
 }
 // amp[0 .. 2M] = bm1s-weighted L2 norms of A_0, A_1, B_1, .. over ALL ranks: per rank one pass of k_mode_norm2 over its mode
@@ -3434,259 +3437,41 @@ int nsk_seed_noise(nsk_ctx* c, nsk_vec v) {
   return 0;
 }
 
-// ---- sensitivity post-processing (core/sensitivity.f) ---------------------------------------------------------------
+// ---- eigenmode post-processing (core/sensitivity.f, core/postproc.f; uparam(1) = 4.x) -------------------------------------
+// One body per operation, written for the ranks living in this process: G holds n contexts and every vector argument is an
+// array of n handles (rank r's at [r]).  A full-mesh context is a group of one whose exchange is empty: Dev::cs == nloc, no
+// halo and no peers (xchg_vel_at launches and copies nothing), no transport (group_sum adds one term).  So a single-rank entry
+// wraps its handles into arrays of length 1 and runs the kernels, strides and order of operations of the group entry; the two
+// differ in the contexts they accept (sens_ctx_ok / sens_group_ok) and in the name their error texts carry (`who`).  n = 1
+// with a host or RCCL transport attached: one process per GPU.
+// dsavg: the field at component stride Dev::cs (on a shard: ghost slots behind its nloc entries), halo exchange (xchg_vel_at),
+// gather, times minv (a shard's is sliced from the parent: the global multiplicity).  The exchanged work array is nsk_ctx::wv1
+// (ndim * cs doubles; the kernel-test hooks' buffer, which no map reads or writes), so a map that follows finds its own work
+// arrays as the last map left them.
+static int sfail(const char* who, const char* msg) { return fail(NSK_EINVAL, std::string(who) + ": " + msg); }
+
 static int sens_ctx_ok(nsk_ctx* c, const char* who) {
-  if (!c) return fail(NSK_EINVAL, std::string(who) + ": bad argument");
+  if (!c) return sfail(who, "bad argument");
   if (c->parent || c->local || c->released || c->d.nranks > 1)
     return fail(NSK_EINVAL, std::string(who) + ": single-rank full-mesh contexts only (shards: use nsk_group_" + std::string(who).substr(4) + ")");
   return 0;
 }
+static int sens_group_ok(nsk_ctx** shards, int n, const char* who) {
+  if (!shards || n < 1 || n > 16) return sfail(who, "bad argument");
+  for (int r = 0; r < n; ++r) {
+    if (!shards[r]) return sfail(who, "bad argument");
+    if (!shards[r]->parent) return sfail(who, "needs shard contexts");
+    if (shards[r]->key != shards[0]->key) return sfail(who, "the shards differ in lx1");
+  }
+  return 0;
+}
+static int sens_key_ok(int key) { DISPATCH_SENS(key, {}); return 0; }
 
 static bool distinct(const std::vector<const void*>& v) {
   for (size_t a = 0; a < v.size(); ++a)
     for (size_t b = a + 1; b < v.size(); ++b)
       if (v[a] == v[b]) return false;
   return true;
-}
-
-int nsk_biorthogonalize(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, double* gamma_delta) {
-  int rc = sens_ctx_ok(c, "nsk_biorthogonalize");
-  if (rc) return rc;
-  if (!dRe || !dIm || !aRe || !aIm || !distinct({dRe, dIm, aRe, aIm})) return fail(NSK_EINVAL, "nsk_biorthogonalize: four distinct vectors needed");
-  double a = 0, b = 0;                                           // || d ||^2 = || dRe ||^2 + || dIm ||^2  (:459-465)
-  if ((rc = nsk_dot(c, dRe, dRe, &a)) || (rc = nsk_dot(c, dIm, dIm, &b))) return rc;
-  if (!(a + b > 0.0)) return fail(NSK_EINVAL, "nsk_biorthogonalize: the direct mode is zero");
-  const double s = 1.0 / std::sqrt(a + b);
-  if ((rc = nsk_scal(c, dRe, s)) || (rc = nsk_scal(c, dIm, s))) return rc;
-  double rr = 0, ii = 0, ri = 0, ir = 0;                         // <a, d> = gamma + i delta  (:468-476)
-  if ((rc = nsk_dot(c, aRe, dRe, &rr)) || (rc = nsk_dot(c, aIm, dIm, &ii)) || (rc = nsk_dot(c, aRe, dIm, &ri)) ||
-      (rc = nsk_dot(c, aIm, dRe, &ir))) return rc;
-  const double gamma = rr + ii, delta = ri - ir, den = gamma * gamma + delta * delta;
-  if (!(den > 0.0)) return fail(NSK_EINVAL, "nsk_biorthogonalize: the adjoint mode is orthogonal to the direct mode");
-  hipLaunchKernelGGL(nsk::sens::k_cdiv, dim3((unsigned)((c->nstate + 255) / 256)), dim3(256), 0, c->stream, (double*)aRe, (double*)aIm,
-                     gamma / den, delta / den, c->nstate);
-  HIPCHK(hipGetLastError());
-  if (gamma_delta) { gamma_delta[0] = gamma; gamma_delta[1] = delta; }
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-int nsk_wavemaker(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec wm) {
-  int rc = sens_ctx_ok(c, "nsk_wavemaker");
-  if (rc) return rc;
-  if (!dRe || !dIm || !aRe || !aIm || !wm) return fail(NSK_EINVAL, "nsk_wavemaker: bad argument");
-  if (!distinct({dRe, wm}) || !distinct({dIm, wm}) || !distinct({aRe, wm}) || !distinct({aIm, wm}))
-    return fail(NSK_EINVAL, "nsk_wavemaker: the output may not be one of the modes");
-  HIPCHK(hipMemsetAsync(wm, 0, c->nstate * sizeof(double), c->stream));
-  hipLaunchKernelGGL(nsk::sens::k_wavemaker, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream, (const double*)dRe,
-                     (const double*)dIm, (const double*)aRe, (const double*)aIm, (double*)wm, c->nloc, c->ndim);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-// element-local gradient of the velocity-mesh field f into g (ndim fields of component stride gs): k_sens_grad of the context's lx1
-static int sens_grad(nsk_ctx* c, const double* f, double* g, long long gs) {
-  switch (c->key) {
-    case 6: nsk::sens::launch_sens_grad<6, 2>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
-    case 8: nsk::sens::launch_sens_grad<8, 2>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
-    case 10: nsk::sens::launch_sens_grad<10, 2>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
-    case 12: nsk::sens::launch_sens_grad<12, 2>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
-    case 106: nsk::sens::launch_sens_grad<6, 3>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
-    case 108: nsk::sens::launch_sens_grad<8, 3>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
-    case 110: nsk::sens::launch_sens_grad<10, 3>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); break;
-    default: return fail(NSK_EINVAL, "unsupported lx1");
-  }
-  return 0;
-}
-
-int nsk_bf_sensitivity(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec sr, nsk_vec si, nsk_vec* parts) {
-  int rc = sens_ctx_ok(c, "nsk_bf_sensitivity");
-  if (rc) return rc;
-  if (!dRe || !dIm || !aRe || !aIm || !sr || !si) return fail(NSK_EINVAL, "nsk_bf_sensitivity: bad argument");
-  if (parts && (!parts[0] || !parts[1] || !parts[2] || !parts[3])) return fail(NSK_EINVAL, "nsk_bf_sensitivity: parts needs four vectors");
-  if (!c->xyz || !c->scratch) return fail(NSK_EINVAL, "nsk_bf_sensitivity: context holds no coordinates");
-  std::vector<const void*> all = {dRe, dIm, aRe, aIm, sr, si};
-  if (parts) all.insert(all.end(), parts, parts + 4);
-  if (!distinct(all))
-    return fail(NSK_EINVAL, "nsk_bf_sensitivity: inputs and outputs must be distinct vectors");
-  double* outs[6] = {(double*)sr, (double*)si, parts ? (double*)parts[0] : nullptr, parts ? (double*)parts[1] : nullptr,
-                     parts ? (double*)parts[2] : nullptr, parts ? (double*)parts[3] : nullptr};
-  for (double* o : outs) if (o) HIPCHK(hipMemsetAsync(o, 0, c->nstate * sizeof(double), c->stream));
-  double* tR = parts ? outs[2] : outs[0];                        // transport (tr, ti) and production (pr, pi) terms
-  double* tI = parts ? outs[3] : outs[1];
-  double* pR = parts ? outs[4] : outs[0];
-  double* pI = parts ? outs[5] : outs[1];
-  const double* m[4] = {(const double*)dRe, (const double*)dIm, (const double*)aRe, (const double*)aIm};
-  // kind 0 / 1: gradient of the direct mode (transport), kind 2 / 3: of the adjoint mode (production); sensitivity.f:215-256
-  // with d v / d z where the reference reads d w / d z in the transport term (:219, 222, 228, 231)
-  const nsk::sens::SensAcc acc[4] = {
-      {m[2], m[3], tR, tI, -1.0, -1.0, 0, 0},
-      {m[3], m[2], tR, tI, -1.0, 1.0, 0, 0},
-      {m[0], m[1], pR, pI, 1.0, -1.0, 0, 1},
-      {m[1], m[0], pR, pI, 1.0, 1.0, 0, 1}};
-  const unsigned grid = (unsigned)((c->nloc + 255) / 256);
-  for (int kind = 0; kind < 4; ++kind)
-    for (int comp = 0; comp < c->ndim; ++comp) {
-      const double* f = m[kind] + (size_t)comp * c->nloc;
-      if ((rc = sens_grad(c, f, c->scratch, c->nloc))) return rc;
-      nsk::sens::SensAcc a = acc[kind];
-      a.comp = comp;
-      if (c->ndim == 2) hipLaunchKernelGGL(nsk::sens::k_sens_acc<2>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, c->nloc, a);
-      else hipLaunchKernelGGL(nsk::sens::k_sens_acc<3>, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, c->nloc, a);
-    }
-  if (parts) {
-    const long long nv = (long long)c->ndim * c->nloc;
-    const unsigned gv = (unsigned)((nv + 255) / 256);
-    hipLaunchKernelGGL(nsk::sens::k_add3, dim3(gv), dim3(256), 0, c->stream, outs[0], (const double*)tR, (const double*)pR, nv);
-    hipLaunchKernelGGL(nsk::sens::k_add3, dim3(gv), dim3(256), 0, c->stream, outs[1], (const double*)tI, (const double*)pI, nv);
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-// stability_energy_budget (core/postproc.f:657-872): 1 + 6 ndim launches + 2 reductions, one workspace allocated once per context
-extern "C++" {
-template <int N, int NDIM>
-static void energy_budget_launch(nsk_ctx* c, const double* ub, const double* uR, const double* uI, double* const* prod, double* diss,
-                                 double s, double* wrk) {
-  const long long n = c->nloc;
-  const int nb = (int)((n + 255) / 256);
-  double* div = wrk;
-  double* ppart = wrk + n;                                       // [9][nel]
-  double* dpart = ppart + 9 * (size_t)c->nel;                    // [2 ndim][nb]
-  double* out = dpart + 2 * NDIM * (size_t)nb;                   // [10]
-  nsk::sens::BudgetProd bp{{prod ? prod[0] : nullptr, prod ? prod[1] : nullptr, prod && NDIM == 3 ? prod[2] : nullptr}};
-  hipLaunchKernelGGL((nsk::sens::k_budget_prod<N, NDIM>), dim3(c->nel), dim3(nsk::sens::SensCfg<N, NDIM>::NT), 0, c->stream, c->d.D,
-                     c->xyz, ub, uR, uI, c->d.bm1, bp, -0.5 * s, ppart, n);
-  const double wd = 0.5 * c->d.nu * s;                           // param(2) / param(1) = 1 / Re
-  for (int k = 0; k < 2 * NDIM; ++k) {                           // u_R,x  u_I,x  u_R,y  u_I,y [ u_R,z  u_I,z ]
-    const double* a = ((k & 1) ? uI : uR) + (size_t)(k >> 1) * n;
-    nsk::sens::launch_sens_grad<N, NDIM>(c->stream, c->nel, c->d.D, c->xyz, a, c->scratch, n, n);
-    hipLaunchKernelGGL((nsk::sens::k_budget_div<N, NDIM>), dim3(c->nel), dim3(nsk::sens::SensCfg<N, NDIM>::NT), 0, c->stream, c->d,
-                       c->xyz, (const double*)c->scratch, n, div);
-    hipLaunchKernelGGL(nsk::sens::k_budget_diss, dim3(nb), dim3(256), 0, c->stream, c->d, (const double*)div, a, diss, wd, k == 0 ? 1 : 0,
-                       dpart + (size_t)k * nb);
-  }
-  hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)ppart, 9, c->nel, out);
-  hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)dpart, 1, 2 * NDIM * nb, out + 9);
-}
-}  // extern "C++"
-
-int nsk_energy_budget(nsk_ctx* c, nsk_vec ub, nsk_vec dRe, nsk_vec dIm, nsk_vec* prod, nsk_vec diss, double* integrals) {
-  int rc = sens_ctx_ok(c, "nsk_energy_budget");
-  if (rc) return rc;
-  if (!ub || !dRe || !dIm || !integrals) return fail(NSK_EINVAL, "nsk_energy_budget: bad argument (ub, dRe, dIm and integrals are required)");
-  if (prod) for (int k = 0; k < c->ndim; ++k) if (!prod[k]) return fail(NSK_EINVAL, "nsk_energy_budget: prod needs ndim vectors");
-  if (!c->xyz || !c->scratch) return fail(NSK_EINVAL, "nsk_energy_budget: context holds no coordinates");
-  std::vector<const void*> outs;
-  if (prod) outs.insert(outs.end(), prod, prod + c->ndim);
-  if (diss) outs.push_back(diss);
-  for (const void* o : outs)
-    if (o == ub || o == dRe || o == dIm) return fail(NSK_EINVAL, "nsk_energy_budget: an output may not be one of the inputs");
-  if (!distinct(outs)) return fail(NSK_EINVAL, "nsk_energy_budget: the outputs must be distinct vectors");
-  if (c->key != 6 && c->key != 8 && c->key != 10 && c->key != 12 && c->key != 106 && c->key != 108 && c->key != 110)
-    return fail(NSK_EINVAL, "nsk_energy_budget: unsupported lx1");
-  double a = 0, b = 0;                                           // alpha^2 = ||dRe||^2 + ||dIm||^2  (postproc.f:703-707)
-  if ((rc = nsk_dot(c, dRe, dRe, &a)) || (rc = nsk_dot(c, dIm, dIm, &b))) return rc;
-  if (!(a + b > 0.0)) return fail(NSK_EINVAL, "nsk_energy_budget: the direct mode is zero");
-  // the mode divided by alpha (the reference's comment; its code multiplies): every term is quadratic in the mode, so the scale
-  // enters as 1 / alpha^2 on the weights and the inputs are left as they are
-  const double s = 1.0 / (a + b);
-  const long long nb = (c->nloc + 255) / 256;
-  if (!c->budget_wrk && (rc = dalloc(c, &c->budget_wrk, (size_t)(c->nloc + 9LL * c->nel + 2LL * c->ndim * nb + 10)))) return rc;
-  const long long nv = (long long)c->ndim * c->nloc;
-  if (prod) for (int k = 0; k < c->ndim; ++k) HIPCHK(hipMemsetAsync((double*)prod[k] + nv, 0, (c->nstate - nv) * sizeof(double), c->stream));
-  if (diss) HIPCHK(hipMemsetAsync((double*)diss + c->nloc, 0, (c->nstate - c->nloc) * sizeof(double), c->stream));
-  double* const* pv = (double* const*)prod;
-  const double *u = (const double*)ub, *r = (const double*)dRe, *m = (const double*)dIm;
-  switch (c->key) {
-    case 6: energy_budget_launch<6, 2>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
-    case 8: energy_budget_launch<8, 2>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
-    case 10: energy_budget_launch<10, 2>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
-    case 12: energy_budget_launch<12, 2>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
-    case 106: energy_budget_launch<6, 3>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
-    case 108: energy_budget_launch<8, 3>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
-    default: energy_budget_launch<10, 3>(c, u, r, m, pv, (double*)diss, s, c->budget_wrk); break;
-  }
-  HIPCHK(hipGetLastError());
-  const double* out = c->budget_wrk + c->nloc + 9LL * c->nel + 2LL * c->ndim * nb;
-  HIPCHK(hipMemcpyAsync(integrals, out, 10 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-// comp_vort3 (the Rv files of outpost_ks, core/eigensolvers.f:629-637): k_vort writes bm1 x curl of q's velocity into g (1 or 3
-// fields of component stride gs), k_vort_avg gathers it, divides by the assembled unmasked mass and fills w
-static int vort_curl(nsk_ctx* c, const double* q, double* g, long long gs) {
-  switch (c->key) {
-    case 6: nsk::sens::launch_vort<6, 2>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
-    case 8: nsk::sens::launch_vort<8, 2>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
-    case 10: nsk::sens::launch_vort<10, 2>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
-    case 12: nsk::sens::launch_vort<12, 2>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
-    case 106: nsk::sens::launch_vort<6, 3>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
-    case 108: nsk::sens::launch_vort<8, 3>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
-    case 110: nsk::sens::launch_vort<10, 3>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); break;
-    default: return fail(NSK_EINVAL, "nsk_vorticity: unsupported lx1");
-  }
-  return 0;
-}
-static void vort_avg(nsk_ctx* c, const double* g, long long gs, double* w) {
-  const unsigned grid = (unsigned)((c->nstate + 255) / 256);
-  if (c->ndim == 2) hipLaunchKernelGGL(nsk::sens::k_vort_avg<2>, dim3(grid), dim3(256), 0, c->stream, c->d, g, gs, (const double*)c->vort_mass, w, (long long)c->nstate);
-  else hipLaunchKernelGGL(nsk::sens::k_vort_avg<3>, dim3(grid), dim3(256), 0, c->stream, c->d, g, gs, (const double*)c->vort_mass, w, (long long)c->nstate);
-}
-
-int nsk_vorticity(nsk_ctx* c, nsk_vec q, nsk_vec w) {
-  int rc = sens_ctx_ok(c, "nsk_vorticity");
-  if (rc) return rc;
-  if (!q || !w) return fail(NSK_EINVAL, "nsk_vorticity: bad argument");
-  if (q == w) return fail(NSK_EINVAL, "nsk_vorticity: the output may not be the input vector");
-  if (!c->xyz || !c->scratch) return fail(NSK_EINVAL, "nsk_vorticity: context holds no coordinates");
-  const unsigned grid = (unsigned)((c->nloc + 255) / 256);
-  if (!c->vort_mass) {                                           // once per context: nloc doubles, kept until nsk_finalize
-    if ((rc = dalloc(c, &c->vort_mass, (size_t)c->nloc))) return rc;
-    hipLaunchKernelGGL(nsk::sens::k_vort_mass, dim3(grid), dim3(256), 0, c->stream, c->d, c->d.bm1, c->vort_mass);
-  }
-  if ((rc = vort_curl(c, (const double*)q, c->scratch, c->nloc))) return rc;
-  vort_avg(c, c->scratch, c->nloc, (double*)w);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-int nsk_forced_map(nsk_ctx* c, int mode, nsk_vec fv, nsk_vec qv, nsk_vec force) {
-  int rc = sens_ctx_ok(c, "nsk_forced_map");
-  if (rc) return rc;
-  if (!fv || !qv || !force) return fail(NSK_EINVAL, "nsk_forced_map: bad argument");
-  if (mode != NSK_DIRECT && mode != NSK_ADJOINT) return fail(NSK_EINVAL, "nsk_forced_map: mode must be NSK_DIRECT or NSK_ADJOINT");
-  if (force == fv) return fail(NSK_EINVAL, "nsk_forced_map: the force may not be the output vector");
-  // eager time steps: the captured step graphs of the unforced maps stay as they are (and are not used here)
-  c->hstats = Stats{};
-  const int use_graph = c->use_graph;
-  c->force = (const double*)force;
-  c->use_graph = 0;
-  rc = run_map_adaptive(c, mode, (double*)fv, (const double*)qv);
-  c->use_graph = use_graph;
-  c->force = nullptr;
-  return rc;
-}
-
-// ---- the same post-processing on element shards, for the ranks living in this process (uparam(1) = 4.x under the MPI
-// decomposition of everything else).  n shards together, every vector argument an array of n handles (rank r's at [r]); n = 1
-// with a host or RCCL transport attached: one process per GPU.  dsavg on a shard: the field at component stride Dev::cs
-// (ghost slots behind its nloc entries), halo exchange (xchg_vel_at), gather, times the shard's minv (sliced from the parent:
-// the global multiplicity).  The exchanged work array is nsk_ctx::wv1 (ndim * cs doubles; the kernel-test hooks' buffer,
-// which no map reads or writes), so a map that follows finds its own work arrays as the last map left them.
-static int sens_group_ok(nsk_ctx** shards, int n, const char* who) {
-  if (!shards || n < 1 || n > 16) return fail(NSK_EINVAL, std::string(who) + ": bad argument");
-  for (int r = 0; r < n; ++r) {
-    if (!shards[r]) return fail(NSK_EINVAL, std::string(who) + ": bad argument");
-    if (!shards[r]->parent) return fail(NSK_EINVAL, std::string(who) + ": needs shard contexts");
-    if (shards[r]->key != shards[0]->key) return fail(NSK_EINVAL, std::string(who) + ": the shards differ in lx1");
-  }
-  return 0;
 }
 // out[k] = sum over ALL ranks of the m per-rank values vals[r * m + k]: rank order for the ranks of this process, the
 // transport's all-reduce between processes -- every rank receives the same values
@@ -3707,23 +3492,21 @@ static int group_dots(std::vector<nsk_ctx*>& G, int nq, const nsk_vec* const* p,
   return group_sum(G, loc.data(), nq, out);
 }
 
-int nsk_group_biorthogonalize(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, double* gamma_delta) {
-  int rc = sens_group_ok(shards, n, "nsk_group_biorthogonalize");
-  if (rc) return rc;
-  if (!dRe || !dIm || !aRe || !aIm) return fail(NSK_EINVAL, "nsk_group_biorthogonalize: four distinct vectors needed");
+static int sens_biorthogonalize(std::vector<nsk_ctx*>& G, const char* who, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, double* gamma_delta) {
+  const int n = (int)G.size();
+  int rc;
+  if (!dRe || !dIm || !aRe || !aIm) return sfail(who, "four distinct vectors needed");
   for (int r = 0; r < n; ++r)
-    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !distinct({dRe[r], dIm[r], aRe[r], aIm[r]}))
-      return fail(NSK_EINVAL, "nsk_group_biorthogonalize: four distinct vectors needed");
-  std::vector<nsk_ctx*> G(shards, shards + n);
-  double nn[2];
+    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !distinct({dRe[r], dIm[r], aRe[r], aIm[r]})) return sfail(who, "four distinct vectors needed");
+  double nn[2];                                                  // || d ||^2 = || dRe ||^2 + || dIm ||^2  (:459-465)
   { const nsk_vec* p[2] = {dRe, dIm}; if ((rc = group_dots(G, 2, p, p, nn))) return rc; }
-  if (!(nn[0] + nn[1] > 0.0)) return fail(NSK_EINVAL, "nsk_group_biorthogonalize: the direct mode is zero");
+  if (!(nn[0] + nn[1] > 0.0)) return sfail(who, "the direct mode is zero");
   const double s = 1.0 / std::sqrt(nn[0] + nn[1]);
   for (int r = 0; r < n; ++r) if ((rc = nsk_scal(G[r], dRe[r], s)) || (rc = nsk_scal(G[r], dIm[r], s))) return rc;
-  double v[4];                                                   // rr, ii, ri, ir
+  double v[4];                                                   // <a, d> = gamma + i delta  (:468-476): rr, ii, ri, ir
   { const nsk_vec* p[4] = {aRe, aIm, aRe, aIm}; const nsk_vec* q[4] = {dRe, dIm, dIm, dRe}; if ((rc = group_dots(G, 4, p, q, v))) return rc; }
   const double gamma = v[0] + v[1], delta = v[2] - v[3], den = gamma * gamma + delta * delta;
-  if (!(den > 0.0)) return fail(NSK_EINVAL, "nsk_group_biorthogonalize: the adjoint mode is orthogonal to the direct mode");
+  if (!(den > 0.0)) return sfail(who, "the adjoint mode is orthogonal to the direct mode");
   for (int r = 0; r < n; ++r) {
     nsk_ctx* c = G[r];
     hipLaunchKernelGGL(nsk::sens::k_cdiv, dim3((unsigned)((c->nstate + 255) / 256)), dim3(256), 0, c->stream, (double*)aRe[r], (double*)aIm[r],
@@ -3734,43 +3517,71 @@ int nsk_group_biorthogonalize(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dI
   for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
-
-int nsk_group_wavemaker(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* wm) {
-  int rc = sens_group_ok(shards, n, "nsk_group_wavemaker");
+int nsk_biorthogonalize(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, double* gamma_delta) {
+  int rc = sens_ctx_ok(c, "nsk_biorthogonalize");
   if (rc) return rc;
-  if (!dRe || !dIm || !aRe || !aIm || !wm) return fail(NSK_EINVAL, "nsk_group_wavemaker: bad argument");
+  std::vector<nsk_ctx*> G(1, c);
+  return sens_biorthogonalize(G, "nsk_biorthogonalize", &dRe, &dIm, &aRe, &aIm, gamma_delta);
+}
+int nsk_group_biorthogonalize(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, double* gamma_delta) {
+  int rc = sens_group_ok(shards, n, "nsk_group_biorthogonalize");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return sens_biorthogonalize(G, "nsk_group_biorthogonalize", dRe, dIm, aRe, aIm, gamma_delta);
+}
+
+static int sens_wavemaker(std::vector<nsk_ctx*>& G, const char* who, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* wm) {
+  const int n = (int)G.size();
+  if (!dRe || !dIm || !aRe || !aIm || !wm) return sfail(who, "bad argument");
   for (int r = 0; r < n; ++r) {
-    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !wm[r]) return fail(NSK_EINVAL, "nsk_group_wavemaker: bad argument");
-    if (wm[r] == dRe[r] || wm[r] == dIm[r] || wm[r] == aRe[r] || wm[r] == aIm[r])
-      return fail(NSK_EINVAL, "nsk_group_wavemaker: the output may not be one of the modes");
+    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !wm[r]) return sfail(who, "bad argument");
+    if (wm[r] == dRe[r] || wm[r] == dIm[r] || wm[r] == aRe[r] || wm[r] == aIm[r]) return sfail(who, "the output may not be one of the modes");
   }
   for (int r = 0; r < n; ++r) {
-    nsk_ctx* c = shards[r];
+    nsk_ctx* c = G[r];
     HIPCHK(hipMemsetAsync(wm[r], 0, c->nstate * sizeof(double), c->stream));
     hipLaunchKernelGGL(nsk::sens::k_wavemaker, dim3((unsigned)((c->nloc + 255) / 256)), dim3(256), 0, c->stream, (const double*)dRe[r],
                        (const double*)dIm[r], (const double*)aRe[r], (const double*)aIm[r], (double*)wm[r], c->nloc, c->ndim);
   }
   HIPCHK(hipGetLastError());
-  for (int r = 0; r < n; ++r) HIPCHK(hipStreamSynchronize(shards[r]->stream));
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+int nsk_wavemaker(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec wm) {
+  int rc = sens_ctx_ok(c, "nsk_wavemaker");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return sens_wavemaker(G, "nsk_wavemaker", &dRe, &dIm, &aRe, &aIm, &wm);
+}
+int nsk_group_wavemaker(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* wm) {
+  int rc = sens_group_ok(shards, n, "nsk_group_wavemaker");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return sens_wavemaker(G, "nsk_group_wavemaker", dRe, dIm, aRe, aIm, wm);
+}
+
+// element-local gradient of the velocity-mesh field f into g (ndim fields of component stride gs): k_sens_grad of the context's lx1
+static int sens_grad(nsk_ctx* c, const double* f, double* g, long long gs) {
+  DISPATCH_SENS(c->key, { nsk::sens::launch_sens_grad<N, NDIM>(c->stream, c->nel, c->d.D, c->xyz, f, g, c->nloc, gs); });
   return 0;
 }
 
 // parts: NULL or 4 n handles, rank-major (parts[4 r + k], k = tr, ti, pr, pi).  4 ndim halo exchanges of ndim components each.
-int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* sr, nsk_vec* si, nsk_vec* parts) {
-  int rc = sens_group_ok(shards, n, "nsk_group_bf_sensitivity");
-  if (rc) return rc;
-  if (!dRe || !dIm || !aRe || !aIm || !sr || !si) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: bad argument");
-  std::vector<nsk_ctx*> G(shards, shards + n);
-  const int nd = G[0]->ndim;
+static int sens_bf_sensitivity(std::vector<nsk_ctx*>& G, const char* who, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* sr,
+                               nsk_vec* si, nsk_vec* parts) {
+  const int n = (int)G.size(), nd = G[0]->ndim;
+  int rc;
+  if (!dRe || !dIm || !aRe || !aIm || !sr || !si) return sfail(who, "bad argument");
   for (int r = 0; r < n; ++r) {
-    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !sr[r] || !si[r]) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: bad argument");
+    if (!dRe[r] || !dIm[r] || !aRe[r] || !aIm[r] || !sr[r] || !si[r]) return sfail(who, "bad argument");
     const nsk_vec* pr = parts ? parts + 4 * r : nullptr;
-    if (pr && (!pr[0] || !pr[1] || !pr[2] || !pr[3])) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: parts needs four vectors per rank");
-    if (!G[r]->xyz || !G[r]->wv1) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: context holds no coordinates");
+    if (pr && (!pr[0] || !pr[1] || !pr[2] || !pr[3])) return sfail(who, "parts needs four vectors per rank");
+    if (!G[r]->xyz || !G[r]->wv1) return sfail(who, "context holds no coordinates");
     std::vector<const void*> all = {dRe[r], dIm[r], aRe[r], aIm[r], sr[r], si[r]};
     if (pr) all.insert(all.end(), pr, pr + 4);
-    if (!distinct(all)) return fail(NSK_EINVAL, "nsk_group_bf_sensitivity: inputs and outputs must be distinct vectors");
+    if (!distinct(all)) return sfail(who, "inputs and outputs must be distinct vectors");
   }
+  if (sens_key_ok(G[0]->key)) return sfail(who, "unsupported lx1");
   struct Rank { double* outs[6]; double *tR, *tI, *pR, *pI; const double* m[4]; };
   std::vector<Rank> R(n);
   double* base[16];
@@ -3781,12 +3592,13 @@ int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm
     k.outs[0] = (double*)sr[r]; k.outs[1] = (double*)si[r];
     for (int q = 0; q < 4; ++q) k.outs[2 + q] = pr ? (double*)pr[q] : nullptr;
     for (double* o : k.outs) if (o) HIPCHK(hipMemsetAsync(o, 0, c->nstate * sizeof(double), c->stream));
-    k.tR = pr ? k.outs[2] : k.outs[0]; k.tI = pr ? k.outs[3] : k.outs[1];
+    k.tR = pr ? k.outs[2] : k.outs[0]; k.tI = pr ? k.outs[3] : k.outs[1];   // transport (tr, ti) and production (pr, pi) terms
     k.pR = pr ? k.outs[4] : k.outs[0]; k.pI = pr ? k.outs[5] : k.outs[1];
     k.m[0] = (const double*)dRe[r]; k.m[1] = (const double*)dIm[r]; k.m[2] = (const double*)aRe[r]; k.m[3] = (const double*)aIm[r];
     base[r] = c->wv1;
   }
-  // kinds, weights and term order: nsk_bf_sensitivity
+  // kind 0 / 1: gradient of the direct mode (transport), kind 2 / 3: of the adjoint mode (production); sensitivity.f:215-256
+  // with d v / d z where the reference reads d w / d z in the transport term (:219, 222, 228, 231)
   for (int kind = 0; kind < 4; ++kind)
     for (int comp = 0; comp < nd; ++comp) {
       for (int r = 0; r < n; ++r)
@@ -3817,29 +3629,48 @@ int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm
   for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
+int nsk_bf_sensitivity(nsk_ctx* c, nsk_vec dRe, nsk_vec dIm, nsk_vec aRe, nsk_vec aIm, nsk_vec sr, nsk_vec si, nsk_vec* parts) {
+  int rc = sens_ctx_ok(c, "nsk_bf_sensitivity");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return sens_bf_sensitivity(G, "nsk_bf_sensitivity", &dRe, &dIm, &aRe, &aIm, &sr, &si, parts);
+}
+int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* sr, nsk_vec* si, nsk_vec* parts) {
+  int rc = sens_group_ok(shards, n, "nsk_group_bf_sensitivity");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return sens_bf_sensitivity(G, "nsk_group_bf_sensitivity", dRe, dIm, aRe, aIm, sr, si, parts);
+}
 
-// budget workspace of a shard: divergence field [cs] (ghost slots: it is averaged a second time), [9][nel] production partials,
-// [2 ndim][ceil(nloc / 256)] dissipation partials, 10 sums
-static size_t budget_wrk_size(const nsk_ctx* c) {
-  const long long nb = (c->nloc + 255) / 256;
-  return (size_t)(c->d.cs + 9LL * c->nel + 2LL * c->ndim * nb + 10);
+// budget workspace of a context (nsk_ctx::budget_wrk, allocated once), offsets in doubles: the divergence field [cs] at 0 (ghost
+// slots: it is averaged a second time), [9][nel] production partials, [2 ndim][ceil(nloc / 256)] dissipation partials, 10 sums
+struct BudgetWrk { size_t ppart, dpart, out, size; };
+static BudgetWrk budget_wrk_layout(const nsk_ctx* c) {
+  const size_t nb = (size_t)((c->nloc + 255) / 256);
+  BudgetWrk w;
+  w.ppart = (size_t)c->d.cs;
+  w.dpart = w.ppart + 9 * (size_t)c->nel;
+  w.out = w.dpart + 2 * (size_t)c->ndim * nb;
+  w.size = w.out + 10;
+  return w;
 }
 extern "C++" {
-// nsk_energy_budget's launches on the ranks of G: 2 halo exchanges per mode component (ndim gradient components, then the
-// divergence); the production terms are element-local.  ub, uR, uI, prod (rank-major, may be null), diss (entries may be null) per rank.
+// stability_energy_budget (core/postproc.f:657-872) on the ranks of G: per rank 1 + 6 ndim launches + 2 reductions, 2 halo
+// exchanges per mode component (ndim gradient components, then the divergence); the production terms are element-local.
+// ub, uR, uI, prod (rank-major, may be null), diss (may be null) per rank.
 template <int N, int NDIM>
-static int energy_budget_group_launch(std::vector<nsk_ctx*>& G, const nsk_vec* ub, const nsk_vec* uR, const nsk_vec* uI, const nsk_vec* prod,
-                                      const nsk_vec* diss, double s) {
+static int energy_budget_launch(std::vector<nsk_ctx*>& G, const nsk_vec* ub, const nsk_vec* uR, const nsk_vec* uI, const nsk_vec* prod,
+                                const nsk_vec* diss, double s) {
   const int n = (int)G.size();
   double *gbase[16], *dbase[16];
   int rc;
   for (int r = 0; r < n; ++r) {
     nsk_ctx* c = G[r];
-    double* ppart = c->budget_wrk + c->d.cs;
     const nsk_vec* pr = prod ? prod + (size_t)NDIM * r : nullptr;
     nsk::sens::BudgetProd bp{{pr ? (double*)pr[0] : nullptr, pr ? (double*)pr[1] : nullptr, pr && NDIM == 3 ? (double*)pr[NDIM - 1] : nullptr}};
     hipLaunchKernelGGL((nsk::sens::k_budget_prod<N, NDIM>), dim3(c->nel), dim3(nsk::sens::SensCfg<N, NDIM>::NT), 0, c->stream, c->d.D,
-                       c->xyz, (const double*)ub[r], (const double*)uR[r], (const double*)uI[r], c->d.bm1, bp, -0.5 * s, ppart, c->nloc);
+                       c->xyz, (const double*)ub[r], (const double*)uR[r], (const double*)uI[r], c->d.bm1, bp, -0.5 * s,
+                       c->budget_wrk + budget_wrk_layout(c).ppart, c->nloc);
     gbase[r] = c->wv1; dbase[r] = c->budget_wrk;
   }
   for (int k = 0; k < 2 * NDIM; ++k) {                           // u_R,x  u_I,x  u_R,y  u_I,y [ u_R,z  u_I,z ]
@@ -3857,93 +3688,103 @@ static int energy_budget_group_launch(std::vector<nsk_ctx*>& G, const nsk_vec* u
       nsk_ctx* c = G[r];
       const int nb = (int)((c->nloc + 255) / 256);
       const double* a = (const double*)((k & 1) ? uI[r] : uR[r]) + (size_t)(k >> 1) * c->nloc;
-      double* dpart = c->budget_wrk + c->d.cs + 9 * (size_t)c->nel;
+      // param(2) / param(1) = 1 / Re
       hipLaunchKernelGGL(nsk::sens::k_budget_diss, dim3(nb), dim3(256), 0, c->stream, c->d, (const double*)c->budget_wrk, a,
-                         diss ? (double*)diss[r] : nullptr, 0.5 * c->d.nu * s, k == 0 ? 1 : 0, dpart + (size_t)k * nb);
+                         diss ? (double*)diss[r] : nullptr, 0.5 * c->d.nu * s, k == 0 ? 1 : 0,
+                         c->budget_wrk + budget_wrk_layout(c).dpart + (size_t)k * nb);
     }
   }
   for (nsk_ctx* c : G) {
     const int nb = (int)((c->nloc + 255) / 256);
-    double* ppart = c->budget_wrk + c->d.cs;
-    double* dpart = ppart + 9 * (size_t)c->nel;
-    double* out = dpart + 2 * NDIM * (size_t)nb;
-    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)ppart, 9, c->nel, out);
-    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)dpart, 1, 2 * NDIM * nb, out + 9);
+    const BudgetWrk w = budget_wrk_layout(c);
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)(c->budget_wrk + w.ppart), 9, c->nel, c->budget_wrk + w.out);
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)(c->budget_wrk + w.dpart), 1, 2 * NDIM * nb, c->budget_wrk + w.out + 9);
   }
   return 0;
 }
 }  // extern "C++"
 
 // prod: NULL or ndim n handles, rank-major (prod[ndim r + c]); diss: NULL or n handles.  integrals[10]: sums over all ranks.
-int nsk_group_energy_budget(nsk_ctx** shards, int n, nsk_vec* ub, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* prod, nsk_vec* diss, double* integrals) {
-  int rc = sens_group_ok(shards, n, "nsk_group_energy_budget");
-  if (rc) return rc;
-  if (!ub || !dRe || !dIm || !integrals) return fail(NSK_EINVAL, "nsk_group_energy_budget: bad argument (ub, dRe, dIm and integrals are required)");
-  std::vector<nsk_ctx*> G(shards, shards + n);
-  const int nd = G[0]->ndim, key = G[0]->key;
+static int sens_energy_budget(std::vector<nsk_ctx*>& G, const char* who, nsk_vec* ub, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* prod, nsk_vec* diss,
+                              double* integrals) {
+  const int n = (int)G.size(), nd = G[0]->ndim;
+  int rc;
+  if (!ub || !dRe || !dIm || !integrals) return sfail(who, "bad argument (ub, dRe, dIm and integrals are required)");
   for (int r = 0; r < n; ++r) {
     nsk_ctx* c = G[r];
-    if (!ub[r] || !dRe[r] || !dIm[r]) return fail(NSK_EINVAL, "nsk_group_energy_budget: bad argument (ub, dRe, dIm and integrals are required)");
-    if (prod) for (int k = 0; k < nd; ++k) if (!prod[(size_t)nd * r + k]) return fail(NSK_EINVAL, "nsk_group_energy_budget: prod needs ndim vectors per rank");
-    if (diss && !diss[r]) return fail(NSK_EINVAL, "nsk_group_energy_budget: diss needs one vector per rank");
-    if (!c->xyz || !c->wv1) return fail(NSK_EINVAL, "nsk_group_energy_budget: context holds no coordinates");
+    if (!ub[r] || !dRe[r] || !dIm[r]) return sfail(who, "bad argument (ub, dRe, dIm and integrals are required)");
+    if (prod) for (int k = 0; k < nd; ++k) if (!prod[(size_t)nd * r + k]) return sfail(who, "prod needs ndim vectors per rank");
+    if (diss && !diss[r]) return sfail(who, "diss needs one vector per rank");
+    if (!c->xyz || !c->wv1) return sfail(who, "context holds no coordinates");
     std::vector<const void*> outs;
     if (prod) outs.insert(outs.end(), prod + (size_t)nd * r, prod + (size_t)nd * (r + 1));
     if (diss) outs.push_back(diss[r]);
     for (const void* o : outs)
-      if (o == ub[r] || o == dRe[r] || o == dIm[r]) return fail(NSK_EINVAL, "nsk_group_energy_budget: an output may not be one of the inputs");
-    if (!distinct(outs)) return fail(NSK_EINVAL, "nsk_group_energy_budget: the outputs must be distinct vectors");
+      if (o == ub[r] || o == dRe[r] || o == dIm[r]) return sfail(who, "an output may not be one of the inputs");
+    if (!distinct(outs)) return sfail(who, "the outputs must be distinct vectors");
   }
-  if (key != 6 && key != 8 && key != 10 && key != 12 && key != 106 && key != 108 && key != 110)
-    return fail(NSK_EINVAL, "nsk_group_energy_budget: unsupported lx1");
-  double nn[2];                                                  // alpha^2 over all ranks
+  if (sens_key_ok(G[0]->key)) return sfail(who, "unsupported lx1");
+  double nn[2];                                                  // alpha^2 = ||dRe||^2 + ||dIm||^2 over all ranks  (postproc.f:703-707)
   { const nsk_vec* p[2] = {dRe, dIm}; if ((rc = group_dots(G, 2, p, p, nn))) return rc; }
-  if (!(nn[0] + nn[1] > 0.0)) return fail(NSK_EINVAL, "nsk_group_energy_budget: the direct mode is zero");
+  if (!(nn[0] + nn[1] > 0.0)) return sfail(who, "the direct mode is zero");
+  // the mode divided by alpha (the reference's comment; its code multiplies): every term is quadratic in the mode, so the scale
+  // enters as 1 / alpha^2 on the weights and the inputs are left as they are
   const double s = 1.0 / (nn[0] + nn[1]);
   for (int r = 0; r < n; ++r) {
     nsk_ctx* c = G[r];
-    if (!c->budget_wrk && (rc = dalloc(c, &c->budget_wrk, budget_wrk_size(c)))) return rc;
+    if (!c->budget_wrk && (rc = dalloc(c, &c->budget_wrk, budget_wrk_layout(c).size))) return rc;
     const long long nv = (long long)nd * c->nloc;
     if (prod) for (int k = 0; k < nd; ++k) HIPCHK(hipMemsetAsync((double*)prod[(size_t)nd * r + k] + nv, 0, (c->nstate - nv) * sizeof(double), c->stream));
     if (diss) HIPCHK(hipMemsetAsync((double*)diss[r] + c->nloc, 0, (c->nstate - c->nloc) * sizeof(double), c->stream));
   }
-  switch (key) {
-    case 6: rc = energy_budget_group_launch<6, 2>(G, ub, dRe, dIm, prod, diss, s); break;
-    case 8: rc = energy_budget_group_launch<8, 2>(G, ub, dRe, dIm, prod, diss, s); break;
-    case 10: rc = energy_budget_group_launch<10, 2>(G, ub, dRe, dIm, prod, diss, s); break;
-    case 12: rc = energy_budget_group_launch<12, 2>(G, ub, dRe, dIm, prod, diss, s); break;
-    case 106: rc = energy_budget_group_launch<6, 3>(G, ub, dRe, dIm, prod, diss, s); break;
-    case 108: rc = energy_budget_group_launch<8, 3>(G, ub, dRe, dIm, prod, diss, s); break;
-    default: rc = energy_budget_group_launch<10, 3>(G, ub, dRe, dIm, prod, diss, s); break;
-  }
+  DISPATCH_SENS(G[0]->key, { rc = energy_budget_launch<N, NDIM>(G, ub, dRe, dIm, prod, diss, s); });
   if (rc) return rc;
   HIPCHK(hipGetLastError());
   std::vector<double> loc((size_t)10 * n);
   for (int r = 0; r < n; ++r) {
     nsk_ctx* c = G[r];
-    const double* out = c->budget_wrk + budget_wrk_size(c) - 10;
-    HIPCHK(hipMemcpyAsync(&loc[(size_t)10 * r], out, 10 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&loc[(size_t)10 * r], c->budget_wrk + budget_wrk_layout(c).out, 10 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   }
   for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
   return group_sum(G, loc.data(), 10, integrals);
 }
-
-// nsk_vorticity on shards: ONE halo exchange per call, all curl components in one message per peer (the exchanged array is wv1,
-// as in nsk_group_bf_sensitivity).  The divisor is the mass assembled over ALL ranks: built at a group's first call (bm1 into
-// wv1, one exchange of one component, gather) and kept by every shard until it is finalised.
-int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w) {
-  int rc = sens_group_ok(shards, n, "nsk_group_vorticity");
+int nsk_energy_budget(nsk_ctx* c, nsk_vec ub, nsk_vec dRe, nsk_vec dIm, nsk_vec* prod, nsk_vec diss, double* integrals) {
+  int rc = sens_ctx_ok(c, "nsk_energy_budget");
   if (rc) return rc;
-  if (!q || !w) return fail(NSK_EINVAL, "nsk_group_vorticity: bad argument");
+  std::vector<nsk_ctx*> G(1, c);
+  return sens_energy_budget(G, "nsk_energy_budget", &ub, &dRe, &dIm, prod, diss ? &diss : nullptr, integrals);
+}
+int nsk_group_energy_budget(nsk_ctx** shards, int n, nsk_vec* ub, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* prod, nsk_vec* diss, double* integrals) {
+  int rc = sens_group_ok(shards, n, "nsk_group_energy_budget");
+  if (rc) return rc;
   std::vector<nsk_ctx*> G(shards, shards + n);
-  const int key = G[0]->key;
+  return sens_energy_budget(G, "nsk_group_energy_budget", ub, dRe, dIm, prod, diss, integrals);
+}
+
+// comp_vort3 (the Rv files of outpost_ks, core/eigensolvers.f:629-637): k_vort writes bm1 x curl of q's velocity into g (1 or 3
+// fields of component stride gs), k_vort_avg gathers it, divides by the assembled unmasked mass and fills w
+static int vort_curl(nsk_ctx* c, const double* q, double* g, long long gs) {
+  DISPATCH_SENS(c->key, { nsk::sens::launch_vort<N, NDIM>(c->stream, c->nel, c->d.D, c->xyz, q, c->d.bm1, g, c->nloc, gs); });
+  return 0;
+}
+static void vort_avg(nsk_ctx* c, const double* g, long long gs, double* w) {
+  const unsigned grid = (unsigned)((c->nstate + 255) / 256);
+  if (c->ndim == 2) hipLaunchKernelGGL(nsk::sens::k_vort_avg<2>, dim3(grid), dim3(256), 0, c->stream, c->d, g, gs, (const double*)c->vort_mass, w, (long long)c->nstate);
+  else hipLaunchKernelGGL(nsk::sens::k_vort_avg<3>, dim3(grid), dim3(256), 0, c->stream, c->d, g, gs, (const double*)c->vort_mass, w, (long long)c->nstate);
+}
+// ONE halo exchange per call, all curl components in one message per peer.  The divisor is the mass assembled over ALL ranks:
+// built at a group's first call (bm1 into wv1, one exchange of one component, gather) and kept by every context until it is
+// finalised.
+static int sens_vorticity(std::vector<nsk_ctx*>& G, const char* who, nsk_vec* q, nsk_vec* w) {
+  const int n = (int)G.size();
+  int rc;
+  if (!q || !w) return sfail(who, "bad argument");
   for (int r = 0; r < n; ++r) {
-    if (!q[r] || !w[r]) return fail(NSK_EINVAL, "nsk_group_vorticity: bad argument (q and w need one vector per rank)");
-    if (q[r] == w[r]) return fail(NSK_EINVAL, "nsk_group_vorticity: the output may not be the input vector");
-    if (!G[r]->xyz || !G[r]->wv1) return fail(NSK_EINVAL, "nsk_group_vorticity: context holds no coordinates");
+    if (!q[r] || !w[r]) return sfail(who, "bad argument (q and w need one vector per rank)");
+    if (q[r] == w[r]) return sfail(who, "the output may not be the input vector");
+    if (!G[r]->xyz || !G[r]->wv1) return sfail(who, "context holds no coordinates");
   }
-  if (key != 6 && key != 8 && key != 10 && key != 12 && key != 106 && key != 108 && key != 110)
-    return fail(NSK_EINVAL, "nsk_group_vorticity: unsupported lx1");
+  if (sens_key_ok(G[0]->key)) return sfail(who, "unsupported lx1");
   double* base[16];
   for (int r = 0; r < n; ++r) base[r] = G[r]->wv1;
   bool have = true;
@@ -3964,6 +3805,35 @@ int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w) {
   HIPCHK(hipGetLastError());
   for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
+}
+int nsk_vorticity(nsk_ctx* c, nsk_vec q, nsk_vec w) {
+  int rc = sens_ctx_ok(c, "nsk_vorticity");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return sens_vorticity(G, "nsk_vorticity", &q, &w);
+}
+int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w) {
+  int rc = sens_group_ok(shards, n, "nsk_group_vorticity");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return sens_vorticity(G, "nsk_group_vorticity", q, w);
+}
+
+int nsk_forced_map(nsk_ctx* c, int mode, nsk_vec fv, nsk_vec qv, nsk_vec force) {
+  int rc = sens_ctx_ok(c, "nsk_forced_map");
+  if (rc) return rc;
+  if (!fv || !qv || !force) return fail(NSK_EINVAL, "nsk_forced_map: bad argument");
+  if (mode != NSK_DIRECT && mode != NSK_ADJOINT) return fail(NSK_EINVAL, "nsk_forced_map: mode must be NSK_DIRECT or NSK_ADJOINT");
+  if (force == fv) return fail(NSK_EINVAL, "nsk_forced_map: the force may not be the output vector");
+  // eager time steps: the captured step graphs of the unforced maps stay as they are (and are not used here)
+  c->hstats = Stats{};
+  const int use_graph = c->use_graph;
+  c->force = (const double*)force;
+  c->use_graph = 0;
+  rc = run_map_adaptive(c, mode, (double*)fv, (const double*)qv);
+  c->use_graph = use_graph;
+  c->force = nullptr;
+  return rc;
 }
 
 // nsk_forced_map on shards: eager sharded steps with k_add_force behind the convection kernel of every rank (group_step).  The
