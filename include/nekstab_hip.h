@@ -300,6 +300,9 @@ typedef struct {
   long long convfuse_steps;                 /* time steps since init that ran convection and the velocity right-hand side in ONE launch (k_convect_rhs, option
                                                "conv_fuse") instead of k_convect + k_rhs (a redone map counts again).  0 wherever the option does not apply:
                                                hexahedra, shards, forced maps, the persistent velocity solve */
+  long long helmpack_steps;                 /* time steps since init whose velocity solve ran on the packed scratch arrays (option "helm_pack": 16-byte
+                                               accesses in k_helm / k_helm_tail / k_pres_rhs; a redone map counts again).  0 wherever the option does not
+                                               apply: hexahedra, shards, the persistent velocity solve, and lx1 = 12 unless the option is 1 */
 } nsk_stats;
 int nsk_get_stats(nsk_ctx* ctx, nsk_stats* s);
 

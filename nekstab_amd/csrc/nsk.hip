@@ -155,6 +155,8 @@ struct nsk_ctx {
   int tail_off_h = 0, tail_off_p = 0;    // heads = median + these (options "tail_off_h" / "tail_off_p": tests push work into the tails with negative values)
   long long tail_maps = 0;
   long long absorb_maps = 0;             // maps run with the deferred update of the projection space (option "proj_absorb")
+  long long helmpack_steps = 0;          // time steps whose velocity solve ran on the packed scratch arrays (option "helm_pack")
+  int helm_pack = -1;                   // 16-byte accesses in the quadrilateral velocity solve (k_helm<N, true>, k_helm_tail<N, true>, k_pres_rhs<N, .., true>): -1 = where allowed and where it pays (helmpack_on: lx1 <= 10), 0 = never, 1 = wherever allowed; option "helm_pack"
   long long convfuse_steps = 0;          // time steps run with convection and the velocity right-hand side in one launch (option "conv_fuse")
   long long sb_maps = 0, sb_steps = 0, sb_launch_h = 0, sb_launch_p = 0;     // maps / time steps run on per-step budgets and their budgeted launches (diagnostics)
   bool last_map_per_step = false;        // the map just run took the per-step budgets
@@ -1032,7 +1034,8 @@ static void launch_rhs_absorb(nsk_ctx* c, const Dev& d, const StepCoef& sc) {   
 template <int N>
 static void launch_pres_rhs_absorb(nsk_ctx* c, const Dev& d, const StepCoef& sc, int helm_par, int check_helm) {      // (quadrilaterals only: absorb_on)
   if (c->ndim != 2) return;
-  hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
+  if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, true, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
+  else hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
 }
 template <int N>
 static void launch_divgs_t(nsk_ctx* c, const Dev& d, int j) {
@@ -1091,6 +1094,17 @@ static bool convfuse_on(const nsk_ctx* c) {
   if (c->conv_fuse == 0 || c->ndim != 2 || c->parent || c->d.nranks > 1 || c->fused || c->force || c->in_test) return false;
   return true;
 }
+// The velocity solve on packed scratch arrays (option "helm_pack"): quadrilaterals on one rank whose solve is launched per
+// iteration or ends in the persistent tail.  Shards (the halo exchange and the totals index rows), hexahedra and the persistent
+// solve (k_helm_fused has its own body) keep the component-major layout.  The arrays are scratch within one solve, so the two
+// layouts share the allocations and nothing is converted when the option changes.
+// lx1 = 12 takes it only when the option is 1: k_helm<12, true> needs 142 registers where k_helm<12> needs 124, one wavefront per
+// SIMD fewer, and that kernel is close to its bandwidth bound (config 3: 18.9 -> 20.2 us per launch, -3 % matvecs/s).
+static bool helmpack_on(const nsk_ctx* c) {
+  if (c->helm_pack == 0 || c->ndim != 2 || c->parent || c->d.nranks > 1 || c->fused) return false;
+  if (c->helm_pack < 0 && c->N > 10) return false;
+  return true;
+}
 template <int N>
 static void launch_convect_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool absorb) {      // (quadrilaterals only: convfuse_on)
   if (c->ndim != 2) return;
@@ -1100,7 +1114,8 @@ static void launch_convect_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, boo
 template <int N>
 static void launch_pres_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, int helm_par, int check_helm) {      // (quadrilaterals only: the plain k_pres_rhs with Dev::bstep_late)
   if (c->ndim != 2) return;
-  hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, false>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
+  if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, false, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
+  else hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, false>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
 }
 // A map ends, or something is about to read, copy or reset the space: the update its last step left behind goes in with the
 // standalone kernel (one launch per map), and the context looks as it does without the option.
@@ -1243,6 +1258,8 @@ static void launch_helm_iter(nsk_ctx* c, const Dev& d, const StepCoef& sc, int i
       }
     }
     if constexpr (N <= 10) hipLaunchKernelGGL(nsk::k3::k_helm<N>, dim3(c->nblk), dim3(nsk::k3::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
+  } else if (d.helm_pk) {
+    hipLaunchKernelGGL((nsk::k2::k_helm<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
   } else {
     hipLaunchKernelGGL(nsk::k2::k_helm<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
   }
@@ -1432,7 +1449,8 @@ static int tails_resident(nsk_ctx* c, int ncu) {
   const size_t sh = (size_t)c->d.coarse_lda * sizeof(double);
   const int nit = c->d.coarse_lda / 256;
   int ph = 0, pp = 0;
-  hipError_t e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, nsk::k2::k_helm_tail<N>, nsk::k2::Cfg<N>::NT, 0), e2 = hipErrorUnknown;
+  hipError_t e1 = helmpack_on(c) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, true>), nsk::k2::Cfg<N>::NT, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, false>), nsk::k2::Cfg<N>::NT, 0), e2 = hipErrorUnknown;
   if (nit <= 3) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 3>), nsk::k2::Cfg<N>::NT, sh);
   else if (nit <= 6) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 6>), nsk::k2::Cfg<N>::NT, sh);
   else if (nit <= 9) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 9>), nsk::k2::Cfg<N>::NT, sh);
@@ -1479,7 +1497,8 @@ static bool tails_on(nsk_ctx* c) {
 template <int N>
 static void launch_helm_tail(nsk_ctx* c, const Dev& d, const StepCoef& sc, int it0, int it_end) {
   if (c->ndim != 2) return;
-  hipLaunchKernelGGL(nsk::k2::k_helm_tail<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
+  if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_helm_tail<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
+  else hipLaunchKernelGGL(nsk::k2::k_helm_tail<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
 }
 template <int N>
 static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double scale, int min_iter, int ord, bool start) {
@@ -1517,6 +1536,10 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
   // one launch for convection + right-hand side (convfuse_on); it reads *bstep in every workgroup, so this step's k_pres_rhs
   // advances it (once per step in every launch mode: budgets, tails, eager, captured)
   const bool cfuse = convfuse_on(c);
+  // the velocity solve on the packed scratch arrays (helmpack_on): k_helm, k_helm_tail and this step's k_pres_rhs agree on it
+  const bool hpk = helmpack_on(c);
+  d.helm_pk = da.helm_pk = hpk ? 1 : 0;
+  if (hpk && !in_map) c->helmpack_steps++;
   if (cfuse) da.bstep_late = ((d.bf_stride || d.forb) && adjoint != 2) ? 1 : 0;
   if (cfuse && !in_map) c->convfuse_steps++;            // (the steps of a map are counted by run_map: a captured step is replayed)
   int nh = hc ? c->max_helm : (nh_over > 0 ? nh_over : c->cur_helm[sc.cls]);
@@ -1558,6 +1581,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       if (tail) { launch_helm_tail<N>(c, d, sc, nh, c->max_helm); nh = c->max_helm; }
       if (absorb) launch_pres_rhs_absorb<N>(c, da, sc, (nh - 1) & 1, nh - 1);
       else if (cfuse) launch_pres_rhs<N>(c, da, sc, (nh - 1) & 1, nh - 1);
+      else if (hpk) launch_pres_rhs<N>(c, d, sc, (nh - 1) & 1, nh - 1);
       else hipLaunchKernelGGL(k_pres_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc, (nh - 1) & 1, nh - 1);
     }
   });
@@ -1729,6 +1753,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   }
   if (absorb_on(c)) { c->up_host = true; c->absorb_maps++; }
   if (convfuse_on(c)) c->convfuse_steps += c->nsteps;
+  if (helmpack_on(c)) c->helmpack_steps += c->nsteps;
   for (int istep = 1; istep <= c->nsteps; ++istep) {
     if (per_step) {
       HIPCHK(hipGraphLaunch(plan[istep - 1], c->stream));
@@ -2566,6 +2591,12 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
     c->conv_fuse = (int)value;
     invalidate_graphs(c);
   }
+  else if (n == "helm_pack") {
+    if (value != -1.0 && value != 0.0 && value != 1.0) return fail(NSK_EINVAL, "helm_pack: -1, 0 or 1");
+    c->helm_pack = (int)value;
+    c->tail_ok = -1;                  // (the residency of the tail is asked of the instantiation that runs)
+    invalidate_graphs(c);
+  }
   else if (n == "fuse2_start") { c->fuse2_start = (int)value; invalidate_graphs(c); }
   else if (n == "sb_pct") { c->sb_pct = (int)value; }
   else if (n == "skip_close") { c->skip_close = (int)value; invalidate_graphs(c); }
@@ -2730,6 +2761,7 @@ int nsk_get_stats(nsk_ctx* c, nsk_stats* s) {
   s->tail_maps = c->tail_maps;
   s->absorb_maps = c->absorb_maps;
   s->convfuse_steps = c->convfuse_steps;
+  s->helmpack_steps = c->helmpack_steps;
   s->zero_arrays = (long long)c->d.zmask | ((long long)c->d.bfmask << 12);
   s->step_budget_helm_mean = c->sb_maps ? (double)c->sb_launch_h / ((double)c->sb_steps) : 0.0;
   s->step_budget_pres_mean = c->sb_maps ? (double)c->sb_launch_p / ((double)c->sb_steps) : 0.0;
@@ -3900,7 +3932,11 @@ int nsk_debug_stamps(nsk_ctx* c, unsigned long long* out, int nblk_max) {
     if (nblk_max < 0) {
       Dev dd = d; dd.tol_helm = 0.0; dd.tol_relative = 0;
       const StepCoef sc = make_coef(c, 3, 0);
-      for (int r = 0; r < 6; ++r) hipLaunchKernelGGL(k_helm<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, dd, sc, r, (const double*)d.rloc);
+      const bool hpk = c->ndim == 2 && helmpack_on(c);       // the instantiation the context's steps run (option "helm_pack")
+      for (int r = 0; r < 6; ++r) {
+        if (hpk) hipLaunchKernelGGL((nsk::k2::k_helm<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, dd, sc, r, (const double*)d.rloc);
+        else hipLaunchKernelGGL(k_helm<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, dd, sc, r, (const double*)d.rloc);
+      }
       nblk_max = -nblk_max;
     } else if (std::getenv("NSK_STAMP_KERNEL") && std::string(std::getenv("NSK_STAMP_KERNEL")) == "divgs_w") {
       for (int r = 0; r < 5; ++r) launch_divgs3<N>(c, d, c->nblk, (const double*)d.yl, c->wp2, -1, 0, 3);
@@ -4045,6 +4081,7 @@ int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
   float ms = 0.f;
   if (n == "helm" || n == "helm_wg") {
     d.tol_helm = 0.0; d.tol_relative = 0;                       // never converge: every launch does full work
+    d.helm_pk = helmpack_on(c) ? 1 : 0;                         // the instantiation the context's steps run (option "helm_pack")
     const StepCoef sc = make_coef(c, 3, 0);
     const int cyc = 8;
     const int keep_pf = c->helm_pf;

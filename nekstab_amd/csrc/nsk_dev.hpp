@@ -157,6 +157,7 @@ struct Dev {
   const double* wraw;
   int absorb;                    // set per launch: the update of the projection space is deferred into the next step's readers (GmresScal::up_*)
   int bstep_late;                // set per launch (k_pres_rhs): this launch advances *bstep -- the steps whose k_convect_rhs read it in every workgroup and so could not
+  int helm_pk;                   // host side only (which instantiation is launched): the velocity solve of this step runs on the packed scratch arrays (option "helm_pack")
   int uc_start;                  // set per launch (A_0 only): the solve starts inside k_schwarz_uc (g' raw in Wr, written by k_proj_apply_e)
   GmresScal* gsc;
   // projection onto previous pressure solutions (E-orthonormal)

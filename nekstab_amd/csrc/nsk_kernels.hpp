@@ -115,6 +115,22 @@ __device__ inline void sum_partials(const double* part, int n, double (&out)[NV]
   for (int q = 0; q < NV; ++q) out[q] = v[q];
 }
 
+// the same sums from NP arrays of row PAIRS (double2: rows 2 q and 2 q + 1 of block k side by side), same order per row
+template <int NP>
+__device__ inline void sum_partials_pairs(const double2* part, int n, double (&out)[2 * NP], double* sred,
+                                          int tid, int nthreads) {
+  double v[2 * NP];
+#pragma unroll
+  for (int q = 0; q < NP; ++q) {
+    double s0 = 0.0, s1 = 0.0;
+    for (int k = tid; k < n; k += nthreads) { const double2 a = part[(size_t)q * n + k]; s0 += a.x; s1 += a.y; }
+    v[2 * q] = s0; v[2 * q + 1] = s1;
+  }
+  block_reduce<2 * NP>(v, sred, tid, nthreads);
+#pragma unroll
+  for (int q = 0; q < 2 * NP; ++q) out[q] = v[q];
+}
+
 // sums nq arrays of n per-block partials into sh[0..nq): waves take different q, fixed order
 __device__ inline void sum_partials_multi(const double* part, int n, int nq, double* sh, int tid, int nthreads) {
   const int lane = tid & 63, w = tid >> 6, nw = nthreads >> 6;
@@ -236,6 +252,39 @@ __device__ inline GsVals gs_load(const double* __restrict__ f, const int4 t, lon
 __device__ inline double gs_sum(const GsVals& v, const double* __restrict__ f, const Dev& d, const int4 t, long long l) {
   if (t.x < 0) return gs_csr(f, d, l);
   return ((v.a + v.b) + v.c) + v.d;
+}
+
+// The same gather on a component-interleaved field f[2 l + c] (option "helm_pack"): one 16-byte load per neighbour brings both
+// components, the sums per component keep the order ((a + b) + c) + d; the CSR fallback indexes f[2 id + c].
+struct GsVals2 { double2 a, b, c, d; };
+__device__ inline GsVals2 gs_load2(const double2* __restrict__ f, const int4 t, long long l) {
+  GsVals2 v;                          // (if-form: `cond ? f[i] : zero` on a double2 selects between ADDRESSES, the zero's on the stack)
+  v.a = f[t.x >= 0 ? t.x : l];
+  v.b = v.c = v.d = make_double2(0.0, 0.0);
+  if (t.y >= 0) v.b = f[t.y];
+  if (t.z >= 0) v.c = f[t.z];
+  if (t.w >= 0) v.d = f[t.w];
+  return v;
+}
+__device__ inline double gs_csr2(const double* __restrict__ f, const Dev& d, long long l, int c) {
+  const int o0 = d.gs_off[l], o1 = d.gs_off[l + 1];
+  double s = 0.0;
+  for (int k0 = o0; k0 < o1; k0 += 8) {
+    int id[8];
+    double v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) id[q] = (k0 + q < o1) ? d.gs_idx[k0 + q] : -1;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = (id[q] >= 0) ? f[2 * (size_t)id[q] + c] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (id[q] >= 0) s += v[q];
+  }
+  return s;
+}
+__device__ inline double2 gs_sum2(const GsVals2& v, const double2* __restrict__ f, const Dev& d, const int4 t, long long l) {
+  if (t.x < 0) return make_double2(gs_csr2((const double*)f, d, l, 0), gs_csr2((const double*)f, d, l, 1));
+  return make_double2(((v.a.x + v.b.x) + v.c.x) + v.d.x, ((v.a.y + v.b.y) + v.c.y) + v.d.y);
 }
 
 // ---------------------------------------------------------------------------
@@ -953,7 +1002,13 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_convect_rhs(Dev d, StepCoef sc) 
 // contributions, which is exact for continuous z.   [UPSTREAM hmholtz.f cggo]
 //   hscal[par][c*4 + {0:gamma,1:alpha,2:done,3:res}]
 // ---------------------------------------------------------------------------
-template <int N>
+//
+// PK (option "helm_pack", quadrilaterals on one rank): the scratch arrays of the solve in a layout whose accesses are 16 bytes
+// wide.  hr, hp, hs, hx and hwl[par] are component-interleaved ([2 l + c]: one double2 per array and node, four double2 gathers
+// for both components), and the partial sums are stored as row pairs hpart[par][4][nblk] of double2 ({0,1} {2,3} {4,5} {6,7};
+// the (b, b) pair is loaded by launch 1 only) wherever the launches read them (not use_tot: k_tot2 sums whole rows).  Same
+// allocations, same arithmetic in the same order => the same bits; nothing but the solve and k_pres_rhs<.., PK> sees the arrays.
+template <int N, bool PK = false>
 __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int it, const double* rhs, const unsigned bx_, const unsigned gx_) {
   // (shards with halo / interior overlap launch the boundary workgroups first, the rest with an offset; XCD-contiguous runs of
   //  element blocks: the neighbours' edge values are L2 hits where the grid is larger than the caches, config 3)
@@ -992,10 +1047,16 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
     bm = d.bm1[l]; g1 = d.g1[l]; g2 = d.g2[l]; g4 = d.g4[l]; mk = d.mask[l]; mi = d.minv[l];
     di = d.dinv[(size_t)(sc.k - 1) * d.nloc + l];
     if (it > 0) {
+      if constexpr (PK) {
+        const double2 r2 = ((const double2*)d.hr)[l], p2 = ((const double2*)d.hp)[l], s2 = ((const double2*)d.hs)[l], x2 = ((const double2*)d.hx)[l];
+        rold[0] = r2.x; rold[1] = r2.y; pold[0] = p2.x; pold[1] = p2.y;
+        sold[0] = s2.x; sold[1] = s2.y; xold[0] = x2.x; xold[1] = x2.y;
+      } else {
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const long long lc = c * nl + l;
-        rold[c] = d.hr[lc]; pold[c] = d.hp[lc]; sold[c] = d.hs[lc]; xold[c] = d.hx[lc];
+        for (int c = 0; c < 2; ++c) {
+          const long long lc = c * nl + l;
+          rold[c] = d.hr[lc]; pold[c] = d.hp[lc]; sold[c] = d.hs[lc]; xold[c] = d.hx[lc];
+        }
       }
     }
   }
@@ -1006,6 +1067,15 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
     if (d.nranks > 1 || d.use_tot) {    // totals: all-reduced over ranks, or summed once by k_tot2 (many workgroups)
 #pragma unroll
       for (int q = 0; q < 8; ++q) ps[q] = (tid == 0) ? d.htot[ppar * 8 + q] : 0.0;
+    } else if constexpr (PK) {
+      const double2* part = (const double2*)(d.hpart + (size_t)ppar * 8 * d.nblk);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (q < 3 || it == 1) {         // (b, b), pair 3: the reference norms, read by launch 1 only (uniform: a launch argument)
+          if (tid < d.nblk) { const double2 a = part[(size_t)q * d.nblk + tid]; ps[2 * q] = a.x; ps[2 * q + 1] = a.y; }
+          if (tid + NT < d.nblk) { const double2 b = part[(size_t)q * d.nblk + tid + NT]; ps1[2 * q] = b.x; ps1[2 * q + 1] = b.y; }
+        }
+      }
     } else {
       const double* part = d.hpart + (size_t)ppar * 8 * d.nblk;
 #pragma unroll
@@ -1023,11 +1093,20 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
   NSK_STAMP(1);
   // ---- phase B: gathers of the neighbours' unassembled values (need the table entry)
   GsVals gv[2], gb[2];
+  GsVals2 gw;
+  const double2* wl2 = (const double2*)(d.hwl + (size_t)ppar * 2 * nl);       // PK: the previous launch's A z, both components
   if (act) {
+    if constexpr (PK) {
+      if (it == 0) {                  // (the right-hand sides stay component-major: they are k_rhs's arrays)
 #pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      if (it == 0) { gv[c] = gs_load(rhs + c * nl, tab, l); gb[c] = gs_load(d.bloc + c * nl, tab, l); }
-      else gv[c] = gs_load(d.hwl + ((size_t)ppar * 2 + c) * nl, tab, l);
+        for (int c = 0; c < 2; ++c) { gv[c] = gs_load(rhs + c * nl, tab, l); gb[c] = gs_load(d.bloc + c * nl, tab, l); }
+      } else gw = gs_load2(wl2, tab, l);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        if (it == 0) { gv[c] = gs_load(rhs + c * nl, tab, l); gb[c] = gs_load(d.bloc + c * nl, tab, l); }
+        else gv[c] = gs_load(d.hwl + ((size_t)ppar * 2 + c) * nl, tab, l);
+      }
     }
   }
   NSK_STAMP(2);
@@ -1038,10 +1117,20 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
 #pragma unroll
     for (int q = 0; q < 8; ++q) ps[q] += ps1[q];
     if (!(d.nranks > 1 || d.use_tot)) {
-      const double* part = d.hpart + (size_t)ppar * 8 * d.nblk;
-      for (int k = tid + 2 * NT; k < d.nblk; k += NT) {     // more than 2 NT workgroups without the totals path: not a built configuration
+      if constexpr (PK) {
+        const double2* part = (const double2*)(d.hpart + (size_t)ppar * 8 * d.nblk);
+        for (int k = tid + 2 * NT; k < d.nblk; k += NT) {
 #pragma unroll
-        for (int q = 0; q < 8; ++q) ps[q] += part[(size_t)q * d.nblk + k];
+          for (int q = 0; q < 4; ++q) {
+            if (q < 3 || it == 1) { const double2 a = part[(size_t)q * d.nblk + k]; ps[2 * q] += a.x; ps[2 * q + 1] += a.y; }
+          }
+        }
+      } else {
+        const double* part = d.hpart + (size_t)ppar * 8 * d.nblk;
+        for (int k = tid + 2 * NT; k < d.nblk; k += NT) {     // more than 2 NT workgroups without the totals path: not a built configuration
+#pragma unroll
+          for (int q = 0; q < 8; ++q) ps[q] += part[(size_t)q * d.nblk + k];
+        }
       }
     }
     block_reduce<8>(ps, sred, tid, NT);
@@ -1075,6 +1164,36 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
   // ---- phase D: vector updates, next local A z, dot-product partials
   if (tid < NN) { sD[tid] = dreg; sDt[(tid % N) * N + tid / N] = dreg; }
   double r[2] = {0, 0}, z[2] = {0, 0}, bb[2] = {0, 0};
+  if constexpr (PK) {
+    if (act) {
+      double pn[2], sn[2], xn[2];
+      double2 w2 = make_double2(0.0, 0.0);
+      if (it > 0) w2 = gs_sum2(gw, wl2, d, tab, l);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        if (it == 0) {
+          r[c] = mk * gs_sum(gv[c], rhs + c * nl, d, tab, l);
+          bb[c] = mk * gs_sum(gb[c], d.bloc + c * nl, d, tab, l);
+          pn[c] = 0.0; sn[c] = 0.0; xn[c] = 0.0;
+        } else if (!done[c]) {
+          const double w = mk * (c == 0 ? w2.x : w2.y);
+          // the contractions of the component-major form's code object, spelled out (hipcc fuses one product of a b + c d, and
+          // which one depends on the code around it): p = fma(di, r, beta p), s = fma(beta, s, w), x = fma(alpha, p, x), r = fma(-alpha, s, r)
+          pn[c] = fma(di, rold[c], beta[c] * pold[c]);
+          sn[c] = fma(beta[c], sold[c], w);
+          xn[c] = fma(alpha[c], pn[c], xold[c]);
+          r[c] = fma(-alpha[c], sn[c], rold[c]);
+        } else {                      // a finished component keeps its vectors: its half of the 16-byte stores is what was loaded
+          pn[c] = pold[c]; sn[c] = sold[c]; xn[c] = xold[c];
+          r[c] = rold[c];
+        }
+        z[c] = di * r[c];
+        sz[(c * EPB + el) * NN + nd] = z[c];
+      }
+      ((double2*)d.hp)[l] = make_double2(pn[0], pn[1]); ((double2*)d.hs)[l] = make_double2(sn[0], sn[1]);
+      ((double2*)d.hx)[l] = make_double2(xn[0], xn[1]); ((double2*)d.hr)[l] = make_double2(r[0], r[1]);
+    }
+  } else
   if (act) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
@@ -1105,24 +1224,35 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
   NSK_STAMP(5);
   double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (act) {
+    double wlc[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      const double wl = d.nu * au[c] + sc.h2 * bm * z[c];
-      NSK_ST(d.hwl + ((size_t)par * 2 + c) * nl + l, wl);
+      double wl;
+      if constexpr (PK) wl = fma(sc.h2 * bm, z[c], d.nu * au[c]);       // (as the component-major code object contracts the line below)
+      else wl = d.nu * au[c] + sc.h2 * bm * z[c];
+      if constexpr (PK) wlc[c] = wl;
+      else NSK_ST(d.hwl + ((size_t)par * 2 + c) * nl + l, wl);
       v[c * 3 + 0] = r[c] * z[c] * mi;
       v[c * 3 + 1] = z[c] * wl;
       v[c * 3 + 2] = r[c] * r[c] * mi;
       v[6 + c] = bb[c] * bb[c] * mi;
     }
+    if constexpr (PK) ((double2*)(d.hwl + (size_t)par * 2 * nl))[l] = make_double2(wlc[0], wlc[1]);
   }
   block_reduce<8>(v, sred, tid, NT);
   NSK_STAMP(6);
+  if constexpr (PK) {
+    if (tid < 8) {
+      const size_t row = d.use_tot ? ((size_t)tid * d.nblk + bid) : (((size_t)(tid >> 1) * d.nblk + bid) * 2 + (tid & 1));
+      d.hpart[(size_t)par * 8 * d.nblk + row] = v[tid];
+    }
+  } else
   if (tid < 8) d.hpart[((size_t)par * 8 + tid) * d.nblk + bid] = v[tid];
   NSK_STAMP(7);
 }
-template <int N>
+template <int N, bool PK = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_helm(Dev d, StepCoef sc, int it, const double* rhs) {
-  helm_body<N>(d, sc, it, rhs, blockIdx.x, gridDim.x);
+  helm_body<N, PK>(d, sc, it, rhs, blockIdx.x, gridDim.x);
 }
 
 
@@ -1131,8 +1261,9 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_helm(Dev d, StepCoef sc, int it,
 //     also verifies that the Helmholtz solve converged.   [UPSTREAM incomprp]
 // ---------------------------------------------------------------------------
 // AB: the instantiation of the steps with the deferred update of the projection space (Dev::absorb); every other launch keeps
-// the plain one
-template <int N, bool AB = false>
+// the plain one.  PK: the velocity solve ran on the packed scratch arrays (helm_body<N, true>): hx is component-interleaved, the
+// partial sums are row pairs.
+template <int N, bool AB = false, bool PK = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_rhs(Dev d, StepCoef sc, int helm_par, int check_helm) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NT = C::NT, NM = N * M;
@@ -1162,8 +1293,10 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_rhs(Dev d, StepCoef sc, int
     for (int c = 0; c < 2; ++c) {
       const long long lc = c * nl + l;
       l1_[c] = d.dulag[lc]; l2_[c] = d.dulag[2 * nl + lc]; l3_[c] = d.dulag[4 * nl + lc];
-      hx_[c] = d.hx[lc]; un_[c] = d.u[lc];
+      if constexpr (!PK) hx_[c] = d.hx[lc];
+      un_[c] = d.u[lc];
     }
+    if constexpr (PK) { const double2 x2 = ((const double2*)d.hx)[l]; hx_[0] = x2.x; hx_[1] = x2.y; }
   }
   // deferred update of the projection space (Dev::absorb): the last step's new vector  x = delta - sum_k cf_k x_k (+ a_s x_s)
   // is formed further down from the pxr[] above, with the scalars that the bookkeeping workgroup of this step's k_rhs left in
@@ -1185,6 +1318,8 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_rhs(Dev d, StepCoef sc, int
     if (d.nranks > 1 || d.use_tot) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) s[q] = d.htot[helm_par * 8 + q];
+    } else if constexpr (PK) {
+      sum_partials_pairs<4>((const double2*)(d.hpart + (size_t)helm_par * 8 * d.nblk), d.nblk, s, sred, tid, NT);
     } else {
       sum_partials<8>(d.hpart + (size_t)helm_par * 8 * d.nblk, d.nblk, s, sred, tid, NT);
     }

@@ -396,7 +396,8 @@ namespace k2 {
 
 // CG iterations it0 .. it_end-1 of the velocity solve (launch indices as k_helm's `it`); leaves the state exactly as the launches
 // it0 .. it_end-1 would: k_pres_rhs follows with helm_par = (it_end-1) & 1, check_helm = it_end-1.
-template <int N>
+// PK: on the packed scratch arrays (helm_body<N, true>, option "helm_pack").
+template <int N, bool PK = false>
 __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_helm_tail(Dev d, StepCoef sc, int it0, int it_end, const double* rhs, unsigned* sync, unsigned* sync_other) {
   __shared__ int s_fail;
   const int tid = threadIdx.x;
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_helm_tail(Dev d, StepCoef sc,
       const double f1 = __hip_atomic_load(d.hscal + ((it - 1) & 1) * 8 + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (f0 != 0.0 && f1 != 0.0) { fin = true; break; }
     }
-    helm_body<N>(d, sc, it, rhs, blockIdx.x, gridDim.x);
+    helm_body<N, PK>(d, sc, it, rhs, blockIdx.x, gridDim.x);
     ok = grid_barrier(sync, epoch++, (int)gridDim.x, &s_fail);
     if (!ok) break;
   }

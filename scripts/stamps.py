@@ -7,6 +7,9 @@ capi.LIB_PATH = os.path.join(ROOT, "nekstab_amd", "lib", "libnekstab_hip_stamps.
 from nekstab_amd.capi import NekStabHip
 case = mesh.load_case_npz(os.path.join(ROOT, "tests/golden/cylinder_case.npz"), 8)
 h = NekStabHip(case, case.meta["vert"], case.meta["nvert"], tol_helm=1e-11, tol_pres=1e-1, tol_relative=1, nproj=8)
+if len(sys.argv) > 1:                       # python scripts/stamps.py [helm_pack]: 0 = component-major scratch arrays of k_helm, 1 = packed
+    h.set_option("helm_pack", int(sys.argv[1]))
+    print("helm_pack =", int(sys.argv[1]))
 rng = np.random.default_rng(0)
 vq, vf = h.alloc(2)
 h.upload(vq, rng.standard_normal(case.x.shape) * case.mask, rng.standard_normal(case.x.shape) * case.mask, np.zeros(h.npres))
