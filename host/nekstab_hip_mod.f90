@@ -46,6 +46,13 @@ module nekstab_hip
       type(nsk_case), intent(in) :: c
       type(c_ptr), intent(out) :: ctx
     end function
+    ! one Dirichlet mask per velocity component (SYM / ON boundaries): cmask(k) = c_loc(v1mask), c_loc(v2mask)
+    integer(c_int) function nsk_init_masks(c, cmask, ctx) bind(c, name='nsk_init_masks')
+      import
+      type(nsk_case), intent(in) :: c
+      type(c_ptr), intent(in) :: cmask(*)
+      type(c_ptr), intent(out) :: ctx
+    end function
     integer(c_int) function nsk_finalize(ctx) bind(c, name='nsk_finalize')
       import
       type(c_ptr), value :: ctx

@@ -55,6 +55,7 @@ _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
 SYMBOLS = {
     "nsk_init": (C.c_int, [C.POINTER(NskCase), _vpp]),
+    "nsk_init_masks": (C.c_int, [C.POINTER(NskCase), C.POINTER(_dp), _vpp]),
     "nsk_finalize": (C.c_int, [_vp]),
     "nsk_init_local": (C.c_int, [C.POINTER(NskCase), C.POINTER(C.c_int), _vpp]),
     "nsk_local_info": (C.c_int, [_vp, _dp, _dp, _dp, _lp, _lp]),
@@ -207,7 +208,14 @@ class NekStabHip:
                      max_pres_iter=max_pres_iter, nproj=nproj,
                      z=_p(k["z"]) if self.ndim == 3 else None, wb=_p(k["wb"]) if self.ndim == 3 else None)
         self.ctx = C.c_void_p()
-        if local_own is None:
+        cmask = getattr(c, "cmask", None)
+        if cmask is not None:           # one Dirichlet mask per velocity component (symmetry boundaries): nsk_init_masks
+            if local_own is not None:
+                raise ValueError("component masks (Case.cmask): not with a rank-local set-up")
+            k["cmask"] = [f64(m) for m in cmask]
+            arr = (_dp * len(k["cmask"]))(*[_p(m) for m in k["cmask"]])
+            self._chk(self.lib.nsk_init_masks(C.byref(cs), arr, C.byref(self.ctx)))
+        elif local_own is None:
             self._chk(self.lib.nsk_init(C.byref(cs), C.byref(self.ctx)))
         else:
             own = np.ascontiguousarray(local_own, dtype=np.int32)

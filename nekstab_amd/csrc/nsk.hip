@@ -223,6 +223,11 @@ struct nsk_ctx {
   double* hpin = nullptr;   // pinned host scratch
   Stats* hstat_pin = nullptr;           // device counters of the last map attempt (pinned)
   nsk_ctx* clone_of = nullptr;          // a second lane of another context (nsk_clone): shares every immutable device array
+  // ---- one Dirichlet mask per velocity component (nsk_init_masks: symmetry boundaries 'SYM' / 'ON ', quadrilaterals on one rank).
+  // Dev::mask and Dev::binv are then [2][nloc], Dev::dinv [3 orders][2][nloc], h_mask [2][nloc], and every kernel that reads them
+  // is launched in its <.., CM = true> form (launch_*: `cm`); contexts of nsk_init keep cm = 0 and the shared-mask forms.
+  int cm = 0;
+  const double* const* cmask_in = nullptr;              // the caller's arrays, during build() only
   // work vectors for tests / setup
   double *wv1 = nullptr, *wv2 = nullptr, *wp1 = nullptr, *wp2 = nullptr;
   std::vector<double> bm1s_host;
@@ -330,12 +335,31 @@ static StepCoef make_coef(const nsk_ctx* c, int istep, int adjoint) {
 // ---------------------------------------------------------------------------
 // E-apply helper used by setup, tests and the projection space
 // ---------------------------------------------------------------------------
+// (quadrilaterals: k_divgs in the form the context's masks ask for -- nsk_ctx::cm)
+template <int N>
+static void launch_divgs2(nsk_ctx* c, const Dev& d, const double* yl, double* wout, int j, int check_done) {
+  if (c->cm) hipLaunchKernelGGL((nsk::k2::k_divgs<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, yl, wout, j, check_done);
+  else hipLaunchKernelGGL(nsk::k2::k_divgs<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, yl, wout, j, check_done);
+}
 static int eapply(nsk_ctx* c, const double* pin, double* wout) {
   DISPATCH_N(c->key, {
     hipLaunchKernelGGL(k_gradt<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, c->d, pin, c->d.yl);
-    hipLaunchKernelGGL(k_divgs<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, c->d, (const double*)c->d.yl, wout, -1, 0);
+    if (c->ndim == 2) launch_divgs2<N>(c, c->d, (const double*)c->d.yl, wout, -1, 0);
+    else hipLaunchKernelGGL(k_divgs<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, c->d, (const double*)c->d.yl, wout, -1, 0);
   });
   return 0;
+}
+// Jacobi diagonals of H for the three BDF orders from the host copies (h_mask, h_dAs, h_bs) and the context's dt: [3][nloc], or
+// [3][2][nloc] with one mask per component
+static void jacobi_diagonals(const nsk_ctx* c, std::vector<double>& dinv) {
+  const int nmc = c->cm ? 2 : 1;
+  const long long nloc = c->nloc;
+  const double bd0[3] = {1.0, 1.5, 11.0 / 6.0};
+  dinv.resize((size_t)3 * nmc * nloc);
+  for (int k = 0; k < 3; ++k)
+    for (int mc = 0; mc < nmc; ++mc)
+      for (long long l = 0; l < nloc; ++l)
+        dinv[((size_t)k * nmc + mc) * nloc + l] = c->h_mask[(size_t)mc * nloc + l] / (c->d.nu * c->h_dAs[l] + bd0[k] / c->dt * c->h_bs[l]);
 }
 
 // dense in-place inverse (Gauss-Jordan, partial pivoting), n small
@@ -595,17 +619,23 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
     for (long long l = 0; l < nloc; ++l) { double s = 0; for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) s += f[gs_idx[k]]; o[l] = s; }
     return o;
   };
-  std::vector<double> mask(cs.mask, cs.mask + nloc), minv(nloc), binv(nloc), spng(cs.spng, cs.spng + nloc), bm1s(nloc);
+  // (component masks, nsk_init_masks: [2][nloc] each, component mc from the caller's cmask[mc]; cs.mask is not read)
+  const int nmc = c->cm ? 2 : 1;
+  if (c->cm && c->local) return fail(NSK_EINVAL, "component masks: not with a rank-local set-up");
+  std::vector<double> mask((size_t)nmc * nloc), minv(nloc), binv((size_t)nmc * nloc), spng(cs.spng, cs.spng + nloc), bm1s(nloc);
   {
     std::vector<double> bs = dssum_h(bm1);
     double vol = 0;
     for (long long l = 0; l < nloc; ++l) {
       // a node fixed in any copy is fixed in all
-      double mk = 1.0;
-      for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) mk = std::min(mk, cs.mask[gs_idx[k]]);
-      mask[l] = mk;
+      for (int mc = 0; mc < nmc; ++mc) {
+        const double* src = c->cm ? c->cmask_in[mc] : cs.mask;
+        double mk = 1.0;
+        for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) mk = std::min(mk, src[gs_idx[k]]);
+        mask[(size_t)mc * nloc + l] = mk;
+        binv[(size_t)mc * nloc + l] = mk / bs[l];
+      }
       minv[l] = 1.0 / (gs_off[l + 1] - gs_off[l]);
-      binv[l] = mk / bs[l];
       bm1s[l] = (spng[l] != 0.0) ? 0.0 : bm1[l];      // core/usr_extra.f:116-118
       vol += bm1[l];
       if (c->local && c->local_own[l / NN]) c->vol_own += bm1[l];
@@ -641,7 +671,7 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
   }
 
   // ---- Jacobi preconditioner of H for the three BDF orders
-  std::vector<double> dinv(3 * nloc);
+  std::vector<double> dinv;
   {
     std::vector<double> dA(nloc);
     for (int e = 0; e < nel; ++e)
@@ -655,9 +685,7 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
         }
     std::vector<double> dAs = dssum_h(dA), bs = dssum_h(bm1);
     c->h_dAs = dAs; c->h_bs = bs; c->h_mask = mask;
-    const double bd0[3] = {1.0, 1.5, 11.0 / 6.0};
-    for (int k = 0; k < 3; ++k)
-      for (long long l = 0; l < nloc; ++l) dinv[(size_t)k * nloc + l] = mask[l] / (d.nu * dAs[l] + bd0[k] / c->dt * bs[l]);
+    jacobi_diagonals(c, dinv);
   }
 
   if ((rc = dupload(c, &d.g1, g1)) || (rc = dupload(c, &d.g2, g2)) || (rc = dupload(c, &d.g4, g4)) ||
@@ -1040,6 +1068,11 @@ static void launch_pres_rhs_absorb(nsk_ctx* c, const Dev& d, const StepCoef& sc,
 template <int N>
 static void launch_divgs_t(nsk_ctx* c, const Dev& d, int j) {
   if (c->ndim != 2) return;
+  if (c->cm) {
+    if (d.tc32) hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, true, true>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
+    else hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, false, true>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
+    return;
+  }
   if (d.tc32) hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, true>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
   else hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, false>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
 }
@@ -1258,6 +1291,9 @@ static void launch_helm_iter(nsk_ctx* c, const Dev& d, const StepCoef& sc, int i
       }
     }
     if constexpr (N <= 10) hipLaunchKernelGGL(nsk::k3::k_helm<N>, dim3(c->nblk), dim3(nsk::k3::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
+  } else if (c->cm) {               // one mask per component (nsk_init_masks)
+    if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_helm<N, true, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
+    else hipLaunchKernelGGL((nsk::k2::k_helm<N, false, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
   } else if (d.helm_pk) {
     hipLaunchKernelGGL((nsk::k2::k_helm<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
   } else {
@@ -1343,7 +1379,8 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
       }
       launch_update_coarse(c, d, j, scale, c->min_pres, ord);
       hipLaunchKernelGGL(k_schwarz<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)(d.V + (size_t)j * d.ps), d.Z + (size_t)j * d.npr, 1, 1);
-      hipLaunchKernelGGL(k_divgs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2);
+      if (c->ndim == 2) launch_divgs2<N>(c, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2);
+      else hipLaunchKernelGGL(k_divgs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2);
     }
     if (tl && nhead < nm) launch_pres_tail<N>(c, d, nhead, nm, scale, c->min_pres, ord, f2start && nhead == 0);
     // a velocity tail ran in this step but no pressure tail will: the velocity tail's barrier words (set 0) are re-zeroed by
@@ -1388,7 +1425,7 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
         launch_gs_dots3<N>(c, d, j);
       } else {
         if (c->ndim == 3) launch_divgs3<N>(c, d, c->nblk, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 1);
-        else hipLaunchKernelGGL(k_divgs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 1);
+        else launch_divgs2<N>(c, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 1);
       }
       tot_rows(c, d.gpart, j + 2, d.gtot, &d.gsc->done);
       if (lag) {
@@ -1427,7 +1464,7 @@ static void launch_fused(nsk_ctx* c, const StepCoef& sc, int max_it = -1, const 
 // Can every workgroup of the grid be resident at once?  (grid barrier => all or nothing.)  The occupancy query can be
 // one block per CU high at 81..112 SGPRs (MI355X_MICROARCH.md, residency), so one block per CU of margin is kept.
 static int fused_possible(nsk_ctx* c) {
-  if (c->ndim != 2 || c->parent || c->d.use_tot || c->d.nranks > 1) return 0;
+  if (c->ndim != 2 || c->parent || c->d.use_tot || c->d.nranks > 1 || c->cm) return 0;      // (cm: k_helm_fused has no component-mask form)
   int ncu = 0, dev = 0, per = 0;
   if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
   hipError_t e = hipErrorUnknown;
@@ -1444,11 +1481,38 @@ static int fused_possible(nsk_ctx* c) {
 }
 
 // persistent tails: both kernels resident with one workgroup per CU of margin (the occupancy query can be one high)
+// (component-mask contexts: the same questions asked of the <.., CM = true> instantiations, which are the ones they launch)
+template <int N>
+static int tails_resident_cm(nsk_ctx* c, int ncu) {
+  const size_t sh = (size_t)c->d.coarse_lda * sizeof(double);
+  const int nit = c->d.coarse_lda / 256;
+  int ph = 0, pp = 0;
+  hipError_t e1 = helmpack_on(c) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, true, true>), nsk::k2::Cfg<N>::NT, 0)
+                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, false, true>), nsk::k2::Cfg<N>::NT, 0), e2 = hipErrorUnknown;
+  if (fuse2_on(c)) {
+    if (nit <= 3) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail2<N, 3, true>), 256, sh);
+    else if (nit <= 6) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail2<N, 6, true>), 256, sh);
+    else if (nit <= 9) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail2<N, 9, true>), 256, sh);
+    else e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail2<N, 12, true>), 256, sh);
+  } else {
+    const unsigned cgrid = (c->d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS);
+    if (nsk::k2::Cfg<N>::NT != 256 || cgrid > (unsigned)c->nblk) return 0;      // (as tails_resident)
+    if (nit <= 3) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 3, true>), nsk::k2::Cfg<N>::NT, sh);
+    else if (nit <= 6) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 6, true>), nsk::k2::Cfg<N>::NT, sh);
+    else if (nit <= 9) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 9, true>), nsk::k2::Cfg<N>::NT, sh);
+    else e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 12, true>), nsk::k2::Cfg<N>::NT, sh);
+  }
+  if (e1 != hipSuccess || e2 != hipSuccess) return 0;
+  const int need = (c->nblk + ncu - 1) / ncu;
+  if (c->debug) fprintf(stderr, "persistent tails (component masks): %d workgroups per CU needed, occupancy %d (velocity) / %d (pressure)\n", need, ph, pp);
+  return need <= std::min(std::min(ph, pp), 5);
+}
 template <int N>
 static int tails_resident(nsk_ctx* c, int ncu) {
   const size_t sh = (size_t)c->d.coarse_lda * sizeof(double);
   const int nit = c->d.coarse_lda / 256;
   int ph = 0, pp = 0;
+  if (c->cm) return tails_resident_cm<N>(c, ncu);
   hipError_t e1 = helmpack_on(c) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, true>), nsk::k2::Cfg<N>::NT, 0)
                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, false>), nsk::k2::Cfg<N>::NT, 0), e2 = hipErrorUnknown;
   if (nit <= 3) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 3>), nsk::k2::Cfg<N>::NT, sh);
@@ -1497,6 +1561,11 @@ static bool tails_on(nsk_ctx* c) {
 template <int N>
 static void launch_helm_tail(nsk_ctx* c, const Dev& d, const StepCoef& sc, int it0, int it_end) {
   if (c->ndim != 2) return;
+  if (c->cm) {
+    if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_helm_tail<N, true, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
+    else hipLaunchKernelGGL((nsk::k2::k_helm_tail<N, false, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
+    return;
+  }
   if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_helm_tail<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
   else hipLaunchKernelGGL(nsk::k2::k_helm_tail<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
 }
@@ -1511,6 +1580,13 @@ static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double sc
     Dev d0 = d; d0.uc_start = (start && j0 == 0) ? 1 : 0;      // (a head of zero launches: the solve starts in this one)
     launch_schwarz_uc<N>(c, d0, j0, scale, min_iter, ord);   // A_{j0} as a launch: closes column j0-1 (a solve of exactly j0 iterations ends here: skip_a)
     const dim3 grid(c->nblk), blk(256);
+    if (c->cm) {
+      if (nit <= 3) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 3, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+      else if (nit <= 6) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 6, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+      else if (nit <= 9) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 9, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+      else hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 12, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+      return;
+    }
     if (nit <= 3) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 3>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
     else if (nit <= 6) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 6>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
     else if (nit <= 9) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 9>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
@@ -1519,12 +1595,23 @@ static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double sc
   }
   launch_update_coarse(c, d, j0, scale, min_iter, ord);      // closes column j0-1 as a launch: a solve of exactly j0 iterations ends here (k_pres_tail: skip_a)
   const dim3 grid(c->nblk), blk(nsk::k2::Cfg<N>::NT);
+  if (c->cm) {
+    if (nit <= 3) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 3, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+    else if (nit <= 6) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 6, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+    else if (nit <= 9) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 9, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+    else hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 12, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+    return;
+  }
   if (nit <= 3) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 3>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
   else if (nit <= 6) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 6>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
   else if (nit <= 9) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 9>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
   else hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 12>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
 }
 
+template <int N>
+static void launch_vel_update_proj_cm(nsk_ctx* c, const Dev& d, const StepCoef& sc) {      // (quadrilaterals only: nsk_ctx::cm)
+  hipLaunchKernelGGL((nsk::k2::k_vel_update_proj<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
+}
 static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_over = -1, bool tail = false, bool in_map = false) {
   Dev& d = c->d;
   const StepCoef sc = make_coef(c, istep, adjoint);
@@ -1597,7 +1684,8 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
   });
   if (d.nproj_max > 0) {
     DISPATCH_N(c->key, {
-      hipLaunchKernelGGL(k_vel_update_proj<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, df, sc);
+      if (c->cm) launch_vel_update_proj_cm<N>(c, df, sc);
+      else hipLaunchKernelGGL(k_vel_update_proj<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, df, sc);
       if (flat) launch_proj_dots3<N>(c, df);
     });
     if (!absorb) {
@@ -1605,7 +1693,8 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       hipLaunchKernelGGL(k_proj_update, dim3(c->nblk), dim3(256), 0, c->stream, d);
     }
   } else {
-    hipLaunchKernelGGL(k_vel_update, dim3((unsigned)((d.nloc + 255) / 256)), dim3(256), 0, c->stream, d, sc);
+    if (c->cm) hipLaunchKernelGGL(k_vel_update_cm, dim3((unsigned)((d.nloc + 255) / 256)), dim3(256), 0, c->stream, d, sc);
+    else hipLaunchKernelGGL(k_vel_update, dim3((unsigned)((d.nloc + 255) / 256)), dim3(256), 0, c->stream, d, sc);
   }
   return 0;
 }
@@ -2034,6 +2123,7 @@ int nsk_shard_create(nsk_ctx* parent, const int* part, int rank, int nranks, nsk
   if (!parent || !part || !out) return fail(NSK_EINVAL, "bad argument");
   if (parent->released) return fail(NSK_EINVAL, "parent context was released (nsk_shard_release_parent)");
   if (parent->nscal > 0) return fail(NSK_EINVAL, "sharded vectors do not carry scalar fields yet");
+  if (parent->cm) return fail(NSK_EINVAL, "nsk_shard_create: element shards have no component-mask kernels (context of nsk_init_masks)");
   { int rc = flush_proj(parent); if (rc) return rc; }
   return shard_create(parent, part, rank, nranks, out);
 }
@@ -2385,6 +2475,34 @@ int nsk_init(const nsk_case* cs, nsk_ctx** out) {
   return 0;
 }
 
+// One Dirichlet mask per velocity component (symmetry boundaries: 'SYM' fixes the normal component of an axis-aligned face,
+// 'ON ' the tangential one; [UPSTREAM bcmask, non-stress branch: v1mask, v2mask]).  cmask[k], k < ndim: [nel lx1^2], 1.0 free /
+// 0.0 fixed; cs->mask is not read.  NULL: nsk_init.  Equal components: the shared-mask context of nsk_init on that mask (the same
+// kernels, the same bits).  Otherwise quadrilaterals on one rank: every kernel that reads a mask runs in its component-mask form.
+int nsk_init_masks(const nsk_case* cs, const double* const* cmask, nsk_ctx** out) {
+  if (!cmask) return nsk_init(cs, out);
+  if (!cs || !out) return fail(NSK_EINVAL, "null argument");
+  if (cs->ndim != 2) return fail(NSK_EINVAL, "nsk_init_masks: component masks are built for quadrilaterals (ndim = 2) only");
+  if (!cmask[0] || !cmask[1]) return fail(NSK_EINVAL, "nsk_init_masks: null component mask");
+  const size_t nloc = (size_t)cs->nel * cs->lx1 * cs->lx1;
+  if (std::equal(cmask[0], cmask[0] + nloc, cmask[1])) {
+    nsk_case one = *cs;
+    one.mask = cmask[0];
+    return nsk_init(&one, out);
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(NSK_EHIP, "no HIP device: libnekstab_hip has no CPU fallback");
+  nsk_ctx* c = new nsk_ctx();
+  c->cm = 1; c->cmask_in = cmask;
+  int rc = build(c, *cs);
+  c->cmask_in = nullptr;
+  if (!rc) rc = ensure_step_record(c);
+  if (rc) { std::string keep = g_err; nsk_finalize(c); g_err = keep; return rc; }
+  *out = c;
+  return 0;
+}
+
 // ---- rank-local set-up --------------------------------------------------------------------------------------------------
 // A rank of an element-sharded run builds a context over ITS sub-mesh (own elements + two rings of node-sharing neighbours,
 // ascending global element id, global node / vertex ids kept), not over the whole mesh:
@@ -2446,10 +2564,8 @@ int nsk_local_finish(nsk_ctx* c, double vol, double ctarg, double fd_lmax, long 
   c->dt = c->endtime / c->nsteps;
   d.dt = c->dt;
   {
-    std::vector<double> dinv((size_t)3 * c->nloc);
-    const double bd0[3] = {1.0, 1.5, 11.0 / 6.0};
-    for (int k = 0; k < 3; ++k)
-      for (long long l = 0; l < c->nloc; ++l) dinv[(size_t)k * c->nloc + l] = c->h_mask[l] / (d.nu * c->h_dAs[l] + bd0[k] / c->dt * c->h_bs[l]);
+    std::vector<double> dinv;
+    jacobi_diagonals(c, dinv);
     HIPCHK(hipMemcpy((double*)d.dinv, dinv.data(), dinv.size() * sizeof(double), hipMemcpyHostToDevice));
   }
   const int nvert = c->nvert;
@@ -2476,6 +2592,7 @@ int nsk_local_finish(nsk_ctx* c, double vol, double ctarg, double fd_lmax, long 
 
 int nsk_shard_create_local(nsk_ctx* P, const int* part_sub, const long long* elem_glob, int rank, int nranks, nsk_ctx** out) {
   if (!P || !part_sub || !elem_glob || !out) return fail(NSK_EINVAL, "bad argument");
+  if (P->cm) return fail(NSK_EINVAL, "nsk_shard_create_local: element shards have no component-mask kernels (context of nsk_init_masks)");
   if (!P->local || !P->local_done) return fail(NSK_EINVAL, "needs a context made by nsk_init_local and completed by nsk_local_finish");
   if (P->released) return fail(NSK_EINVAL, "parent context was released (nsk_shard_release_parent)");
   for (int e = 0; e < P->nel; ++e) {
@@ -2617,6 +2734,7 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
     invalidate_graphs(c);
   }
   else if (n == "eapply_pipe") { c->eapply_pipe = (int)value; invalidate_graphs(c); }
+  else if (n == "helm_fdm" && c->cm && value != 0.0) return fail(NSK_EINVAL, "helm_fdm: no component-mask form (context of nsk_init_masks)");
   else if (n == "helm_fdm") {           // 0: back to Jacobi (the factors stay); 1: only if the set-up built them (NSK_HELM_FDM=1 or an anisotropic mesh)
     if (value != 0.0 && !c->d.hfS) return fail(NSK_EINVAL, "helm_fdm: the fast-diagonalisation factors were not built at set-up (NSK_HELM_FDM=1)");
     c->d.helm_fdm = value != 0.0 ? 1 : 0;
@@ -2637,6 +2755,7 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
   }
   else if (n == "gmres_cycle") c->gmres_cycle = std::max(2, std::min((int)value, MAXMR));
   else if (n == "fused") {
+    if (value != 0 && c->cm) return fail(NSK_EINVAL, "fused: the persistent velocity solve (k_helm_fused) has no component-mask form (context of nsk_init_masks)");
     if (value != 0 && !fused_possible(c)) return fail(NSK_EINVAL, "persistent velocity solve not available for this context (needs a quadrilateral single-rank context whose workgroups are all resident)");
     c->fused = value != 0;
     for (int k = 0; k < NCLS; ++k) c->cur_helm[k] = c->max_helm;
@@ -2871,10 +2990,8 @@ int nsk_set_baseflow(nsk_ctx* c, nsk_vec qv) {
   c->nsteps = (int)std::ceil(c->endtime / dt0);
   c->dt = c->endtime / c->nsteps;
   d.dt = c->dt;
-  std::vector<double> dinv((size_t)3 * c->nloc);
-  const double bd0[3] = {1.0, 1.5, 11.0 / 6.0};
-  for (int k = 0; k < 3; ++k)
-    for (long long l = 0; l < c->nloc; ++l) dinv[(size_t)k * c->nloc + l] = c->h_mask[l] / (d.nu * c->h_dAs[l] + bd0[k] / c->dt * c->h_bs[l]);
+  std::vector<double> dinv;
+  jacobi_diagonals(c, dinv);
   HIPCHK(hipMemcpy((double*)d.dinv, dinv.data(), dinv.size() * sizeof(double), hipMemcpyHostToDevice));
   { const int rc = scan_bfmask(c); if (rc) return rc; }
   invalidate_graphs(c);           // coefficients are baked into the captured graphs
@@ -3465,7 +3582,8 @@ int nsk_seed_noise(nsk_ctx* c, nsk_vec v) {
   HIPCHK(hipMemsetAsync(q, 0, c->nstate * sizeof(double), c->stream));                // pressure (and scalars): zero
   hipLaunchKernelGGL(k_seed_rand, dim3(grid), dim3(256), 0, c->stream, (const double*)c->xyz, c->nloc, c->ndim, c->N, q);
   hipLaunchKernelGGL(k_seed_avg, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)q, c->scratch, 0);
-  hipLaunchKernelGGL(k_seed_avg, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, q, 1);
+  if (c->cm) hipLaunchKernelGGL(k_seed_avg_cm, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, q, 1);      // bcdirvc with v1mask, v2mask
+  else hipLaunchKernelGGL(k_seed_avg, dim3(grid), dim3(256), 0, c->stream, c->d, (const double*)c->scratch, q, 1);
   return 0;
 }
 
@@ -3903,6 +4021,7 @@ int nsk_group_forced_map(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec*
 // diagnostic (NSK_STAMPS build): run `reps` full pressure iterations' k_divgs and dump the stamps
 int nsk_debug_stamps(nsk_ctx* c, unsigned long long* out, int nblk_max) {
   if (!c || !out) return fail(NSK_EINVAL, "bad argument");
+  if (c->cm) return fail(NSK_EINVAL, "nsk_debug_stamps: launches the shared-mask kernel forms only (context of nsk_init_masks)");
   Dev& d = c->d;
   const size_t nrow = (size_t)c->nblk + (size_t)(d.nvert + 7) / 8 + 8;           // (k_schwarz_uc: Schwarz + coarse workgroups)
   if (!d.dbg) { int rc = dalloc(c, &d.dbg, (size_t)16 * nrow); if (rc) return rc; }
@@ -3982,6 +4101,7 @@ int nsk_clone(nsk_ctx* P, nsk_ctx** out) {
   c->dbg_max_order = P->dbg_max_order; c->dbg_ab2 = P->dbg_ab2; c->dbg_pext = P->dbg_pext;
   c->PS = P->PS; c->coarse_lda = P->coarse_lda; c->cfl_target = P->cfl_target; c->xyz = P->xyz;
   c->clone_of = P;
+  c->cm = P->cm;                                          // (the lane launches the kernel forms of its parent's masks)
   // two persistent grids launched at once can each get a share of the CUs' slots and wait for the rest for ever: contexts with
   // lanes run their maps on launch budgets only
   if (P->tail != 0) { P->tail = 0; invalidate_graphs(P); }
@@ -4073,6 +4193,7 @@ int nsk_get_step_iters(nsk_ctx* c, int n, int* helm, int* pres, int* nsteps) {
 // average duration of one hot kernel, measured with HIP events on the library's stream
 int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
   if (!c || !name || reps < 1 || !avg_us) return fail(NSK_EINVAL, "bad argument");
+  if (c->cm) return fail(NSK_EINVAL, "nsk_bench_kernel: launches the shared-mask kernel forms only (context of nsk_init_masks)");
   const std::string n(name);
   { int rc = flush_proj(c); if (rc) return rc; }
   hipEvent_t e0, e1;
@@ -4410,6 +4531,7 @@ int nsk_test_eapply(nsk_ctx* c, const double* p, double* out) {
 
 int nsk_test_helm_solve(nsk_ctx* c, const double* rx, const double* ry, int order, double* ox, double* oy, int* iters) {
   if (c->ndim != 2) return fail(NSK_EINVAL, "2-D hook: use nsk_test_op3");
+  if (c->cm) return fail(NSK_EINVAL, "nsk_test_helm_solve: launches the shared-mask k_helm only (context of nsk_init_masks)");
   Dev& d = c->d;
   HIPCHK(hipMemcpy(d.rloc, rx, c->nloc * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d.rloc + d.cs, ry, c->nloc * sizeof(double), hipMemcpyHostToDevice));

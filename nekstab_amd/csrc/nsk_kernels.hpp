@@ -1008,7 +1008,11 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_convect_rhs(Dev d, StepCoef sc) 
 // for both components), and the partial sums are stored as row pairs hpart[par][4][nblk] of double2 ({0,1} {2,3} {4,5} {6,7};
 // the (b, b) pair is loaded by launch 1 only) wherever the launches read them (not use_tot: k_tot2 sums whole rows).  Same
 // allocations, same arithmetic in the same order => the same bits; nothing but the solve and k_pres_rhs<.., PK> sees the arrays.
-template <int N, bool PK = false>
+//
+// CM (contexts of nsk_init_masks: symmetry boundaries): every velocity component has its own Dirichlet mask and Jacobi diagonal
+// -- Dev::mask is [2][nloc], Dev::dinv [3 orders][2][nloc] -- read with the first batch of loads; the arithmetic per component is
+// that of the shared-mask form.   [UPSTREAM bcmask: v1mask, v2mask]
+template <int N, bool PK = false, bool CM = false>
 __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int it, const double* rhs, const unsigned bx_, const unsigned gx_) {
   // (shards with halo / interior overlap launch the boundary workgroups first, the rest with an offset; XCD-contiguous runs of
   //  element blocks: the neighbours' edge values are L2 hits where the grid is larger than the caches, config 3)
@@ -1042,10 +1046,15 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
   // ---- phase A: issue every independent global load before anything waits
   if (it > 1) { refn[0] = d.hscal[16]; refn[1] = d.hscal[17]; }
   double bm = 0, g1 = 0, g2 = 0, g4 = 0, mk = 0, mi = 0, di = 0;
+  double mk1 = 0, di1 = 0;            // CM: component 1's own (component 0's are mk, di)
   double rold[2] = {0, 0}, pold[2] = {0, 0}, sold[2] = {0, 0}, xold[2] = {0, 0};
   if (act) {
     bm = d.bm1[l]; g1 = d.g1[l]; g2 = d.g2[l]; g4 = d.g4[l]; mk = d.mask[l]; mi = d.minv[l];
-    di = d.dinv[(size_t)(sc.k - 1) * d.nloc + l];
+    if constexpr (CM) {
+      mk1 = d.mask[d.nloc + l];
+      di = d.dinv[(size_t)(sc.k - 1) * 2 * d.nloc + l];
+      di1 = d.dinv[((size_t)(sc.k - 1) * 2 + 1) * d.nloc + l];
+    } else di = d.dinv[(size_t)(sc.k - 1) * d.nloc + l];
     if (it > 0) {
       if constexpr (PK) {
         const double2 r2 = ((const double2*)d.hr)[l], p2 = ((const double2*)d.hp)[l], s2 = ((const double2*)d.hs)[l], x2 = ((const double2*)d.hx)[l];
@@ -1164,6 +1173,8 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
   // ---- phase D: vector updates, next local A z, dot-product partials
   if (tid < NN) { sD[tid] = dreg; sDt[(tid % N) * N + tid / N] = dreg; }
   double r[2] = {0, 0}, z[2] = {0, 0}, bb[2] = {0, 0};
+  const auto mkc = [&](int c) { return (CM && c) ? mk1 : mk; };      // (c is a constant of the unrolled loops)
+  const auto dic = [&](int c) { return (CM && c) ? di1 : di; };
   if constexpr (PK) {
     if (act) {
       double pn[2], sn[2], xn[2];
@@ -1172,14 +1183,14 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         if (it == 0) {
-          r[c] = mk * gs_sum(gv[c], rhs + c * nl, d, tab, l);
-          bb[c] = mk * gs_sum(gb[c], d.bloc + c * nl, d, tab, l);
+          r[c] = mkc(c) * gs_sum(gv[c], rhs + c * nl, d, tab, l);
+          bb[c] = mkc(c) * gs_sum(gb[c], d.bloc + c * nl, d, tab, l);
           pn[c] = 0.0; sn[c] = 0.0; xn[c] = 0.0;
         } else if (!done[c]) {
-          const double w = mk * (c == 0 ? w2.x : w2.y);
+          const double w = mkc(c) * (c == 0 ? w2.x : w2.y);
           // the contractions of the component-major form's code object, spelled out (hipcc fuses one product of a b + c d, and
           // which one depends on the code around it): p = fma(di, r, beta p), s = fma(beta, s, w), x = fma(alpha, p, x), r = fma(-alpha, s, r)
-          pn[c] = fma(di, rold[c], beta[c] * pold[c]);
+          pn[c] = fma(dic(c), rold[c], beta[c] * pold[c]);
           sn[c] = fma(beta[c], sold[c], w);
           xn[c] = fma(alpha[c], pn[c], xold[c]);
           r[c] = fma(-alpha[c], sn[c], rold[c]);
@@ -1187,7 +1198,7 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
           pn[c] = pold[c]; sn[c] = sold[c]; xn[c] = xold[c];
           r[c] = rold[c];
         }
-        z[c] = di * r[c];
+        z[c] = dic(c) * r[c];
         sz[(c * EPB + el) * NN + nd] = z[c];
       }
       ((double2*)d.hp)[l] = make_double2(pn[0], pn[1]); ((double2*)d.hs)[l] = make_double2(sn[0], sn[1]);
@@ -1199,12 +1210,12 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
     for (int c = 0; c < 2; ++c) {
       const long long lc = c * nl + l;
       if (it == 0) {
-        r[c] = mk * gs_sum(gv[c], rhs + c * nl, d, tab, l);
-        bb[c] = mk * gs_sum(gb[c], d.bloc + c * nl, d, tab, l);
+        r[c] = mkc(c) * gs_sum(gv[c], rhs + c * nl, d, tab, l);
+        bb[c] = mkc(c) * gs_sum(gb[c], d.bloc + c * nl, d, tab, l);
         d.hx[lc] = 0.0; d.hp[lc] = 0.0; d.hs[lc] = 0.0; d.hr[lc] = r[c];
       } else if (!done[c]) {
-        const double w = mk * gs_sum(gv[c], d.hwl + ((size_t)ppar * 2 + c) * nl, d, tab, l);
-        const double pn = di * rold[c] + beta[c] * pold[c];
+        const double w = mkc(c) * gs_sum(gv[c], d.hwl + ((size_t)ppar * 2 + c) * nl, d, tab, l);
+        const double pn = dic(c) * rold[c] + beta[c] * pold[c];
         const double sn = w + beta[c] * sold[c];
         NSK_ST(d.hp + lc, pn); NSK_ST(d.hs + lc, sn);
         NSK_ST(d.hx + lc, xold[c] + alpha[c] * pn);
@@ -1213,7 +1224,7 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
       } else {
         r[c] = rold[c];
       }
-      z[c] = di * r[c];
+      z[c] = dic(c) * r[c];
       sz[(c * EPB + el) * NN + nd] = z[c];
     }
   }
@@ -1250,9 +1261,9 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
   if (tid < 8) d.hpart[((size_t)par * 8 + tid) * d.nblk + bid] = v[tid];
   NSK_STAMP(7);
 }
-template <int N, bool PK = false>
+template <int N, bool PK = false, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_helm(Dev d, StepCoef sc, int it, const double* rhs) {
-  helm_body<N, PK>(d, sc, it, rhs, blockIdx.x, gridDim.x);
+  helm_body<N, PK, CM>(d, sc, it, rhs, blockIdx.x, gridDim.x);
 }
 
 
@@ -2182,7 +2193,8 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_gradt(Dev d, const double* __res
 
 // w = D ( B^-1 mask dssum(yl) ) ; optional dots (w, V_i), i <= j, and (w,w)
 // check_done: 0 = always run, 1 = leave when the solve is done, 2 = the same and write the corner restriction of w to d.ec
-template <int N>
+// CM (contexts of nsk_init_masks): B^-1 mask per component, Dev::binv [2][nloc]   [UPSTREAM opbinv: v1mask, v2mask]
+template <int N, bool CM = false>
 __device__ __forceinline__ void divgs_body(const Dev& d, const double* __restrict__ yl, double* __restrict__ wout, int j, int check_done, const unsigned bx_, const unsigned gx_) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NT = C::NT, NM = N * M;
@@ -2198,8 +2210,8 @@ __device__ __forceinline__ void divgs_body(const Dev& d, const double* __restric
   NSK_STAMP(1);
   const long long l = e * NN + nd;
   int4 tab = make_int4(0, -1, -1, -1);
-  double bi = 0;
-  if (act) { tab = d.gs_tab[l]; bi = d.binv[l]; }
+  double bi = 0, bi1 = 0;
+  if (act) { tab = d.gs_tab[l]; bi = d.binv[l]; if constexpr (CM) bi1 = d.binv[d.nloc + l]; }
   int ecs = 0;
   if (check_done == 2 && d.ecv && act && nd < 4) ecs = d.ecslot[e * 4 + nd];      // (with the first loads: the store at the end waits for nothing)
   double j12a = 0, d12a = 0;
@@ -2209,7 +2221,7 @@ __device__ __forceinline__ void divgs_body(const Dev& d, const double* __restric
   if (tid < NM) { sJ12[tid] = j12a; sD12[tid] = d12a; }
   if (act) {
     su[(0 * EPB + el) * NN + nd] = bi * gs_sum(g0, yl, d, tab, l);
-    su[(1 * EPB + el) * NN + nd] = bi * gs_sum(g1, yl + d.cs, d, tab, l);
+    su[(1 * EPB + el) * NN + nd] = (CM ? bi1 : bi) * gs_sum(g1, yl + d.cs, d, tab, l);
   }
   NSK_STAMP(2);
   lds_barrier();
@@ -2251,10 +2263,10 @@ __device__ __forceinline__ void divgs_body(const Dev& d, const double* __restric
     NSK_STAMP(4);
   }
 }
-template <int N>
+template <int N, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_divgs(Dev d, const double* __restrict__ yl,
                                                       double* __restrict__ wout, int j, int check_done) {
-  divgs_body<N>(d, yl, wout, j, check_done, blockIdx.x, gridDim.x);
+  divgs_body<N, CM>(d, yl, wout, j, check_done, blockIdx.x, gridDim.x);
 }
 
 
@@ -2629,7 +2641,8 @@ __global__ __launch_bounds__(256, 3) void k_schwarz_uc(Dev d, int j, double scal
 // four behind one uniform branch each): `cond ? load : 0` costs a branch per load, and a conversion inside such a branch a
 // full wait per load (seen in the instruction stream of the first cut: twenty dependent trips for the fp32 copy).
 constexpr int UC_NVL = 20;
-template <int N, bool T32, bool SLIM = false>
+// CM (contexts of nsk_init_masks): B^-1 mask per component, as divgs_body<N, true>; Tc is the image under the same operator
+template <int N, bool T32, bool SLIM = false, bool CM = false>
 __device__ __forceinline__ void divgs_t_body(const Dev& d, int j, const unsigned bx_, const unsigned gx_) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NM = N * M;
@@ -2654,6 +2667,8 @@ __device__ __forceinline__ void divgs_t_body(const Dev& d, int j, const unsigned
   // ---- first trip: everything addressable from the thread index
   const int4 tab = d.gs_tab[l];
   const double bi = d.binv[l];
+  double bi1 = 0;
+  if constexpr (CM) bi1 = d.binv[d.nloc + l];
   const int ecs = d.ecslot[es * 4 + (nd & 3)];
   const int iv = d.evl[es * NVL + (nd < NVL ? nd : 0)];
   const int4 ev = reinterpret_cast<const int4*>(d.evert)[es];
@@ -2700,7 +2715,7 @@ __device__ __forceinline__ void divgs_t_body(const Dev& d, int j, const unsigned
   for (int r = 0; r < (4 * MM + 255) / 256; ++r) if (tid + r * 256 < 4 * MM) shat[tid + r * 256] = hatv[r];
   if (act) {
     su[(0 * EPB + el) * NN + nd] = bi * gs_sum(g0, d.yl, d, tab, l);
-    su[(1 * EPB + el) * NN + nd] = bi * gs_sum(g1, d.yl + d.cs, d, tab, l);
+    su[(1 * EPB + el) * NN + nd] = (CM ? bi1 : bi) * gs_sum(g1, d.yl + d.cs, d, tab, l);
     if (nd < NVL) sxc[el * NVL + nd] = xcv;
   }
   NSK_STAMP(3);
@@ -2795,9 +2810,9 @@ __device__ __forceinline__ void divgs_t_body(const Dev& d, int j, const unsigned
   }
   NSK_STAMP(6);
 }
-template <int N, bool T32>
+template <int N, bool T32, bool CM = false>
 __global__ __launch_bounds__(256, 2) void k_divgs_t(Dev d, int j) {
-  divgs_t_body<N, T32>(d, j, blockIdx.x, gridDim.x);
+  divgs_t_body<N, T32, false, CM>(d, j, blockIdx.x, gridDim.x);
 }
 
 // after GMRES: dp = h2 * sum_i y_i Z_i (+ projected part) ; p = p* + dp ; yl = D^T dp
@@ -2873,7 +2888,8 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_pres_update(Dev d, StepCoef sc) 
 
 // velocity correction fused with E*dp for the projection space:
 //   v = B^-1 mask dssum(yl);  u += v/h2;  E delta = D v / h2 - sum a_i E x_i;  dots (E x_i, delta), (delta, E delta)
-template <int N>
+// CM (contexts of nsk_init_masks): B^-1 mask per component, Dev::binv [2][nloc]
+template <int N, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_vel_update_proj(Dev d, StepCoef sc) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NT = C::NT, NM = N * M;
@@ -2903,9 +2919,11 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_vel_update_proj(Dev d, StepCoef 
   if (act) {
     const long long l = e * NN + nd;
     const double bi = d.binv[l];
+    double bi1 = bi;
+    if constexpr (CM) bi1 = d.binv[d.nloc + l];
     const double u0 = d.u[l], u1 = d.u[d.cs + l];                 // loads before the stores below (see k_rhs)
     const double vx = bi * gs_gather(d.yl, d, l);
-    const double vy = bi * gs_gather(d.yl + d.cs, d, l);
+    const double vy = bi1 * gs_gather(d.yl + d.cs, d, l);
     d.u[l] = u0 + vx / sc.h2;
     d.u[d.cs + l] = u1 + vy / sc.h2;
     su[(0 * EPB + el) * NN + nd] = vx;
@@ -3057,6 +3075,12 @@ __global__ void k_vel_update(Dev d, StepCoef sc) {
   const double f = d.binv[l] / sc.h2;
   for (int c = 0; c < d.ndim; ++c) d.u[c * d.cs + l] += f * gs_gather(d.yl + c * d.cs, d, l);
 }
+// the same with one mask per component (contexts of nsk_init_masks: Dev::binv [ndim][nloc])
+__global__ void k_vel_update_cm(Dev d, StepCoef sc) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= d.nloc) return;
+  for (int c = 0; c < d.ndim; ++c) d.u[c * d.cs + l] += (d.binv[c * d.nloc + l] / sc.h2) * gs_gather(d.yl + c * d.cs, d, l);
+}
 
 // ---------------------------------------------------------------------------
 // Krylov vector algebra (core/krylov_subspace.f).  State = [vx | vy | pr].
@@ -3199,6 +3223,15 @@ __global__ void k_seed_avg(Dev d, const double* __restrict__ in, double* __restr
   for (int c = 0; c < d.ndim; ++c) {
     const double s = gs_gather(in + (size_t)c * d.nloc, d, l);
     out[(size_t)c * d.nloc + l] = pass ? d.mask[l] * s : (s * d.minv[l]) * d.minv[l];
+  }
+}
+// the same with one mask per component (contexts of nsk_init_masks: Dev::mask [ndim][nloc]; bcdirvc takes v1mask, v2mask, v3mask)
+__global__ void k_seed_avg_cm(Dev d, const double* __restrict__ in, double* __restrict__ out, int pass) {
+  const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (l >= d.nloc) return;
+  for (int c = 0; c < d.ndim; ++c) {
+    const double s = gs_gather(in + (size_t)c * d.nloc, d, l);
+    out[(size_t)c * d.nloc + l] = pass ? d.mask[(size_t)c * d.nloc + l] * s : (s * d.minv[l]) * d.minv[l];
   }
 }
 

@@ -396,8 +396,8 @@ namespace k2 {
 
 // CG iterations it0 .. it_end-1 of the velocity solve (launch indices as k_helm's `it`); leaves the state exactly as the launches
 // it0 .. it_end-1 would: k_pres_rhs follows with helm_par = (it_end-1) & 1, check_helm = it_end-1.
-// PK: on the packed scratch arrays (helm_body<N, true>, option "helm_pack").
-template <int N, bool PK = false>
+// PK: on the packed scratch arrays (helm_body<N, true>, option "helm_pack").  CM: one mask per component (helm_body<N, PK, true>).
+template <int N, bool PK = false, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_helm_tail(Dev d, StepCoef sc, int it0, int it_end, const double* rhs, unsigned* sync, unsigned* sync_other) {
   __shared__ int s_fail;
   const int tid = threadIdx.x;
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_helm_tail(Dev d, StepCoef sc,
       const double f1 = __hip_atomic_load(d.hscal + ((it - 1) & 1) * 8 + 6, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (f0 != 0.0 && f1 != 0.0) { fin = true; break; }
     }
-    helm_body<N, PK>(d, sc, it, rhs, blockIdx.x, gridDim.x);
+    helm_body<N, PK, CM>(d, sc, it, rhs, blockIdx.x, gridDim.x);
     ok = grid_barrier(sync, epoch++, (int)gridDim.x, &s_fail);
     if (!ok) break;
   }
@@ -432,7 +432,8 @@ __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_helm_tail(Dev d, StepCoef sc,
 // merged pressure GMRES iterations j0 .. j1-1 (k_update_coarse, k_schwarz, k_divgs of each); the closing k_gmres_update(j1-1)
 // launch follows as behind the launched form.  skip_a: k_update_coarse(j0) has been LAUNCHED in front of this kernel (it closes
 // column j0-1: a solve of exactly j0 iterations -- the predicted count -- then ends there and this launch finds nothing to do).
-template <int N, int MAXIT>
+// CM: one mask per component (divgs_body<N, true>).
+template <int N, int MAXIT, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_pres_tail(Dev d, int j0, int j1, double scale, int min_iter, int ord, unsigned cgrid, int skip_a, unsigned* sync, unsigned* sync_other) {
   __shared__ int s_fail;
   const int tid = threadIdx.x;
@@ -452,7 +453,7 @@ __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_pres_tail(Dev d, int j0, int 
     schwarz_body<N>(d, (const double*)(d.V + (size_t)j * d.ps), d.Z + (size_t)j * d.npr, 1, 1, blockIdx.x, gridDim.x);
     ok = grid_barrier(sync, epoch++, (int)gridDim.x, &s_fail);
     if (!ok) break;
-    divgs_body<N>(d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2, blockIdx.x, gridDim.x);
+    divgs_body<N, CM>(d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2, blockIdx.x, gridDim.x);
     ok = grid_barrier(sync, epoch++, (int)gridDim.x, &s_fail);
   }
   if (!ok && tid == 0) atomicAdd((unsigned long long*)&d.stats->sync_timeouts, 1ull);
@@ -462,8 +463,8 @@ __global__ __launch_bounds__(Cfg<N>::NT, 2) void k_pres_tail(Dev d, int j0, int 
 //   [A_j: coarse role on workgroups < cgrid, then the Schwarz role on all]  barrier  [B_j]  barrier
 // two grid barriers per iteration instead of three.  skip_a: A_{j0} has been LAUNCHED in front of this kernel (it closes column
 // j0-1: a solve of exactly j0 iterations ends there).  256 threads per workgroup whatever lx1 (the coarse role is written for
-// four wavefronts); the coarse role loops over cgrid, so grids smaller than cgrid are covered too.
-template <int N, int MAXIT>
+// four wavefronts); the coarse role loops over cgrid, so grids smaller than cgrid are covered too.  CM: divgs_t_body<.., true>.
+template <int N, int MAXIT, bool CM = false>
 __global__ __launch_bounds__(256, 2) void k_pres_tail2(Dev d, int j0, int j1, double scale, int min_iter, int ord, unsigned cgrid, int skip_a, unsigned* sync, unsigned* sync_other) {
   __shared__ int s_fail;
   const int tid = threadIdx.x;
@@ -484,7 +485,7 @@ __global__ __launch_bounds__(256, 2) void k_pres_tail2(Dev d, int j0, int j1, do
       ok = grid_barrier(sync, epoch++, (int)gridDim.x, &s_fail);
       if (!ok || __hip_atomic_load(&d.gsc->done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;      // column j-1 closed the solve
     }
-    divgs_t_body<N, false>(d, j, blockIdx.x, gridDim.x);             // (the fp64 coarse image whatever option "tc32" says: one body, no spills)
+    divgs_t_body<N, false, false, CM>(d, j, blockIdx.x, gridDim.x);             // (the fp64 coarse image whatever option "tc32" says: one body, no spills)
     ok = grid_barrier(sync, epoch++, (int)gridDim.x, &s_fail);
   }
   if (!ok && tid == 0) atomicAdd((unsigned long long*)&d.stats->sync_timeouts, 1ull);

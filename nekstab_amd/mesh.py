@@ -3,7 +3,8 @@ the hot path consumes as plain arrays.
 
  * GLL-node geometry from ``.re2`` vertices + circular-arc sides  [UPSTREAM genxyz/arcsrf]
  * C0 global numbering from ``.ma2`` vertex ids (or from coordinates)
- * velocity Dirichlet masks from the boundary-condition codes
+ * velocity Dirichlet masks from the boundary-condition codes, one per component where the mesh has symmetry
+   boundaries ('SYM', 'ON ')  [UPSTREAM bcmask, non-stress branch]
  * nekStab's sponge profile and the sponge-masked inner-product weight
    (reference: core/utils.f:205-342, core/usr_extra.f:102-118)
  * base-flow interpolation between polynomial orders (what Nek's ``load_fld``
@@ -48,6 +49,9 @@ class Case:
     has_outflow: bool = True  # False => pressure null space (adjoint: 'O' -> 'v')
     adjoint: bool = False
     meta: dict = field(default_factory=dict)
+    # (ndim, nel, lx1, lx1) one mask per velocity component, only where the mesh holds a 'SYM' / 'ON ' face (else None: every
+    # component takes ``mask``); ``mask`` is then the product of the components, so whatever still reads it errs on the fixed side
+    cmask: np.ndarray | None = None
 
     @property
     def lx2(self):
@@ -188,6 +192,77 @@ def dirichlet_mask_2d(mesh: nekio.Re2Mesh, lx1: int, dirichlet_codes=("v", "W", 
     return mask
 
 
+# codes that fix ONE kind of component on a face whose normal is a coordinate axis  [UPSTREAM bcmask, non-stress branch]:
+# 'SYM' the normal component (free slip, symmetry plane), 'ON ' the tangential one (normal free)
+COMPONENT_CODES = ("SYM", "ON")
+
+
+def has_component_codes(mesh: nekio.Re2Mesh) -> bool:
+    return any(b[3].strip() in COMPONENT_CODES for b in mesh.bcs)
+
+
+def _face_nodes(f):
+    """index of the GLL nodes of face f in an (lx1, lx1) element array [j, i]"""
+    return [(0, slice(None)), (slice(None), -1), (-1, slice(None)), (slice(None), 0)][f]
+
+
+def component_masks_2d(mesh: nekio.Re2Mesh, lx1: int, gid: np.ndarray, nglob: int, dirichlet_codes=("v", "W", "V")):
+    """Velocity masks per component, (2, nel, lx1, lx1), 1.0 free / 0.0 fixed  [UPSTREAM bcmask, non-stress branch]: on a face
+    whose normal is a coordinate axis 'SYM' fixes the normal component only, 'ON ' the tangential component only,
+    ``dirichlet_codes`` fix both; then a node takes the minimum over all its copies, per component.  The free components get
+    the natural (zero-stress) condition of the weak form.  A 'SYM' / 'ON ' face that is not axis-aligned -- its end vertices
+    differ in both coordinates, or it carries a curved side -- needs Nek5000's stress formulation, which is not built:
+    ValueError naming the element and the face (both 1-based, as in the mesh file)."""
+    cm = np.ones((2, mesh.nel, lx1, lx1))
+    curved = {(c[0], c[1]) for c in mesh.curves if c[3] not in ("", " ") and np.any(np.asarray(c[2]) != 0.0)}
+    for (e, f, _prm, code) in mesh.bcs:
+        cd = code.strip()
+        sel = _face_nodes(f)
+        if cd in dirichlet_codes:
+            cm[0, e][sel] = 0.0
+            cm[1, e][sel] = 0.0
+        elif cd in COMPONENT_CODES:
+            x0, x1 = mesh.xc[e, f], mesh.xc[e, (f + 1) % 4]
+            y0, y1 = mesh.yc[e, f], mesh.yc[e, (f + 1) % 4]
+            eps = 1e-12 * np.hypot(x1 - x0, y1 - y0)
+            along_x, along_y = abs(y1 - y0) <= eps, abs(x1 - x0) <= eps
+            if (e, f) in curved or not (along_x or along_y):
+                raise ValueError("'%s' on element %d face %d: the face is not aligned with a coordinate axis (vertices "
+                                 "(%g, %g) - (%g, %g)%s); such a boundary needs the stress formulation, which is not built"
+                                 % (code, e + 1, f + 1, x0, y0, x1, y1, ", curved side" if (e, f) in curved else ""))
+            normal = 1 if along_x else 0
+            fixed = normal if cd == "SYM" else 1 - normal
+            cm[fixed, e][sel] = 0.0
+    for c in range(2):
+        g = np.ones(nglob)
+        np.minimum.at(g, gid.ravel(), cm[c].ravel())
+        cm[c] = g[gid]
+    return cm
+
+
+def box_mesh_2d(nx: int, ny: int, xy, codes):
+    """Structured mesh of nx * ny straight-sided quadrilaterals (the twin of mesh3d.box_case_3d, as a mesh: build_case_2d makes
+    the Case).  ``xy(i, j)`` -> (x, y) of the vertex (i, j), 0 <= i <= nx, 0 <= j <= ny, for integer arrays i, j -- any map
+    that keeps the elements counter-clockwise; ``codes`` = boundary code per side, keys 'xmin', 'xmax', 'ymin', 'ymax' (the
+    i = 0, i = nx, j = 0, j = ny sides; a missing key or '' leaves the side without a condition).  Element e = ex + nx * ey.
+    Returns (Re2Mesh, vertex ids (nel, 4), 1-based, lexicographic corner order as .ma2 lists them)."""
+    ey, ex = np.meshgrid(np.arange(ny), np.arange(nx), indexing="ij")
+    ex, ey = ex.ravel(), ey.ravel()
+    ci = np.stack([ex, ex + 1, ex + 1, ex], axis=1)         # counter-clockwise corners c0..c3
+    cj = np.stack([ey, ey, ey + 1, ey + 1], axis=1)
+    xc, yc = xy(ci, cj)
+    xc, yc = np.asarray(xc, dtype=np.float64), np.asarray(yc, dtype=np.float64)
+    vid = ci + (nx + 1) * cj + 1
+    side = {0: ("ymin", ey == 0), 1: ("xmax", ex == nx - 1), 2: ("ymax", ey == ny - 1), 3: ("xmin", ex == 0)}
+    bcs = []
+    for e in range(nx * ny):
+        for f in range(4):
+            code = codes.get(side[f][0], "")
+            if code and side[f][1][e]:
+                bcs.append((e, f, np.zeros(5), code))
+    return nekio.Re2Mesh(2, nx * ny, xc, yc, None, [], bcs), vid[:, _LEX2CCW]
+
+
 # ----------------------------------------------------------------------------
 # nekStab sponge (core/utils.f:205-342) and bm1s mask (core/usr_extra.f:102-118)
 # ----------------------------------------------------------------------------
@@ -263,6 +338,10 @@ def build_case_2d(mesh: nekio.Re2Mesh, vlex: np.ndarray, bf_u: np.ndarray, lx1: 
     gmask = np.ones(nglob)                 # a node fixed in one copy is fixed in all
     np.minimum.at(gmask, gid.ravel(), mask.ravel())
     mask = gmask[gid]
+    cmask = None
+    if has_component_codes(mesh):          # symmetry boundaries: one mask per component (the adjoint rule fixes every component)
+        cmask = component_masks_2d(mesh, lx1, gid, nglob, codes)
+        mask = cmask[0] * cmask[1]
     ub = interp_field_2d(np.asarray(bf_u, dtype=np.float64), lx1)
     if spng_str != 0.0:
         spng = sponge_function([x, y], [xlspg, 0.0], [xrspg, 0.0])
@@ -274,7 +353,7 @@ def build_case_2d(mesh: nekio.Re2Mesh, vlex: np.ndarray, bf_u: np.ndarray, lx1: 
     m["nvert"] = int(vlex.max())
     return Case(ndim=2, nel=mesh.nel, lx1=lx1, x=x, y=y, gid=gid, nglob=nglob, mask=mask,
                 ub=ub, spng=spng, re=re, endtime=endtime, cfl=cfl, lxd=3 * lx1 // 2,
-                has_outflow=has_out, adjoint=adjoint, meta=m)
+                has_outflow=has_out, adjoint=adjoint, meta=m, cmask=cmask)
 
 
 def load_cylinder_case(casedir: str, lx1: int, *, session="1cyl", use_ma2=True, **kw) -> Case:
@@ -334,18 +413,19 @@ def refine_case_2x2(case: Case) -> Case:
 
     x, y, ub = split(case.x), split(case.y), split(case.ub)
     # face flags of the parent from its nodal mask (interior face nodes all fixed)
-    pm = case.mask
-    f_sm = np.all(pm[:, 0, 1:-1] == 0, axis=1); f_sp = np.all(pm[:, -1, 1:-1] == 0, axis=1)
-    f_rm = np.all(pm[:, 1:-1, 0] == 0, axis=1); f_rp = np.all(pm[:, 1:-1, -1] == 0, axis=1)
-    mask = np.ones((nel, 4, n, n))
-    for qs in range(2):
-        for qr in range(2):
-            c = qs * 2 + qr
-            if qs == 0: mask[f_sm, c, 0, :] = 0.0
-            if qs == 1: mask[f_sp, c, -1, :] = 0.0
-            if qr == 0: mask[f_rm, c, :, 0] = 0.0
-            if qr == 1: mask[f_rp, c, :, -1] = 0.0
-    mask = mask.reshape(4 * nel, n, n)
+    def child_mask(pm):
+        f_sm = np.all(pm[:, 0, 1:-1] == 0, axis=1); f_sp = np.all(pm[:, -1, 1:-1] == 0, axis=1)
+        f_rm = np.all(pm[:, 1:-1, 0] == 0, axis=1); f_rp = np.all(pm[:, 1:-1, -1] == 0, axis=1)
+        mask = np.ones((nel, 4, n, n))
+        for qs in range(2):
+            for qr in range(2):
+                c = qs * 2 + qr
+                if qs == 0: mask[f_sm, c, 0, :] = 0.0
+                if qs == 1: mask[f_sp, c, -1, :] = 0.0
+                if qr == 0: mask[f_rm, c, :, 0] = 0.0
+                if qr == 1: mask[f_rp, c, :, -1] = 0.0
+        return mask.reshape(4 * nel, n, n)
+    mask = child_mask(case.mask)
     # vertex ids from corner coordinates, periodic in y
     cx = np.stack([x[:, 0, 0], x[:, 0, -1], x[:, -1, 0], x[:, -1, -1]], axis=1)
     cy = np.stack([y[:, 0, 0], y[:, 0, -1], y[:, -1, 0], y[:, -1, -1]], axis=1)
@@ -370,10 +450,18 @@ def refine_case_2x2(case: Case) -> Case:
     gmask = np.ones(nglob)
     np.minimum.at(gmask, gid.ravel(), mask.ravel())
     mask = gmask[gid]
+    cmask = None
+    if case.cmask is not None:             # the same per component; the shared mask stays their product
+        cmask = np.empty((2, 4 * nel, n, n))
+        for c in range(2):
+            g = np.ones(nglob)
+            np.minimum.at(g, gid.ravel(), child_mask(case.cmask[c]).ravel())
+            cmask[c] = g[gid]
+        mask = cmask[0] * cmask[1]
     spng = sponge_function([x, y], [5.0, 0.0], [5.0, 0.0]) if case.spng.max() > 0 else np.zeros_like(x)
     m = dict(case.meta)
     m["vert"] = vlex - 1
     m["nvert"] = int(vlex.max())
     return Case(ndim=2, nel=4 * nel, lx1=n, x=x, y=y, gid=gid, nglob=nglob, mask=mask, ub=ub, spng=spng,
                 re=case.re, endtime=case.endtime, cfl=case.cfl, lxd=case.lxd, has_outflow=case.has_outflow,
-                adjoint=case.adjoint, meta=m)
+                adjoint=case.adjoint, meta=m, cmask=cmask)

@@ -47,10 +47,11 @@ def add_noise(case):
     def dssum(f):
         return np.bincount(g, weights=f.ravel(), minlength=case.nglob)[case.gid]
 
+    cm = getattr(case, "cmask", None)          # one mask per component (symmetry boundaries), else the shared one
     out = []
     for c in range(nd):
         q = _mth_rand(ix, iy, iz, ieg, xl, FCOEFF[c])
         q = dssum(q) * vmult           # opdssum + opcolv(vmult)
         q = dssum(q * vmult)           # dsavg
-        out.append(q * case.mask)      # bcdirvc
+        out.append(q * (case.mask if cm is None else cm[c]))      # bcdirvc (v1mask, v2mask, v3mask: core/utils.f:398)
     return tuple(out)
