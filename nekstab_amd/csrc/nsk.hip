@@ -19,6 +19,7 @@
 #include <utility>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <chrono>
 #include <vector>
 
@@ -66,6 +67,46 @@ static int fail(int code, const std::string& msg) { g_err = msg; return code; }
     case 110: { constexpr int N = 10, NDIM = 3; __VA_ARGS__; } break;                           \
     default: return fail(NSK_EINVAL, "unsupported lx1");                                        \
   }
+
+// Run-time flags that are template arguments of the quadrilateral kernels (namespace k2) become types here and nowhere else:
+// with_bool for a flag, with_nit for the coarse table size -- the smallest of 3, 6, 9, 12 that holds nit = coarse_lda / 256
+// column blocks, 12 beyond that.
+template <class F>
+static auto with_bool(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F>
+static auto with_nit(int nit, F&& f) {
+  if (nit <= 3) return f(std::integral_constant<int, 3>{});
+  if (nit <= 6) return f(std::integral_constant<int, 6>{});
+  if (nit <= 9) return f(std::integral_constant<int, 9>{});
+  return f(std::integral_constant<int, 12>{});
+}
+// One selector per kernel family: the function pointer of the instantiation the flags ask for.  Launches and occupancy queries
+// both go through these, so the kernel asked about is the kernel launched.  (A generic lambda instantiates every branch it can
+// reach: a selector names exactly the combinations that exist.)
+template <int N> static auto pick_helm(bool pk, bool cm) {
+  return with_bool(pk, [&](auto PK) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_helm<N, decltype(PK)::value, decltype(CM)::value>; }); });
+}
+template <int N> static auto pick_helm_tail(bool pk, bool cm) {
+  return with_bool(pk, [&](auto PK) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_helm_tail<N, decltype(PK)::value, decltype(CM)::value>; }); });
+}
+template <int N> static auto pick_pres_rhs(bool ab, bool pk) {
+  return with_bool(ab, [&](auto AB) { return with_bool(pk, [](auto PK) { return &nsk::k2::k_pres_rhs<N, decltype(AB)::value, decltype(PK)::value>; }); });
+}
+template <int N> static auto pick_divgs_t(bool t32, bool cm) {
+  return with_bool(t32, [&](auto T32) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_divgs_t<N, decltype(T32)::value, decltype(CM)::value>; }); });
+}
+template <int N> static auto pick_pres_tail(int nit, bool cm) {
+  return with_nit(nit, [&](auto NIT) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_pres_tail<N, decltype(NIT)::value, decltype(CM)::value>; }); });
+}
+template <int N> static auto pick_pres_tail2(int nit, bool cm) {
+  return with_nit(nit, [&](auto NIT) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_pres_tail2<N, decltype(NIT)::value, decltype(CM)::value>; }); });
+}
+template <int N> static auto pick_schwarz_uc(int nit) { return with_nit(nit, [](auto NIT) { return &nsk::k2::k_schwarz_uc<N, decltype(NIT)::value>; }); }
+static auto pick_update_coarse(int nit) { return with_nit(nit, [](auto NIT) { return &nsk::k_update_coarse<decltype(NIT)::value>; }); }
+template <int N> static auto pick_divgs(bool cm) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_divgs<N, decltype(CM)::value>; }); }
+template <int N> static auto pick_vel_update_proj(bool cm) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_vel_update_proj<N, decltype(CM)::value>; }); }
+template <int N> static auto pick_rhs(bool ab) { return with_bool(ab, [](auto AB) { return &nsk::k2::k_rhs<N, decltype(AB)::value>; }); }
+template <int N> static auto pick_convect_rhs(bool ab) { return with_bool(ab, [](auto AB) { return &nsk::k2::k_convect_rhs<N, decltype(AB)::value>; }); }
 
 struct nsk_ctx {
   int N = 0, NN = 0, M = 0, MM = 0, ND = 0, NDD = 0, EPB = 0, NT = 0, NTD = 0;
@@ -338,8 +379,7 @@ static StepCoef make_coef(const nsk_ctx* c, int istep, int adjoint) {
 // (quadrilaterals: k_divgs in the form the context's masks ask for -- nsk_ctx::cm)
 template <int N>
 static void launch_divgs2(nsk_ctx* c, const Dev& d, const double* yl, double* wout, int j, int check_done) {
-  if (c->cm) hipLaunchKernelGGL((nsk::k2::k_divgs<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, yl, wout, j, check_done);
-  else hipLaunchKernelGGL(nsk::k2::k_divgs<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, yl, wout, j, check_done);
+  hipLaunchKernelGGL(pick_divgs<N>(c->cm), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, yl, wout, j, check_done);
 }
 static int eapply(nsk_ctx* c, const double* pin, double* wout) {
   DISPATCH_N(c->key, {
@@ -1021,11 +1061,7 @@ static inline double early_tol(const Dev& d, double mul) {
 static void launch_update_coarse(nsk_ctx* c, const Dev& d, int j, double scale, int min_iter, int ord) {
   const unsigned cgrid = (d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS);
   const size_t sh = d.coarse_lda * sizeof(double);
-  const int nit = d.coarse_lda / 256;
-  if (nit <= 3) hipLaunchKernelGGL(k_update_coarse<3>, dim3(cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord);
-  else if (nit <= 6) hipLaunchKernelGGL(k_update_coarse<6>, dim3(cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord);
-  else if (nit <= 9) hipLaunchKernelGGL(k_update_coarse<9>, dim3(cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord);
-  else hipLaunchKernelGGL(k_update_coarse<12>, dim3(cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord);
+  hipLaunchKernelGGL(pick_update_coarse(d.coarse_lda / 256), dim3(cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord);
 }
 
 // round 6, the merged iteration in two launches: A_j (Schwarz workgroups + coarse workgroups) and B_j
@@ -1042,39 +1078,31 @@ static void launch_schwarz_uc(nsk_ctx* c, const Dev& d, int j, double scale, int
   const unsigned cgrid = (d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS), nsw = (unsigned)c->nblk;
   const size_t sh = d.coarse_lda * sizeof(double);
   const int nit = d.coarse_lda / 256;
-  const dim3 grid(nsw + cgrid), blk(256);
-  // (fuse2_on: nit is exactly 3, 6, 9 or 12)
-  if (nit == 3) hipLaunchKernelGGL((nsk::k2::k_schwarz_uc<N, 3>), grid, blk, sh, c->stream, d, j, scale, min_iter, ord, nsw, cgrid);
-  else if (nit == 6) hipLaunchKernelGGL((nsk::k2::k_schwarz_uc<N, 6>), grid, blk, sh, c->stream, d, j, scale, min_iter, ord, nsw, cgrid);
-  else if (nit == 9) hipLaunchKernelGGL((nsk::k2::k_schwarz_uc<N, 9>), grid, blk, sh, c->stream, d, j, scale, min_iter, ord, nsw, cgrid);
-  else if (nit == 12) hipLaunchKernelGGL((nsk::k2::k_schwarz_uc<N, 12>), grid, blk, sh, c->stream, d, j, scale, min_iter, ord, nsw, cgrid);
+  // (fuse2_on: nit is exactly 3, 6, 9 or 12, the table size itself; any other value has never launched anything)
+  if (nit < 3 || nit > 12 || nit % 3 != 0) return;
+  hipLaunchKernelGGL(pick_schwarz_uc<N>(nit), dim3(nsw + cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord, nsw, cgrid);
 }
 template <int N>
 static void launch_proj_apply_e(nsk_ctx* c, const Dev& d) {
   if (c->ndim != 2) return;
   hipLaunchKernelGGL(nsk::k2::k_proj_apply_e<N>, dim3(c->nblk), dim3(256), 0, c->stream, d);
 }
+// the quadrilateral forms of the velocity right-hand side and the pressure right-hand side (Dev::absorb, Dev::bstep_late, Dev::helm_pk
+// say what the step asked for): absorb = the deferred projection update (absorb_on), k_rhs then with its bookkeeping workgroup
 template <int N>
-static void launch_rhs_absorb(nsk_ctx* c, const Dev& d, const StepCoef& sc) {      // (quadrilaterals only: absorb_on) the element workgroups + the bookkeeping workgroup
+static void launch_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool absorb) {
   if (c->ndim != 2) return;
-  hipLaunchKernelGGL((nsk::k2::k_rhs<N, true>), dim3(c->nblk + 1), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
+  hipLaunchKernelGGL(pick_rhs<N>(absorb), dim3(c->nblk + (absorb ? 1 : 0)), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
 }
 template <int N>
-static void launch_pres_rhs_absorb(nsk_ctx* c, const Dev& d, const StepCoef& sc, int helm_par, int check_helm) {      // (quadrilaterals only: absorb_on)
+static void launch_pres_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool absorb, int helm_par, int check_helm) {
   if (c->ndim != 2) return;
-  if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, true, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
-  else hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
+  hipLaunchKernelGGL(pick_pres_rhs<N>(absorb, d.helm_pk), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
 }
 template <int N>
 static void launch_divgs_t(nsk_ctx* c, const Dev& d, int j) {
   if (c->ndim != 2) return;
-  if (c->cm) {
-    if (d.tc32) hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, true, true>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
-    else hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, false, true>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
-    return;
-  }
-  if (d.tc32) hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, true>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
-  else hipLaunchKernelGGL((nsk::k2::k_divgs_t<N, false>), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
+  hipLaunchKernelGGL(pick_divgs_t<N>(d.tc32, c->cm), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
 }
 
 static bool stream_capturing(hipStream_t s) {
@@ -1141,14 +1169,7 @@ static bool helmpack_on(const nsk_ctx* c) {
 template <int N>
 static void launch_convect_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool absorb) {      // (quadrilaterals only: convfuse_on)
   if (c->ndim != 2) return;
-  if (absorb) hipLaunchKernelGGL((nsk::k2::k_convect_rhs<N, true>), dim3(c->nblk + 1), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
-  else hipLaunchKernelGGL((nsk::k2::k_convect_rhs<N, false>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
-}
-template <int N>
-static void launch_pres_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, int helm_par, int check_helm) {      // (quadrilaterals only: the plain k_pres_rhs with Dev::bstep_late)
-  if (c->ndim != 2) return;
-  if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, false, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
-  else hipLaunchKernelGGL((nsk::k2::k_pres_rhs<N, false>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
+  hipLaunchKernelGGL(pick_convect_rhs<N>(absorb), dim3(c->nblk + (absorb ? 1 : 0)), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
 }
 // A map ends, or something is about to read, copy or reset the space: the update its last step left behind goes in with the
 // standalone kernel (one launch per map), and the context looks as it does without the option.
@@ -1169,18 +1190,23 @@ static bool gs_lag_on(const nsk_ctx* c) {
   if (c->gs_lag >= 0) return c->gs_lag != 0;
   return c->d.nranks <= 1 && !c->parent;
 }
-// E-apply kernels of the hexahedral pressure iteration as resident workgroups (nsk3_kernels.hpp: k_schwarz_p): as many
-// workgroups as the device holds at once, a multiple of 8 so that a workgroup's stride stays inside its XCD's run of elements.
+// Resident workgroups of a hexahedral kernel: as many as the device holds at once (per_cu on every CU), a multiple of 8 so that
+// a workgroup's stride stays inside its XCD's run of elements.
+static int resident_grid(int per_cu) {
+  int ncu = 0, dev = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  return std::max(8, (std::max(1, per_cu) * std::max(1, ncu)) / 8 * 8);
+}
+// E-apply kernels of the hexahedral pressure iteration as resident workgroups (nsk3_kernels.hpp: k_schwarz_p)
 template <int N>
 static unsigned eapply_grid(nsk_ctx* c, int which, int count) {
   if constexpr (N <= 10) {
     if (!c->eapply_grid[which]) {
-      int per_cu = 0, ncu = 0, dev = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+      int per_cu = 0;
       if (which == 0) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nsk::k3::k_schwarz_p<N>, nsk::k3::Cfg<N>::NT, 0);
       if (const char* g = std::getenv("NSK_EAPPLY_WGS")) per_cu = std::atoi(g);
-      c->eapply_grid[which] = std::max(8, (std::max(1, per_cu) * std::max(1, ncu)) / 8 * 8);
+      c->eapply_grid[which] = resident_grid(per_cu);
     }
   }
   return (unsigned)std::min(count, c->eapply_grid[which]);
@@ -1245,7 +1271,7 @@ static void launch_gs_dots3(nsk_ctx* c, const Dev& d, int j) {         // first-
   }
 }
 template <int N>
-static void launch_gs_lag3(nsk_ctx* c, const Dev& d, int j, double scale, int ord) {
+static void launch_gs_lag_pass3(nsk_ctx* c, const Dev& d, int j) {       // the streaming pass of launch_gs_lag3
   if constexpr (N <= 10) {
     constexpr int ROWS = (nsk::k3::Cfg<N>::MM + 63) / 64;
     constexpr int R4 = ROWS < 4 ? ROWS : 4, R2 = ROWS < 2 ? ROWS : 2;
@@ -1254,20 +1280,24 @@ static void launch_gs_lag3(nsk_ctx* c, const Dev& d, int j, double scale, int or
     else if (j <= 16) hipLaunchKernelGGL((nsk::k3::k_gs_lag<N, 16, R2>), grid, blk, 0, c->stream, d, j);
     else if (j <= 32) hipLaunchKernelGGL((nsk::k3::k_gs_lag<N, 32, 1>), grid, blk, 0, c->stream, d, j);
     else hipLaunchKernelGGL((nsk::k3::k_gs_lag<N, MAXMR, 1>), grid, blk, 0, c->stream, d, j);
+  }
+}
+template <int N>
+static void launch_gs_lag3(nsk_ctx* c, const Dev& d, int j, double scale, int ord) {      // the pass, its totals, the column close
+  if constexpr (N <= 10) {
+    launch_gs_lag_pass3<N>(c, d, j);
     tot_rows(c, d.gpart2, j + 2, d.gtot2, &d.gsc->done);
     hipLaunchKernelGGL(nsk::k3::k_gmres_col, dim3(1), dim3(64), 0, c->stream, d, j, scale, c->min_pres, ord);
   }
 }
 
-// resident workgroups of k_helm_p<10>: what the device holds at once, a multiple of 8 (a workgroup's stride stays inside its XCD's run)
+// resident workgroups of k_helm_p<10>
 static int helm_pf_grid(nsk_ctx* c) {
   if (!c->helm_pf_grid) {
-    int per_cu = 0, ncu = 0, dev = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    int per_cu = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nsk::k3::k_helm_p<10>, nsk::k3::Cfg<10>::NT, 0);
     if (const char* g = std::getenv("NSK_HELM_PF_WGS")) per_cu = std::atoi(g);
-    c->helm_pf_grid = std::max(8, (std::max(1, per_cu) * std::max(1, ncu)) / 8 * 8);
+    c->helm_pf_grid = resident_grid(per_cu);
   }
   return c->helm_pf_grid;
 }
@@ -1291,13 +1321,8 @@ static void launch_helm_iter(nsk_ctx* c, const Dev& d, const StepCoef& sc, int i
       }
     }
     if constexpr (N <= 10) hipLaunchKernelGGL(nsk::k3::k_helm<N>, dim3(c->nblk), dim3(nsk::k3::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
-  } else if (c->cm) {               // one mask per component (nsk_init_masks)
-    if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_helm<N, true, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
-    else hipLaunchKernelGGL((nsk::k2::k_helm<N, false, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
-  } else if (d.helm_pk) {
-    hipLaunchKernelGGL((nsk::k2::k_helm<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
-  } else {
-    hipLaunchKernelGGL(nsk::k2::k_helm<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
+  } else {                          // quadrilaterals: the packed layout (Dev::helm_pk), one mask per component (nsk_init_masks)
+    hipLaunchKernelGGL(pick_helm<N>(d.helm_pk, c->cm), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
   }
 }
 
@@ -1454,7 +1479,6 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
 }
 
 // ---- persistent velocity solve (nsk_persist.hpp): only the quadrilateral kernel set has it
-namespace nsk { namespace k3 { template <int N> __global__ void k_helm_fused(Dev, StepCoef, int, unsigned*) {} } }
 template <int N>
 static void launch_fused(nsk_ctx* c, const StepCoef& sc, int max_it = -1, const Dev* dd = nullptr) {
   if (c->ndim != 2) return;
@@ -1480,60 +1504,31 @@ static int fused_possible(nsk_ctx* c) {
   return need <= std::min(per, 5);      // 5: what ~110 SGPRs admit (floor(800 / 128) = 6) minus one
 }
 
-// persistent tails: both kernels resident with one workgroup per CU of margin (the occupancy query can be one high)
-// (component-mask contexts: the same questions asked of the <.., CM = true> instantiations, which are the ones they launch)
+// The kernels of a context's two persistent tails, from the selectors: launch_helm_tail / launch_pres_tail launch them and
+// tails_resident asks about them, so the two cannot disagree.  (k_pres_tail2 is the two-launch form's tail, 256 threads whatever
+// lx1; the two pressure tails have one signature.)
 template <int N>
-static int tails_resident_cm(nsk_ctx* c, int ncu) {
-  const size_t sh = (size_t)c->d.coarse_lda * sizeof(double);
+static auto helm_tail_kernel(const nsk_ctx* c) { return pick_helm_tail<N>(helmpack_on(c), c->cm); }
+template <int N>
+static auto pres_tail_kernel(const nsk_ctx* c) {
   const int nit = c->d.coarse_lda / 256;
-  int ph = 0, pp = 0;
-  hipError_t e1 = helmpack_on(c) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, true, true>), nsk::k2::Cfg<N>::NT, 0)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, false, true>), nsk::k2::Cfg<N>::NT, 0), e2 = hipErrorUnknown;
-  if (fuse2_on(c)) {
-    if (nit <= 3) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail2<N, 3, true>), 256, sh);
-    else if (nit <= 6) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail2<N, 6, true>), 256, sh);
-    else if (nit <= 9) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail2<N, 9, true>), 256, sh);
-    else e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail2<N, 12, true>), 256, sh);
-  } else {
-    const unsigned cgrid = (c->d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS);
-    if (nsk::k2::Cfg<N>::NT != 256 || cgrid > (unsigned)c->nblk) return 0;      // (as tails_resident)
-    if (nit <= 3) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 3, true>), nsk::k2::Cfg<N>::NT, sh);
-    else if (nit <= 6) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 6, true>), nsk::k2::Cfg<N>::NT, sh);
-    else if (nit <= 9) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 9, true>), nsk::k2::Cfg<N>::NT, sh);
-    else e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 12, true>), nsk::k2::Cfg<N>::NT, sh);
-  }
-  if (e1 != hipSuccess || e2 != hipSuccess) return 0;
-  const int need = (c->nblk + ncu - 1) / ncu;
-  if (c->debug) fprintf(stderr, "persistent tails (component masks): %d workgroups per CU needed, occupancy %d (velocity) / %d (pressure)\n", need, ph, pp);
-  return need <= std::min(std::min(ph, pp), 5);
+  return fuse2_on(c) ? pick_pres_tail2<N>(nit, c->cm) : pick_pres_tail<N>(nit, c->cm);
 }
 template <int N>
+static int pres_tail_threads(const nsk_ctx* c) { return fuse2_on(c) ? 256 : nsk::k2::Cfg<N>::NT; }
+// persistent tails: both kernels resident with one workgroup per CU of margin (the occupancy query can be one high)
+template <int N>
 static int tails_resident(nsk_ctx* c, int ncu) {
+  constexpr int NT = nsk::k2::Cfg<N>::NT;
   const size_t sh = (size_t)c->d.coarse_lda * sizeof(double);
-  const int nit = c->d.coarse_lda / 256;
-  int ph = 0, pp = 0;
-  if (c->cm) return tails_resident_cm<N>(c, ncu);
-  hipError_t e1 = helmpack_on(c) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, true>), nsk::k2::Cfg<N>::NT, 0)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, (nsk::k2::k_helm_tail<N, false>), nsk::k2::Cfg<N>::NT, 0), e2 = hipErrorUnknown;
-  if (nit <= 3) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 3>), nsk::k2::Cfg<N>::NT, sh);
-  else if (nit <= 6) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 6>), nsk::k2::Cfg<N>::NT, sh);
-  else if (nit <= 9) e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 9>), nsk::k2::Cfg<N>::NT, sh);
-  else e2 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, (nsk::k2::k_pres_tail<N, 12>), nsk::k2::Cfg<N>::NT, sh);
-  if (e1 != hipSuccess || e2 != hipSuccess) return 0;
-  if (fuse2_on(c)) {                             // the two-launch form's tail (256 threads whatever lx1)
-    int p2 = 0;
-    hipError_t e3;
-    if (nit <= 3) e3 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, (nsk::k2::k_pres_tail2<N, 3>), 256, sh);
-    else if (nit <= 6) e3 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, (nsk::k2::k_pres_tail2<N, 6>), 256, sh);
-    else if (nit <= 9) e3 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, (nsk::k2::k_pres_tail2<N, 9>), 256, sh);
-    else e3 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&p2, (nsk::k2::k_pres_tail2<N, 12>), 256, sh);
-    if (e3 != hipSuccess) return 0;
-    pp = p2;
-  } else {
+  if (!fuse2_on(c)) {
     // k_pres_tail runs update_coarse_body, written for 256-thread workgroups, on its first cgrid workgroups
     const unsigned cgrid = (c->d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS);
-    if (nsk::k2::Cfg<N>::NT != 256 || cgrid > (unsigned)c->nblk) return 0;
+    if (NT != 256 || cgrid > (unsigned)c->nblk) return 0;
   }
+  int ph = 0, pp = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, helm_tail_kernel<N>(c), NT, 0) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, pres_tail_kernel<N>(c), pres_tail_threads<N>(c), sh) != hipSuccess) return 0;
   const int need = (c->nblk + ncu - 1) / ncu;
   if (c->debug) fprintf(stderr, "persistent tails: %d workgroups per CU needed, occupancy %d (velocity) / %d (pressure)\n", need, ph, pp);
   // (the occupancy query is one workgroup per CU high only where it is bound by scalar registers, 7-8 per CU: MI355X_MICROARCH.md,
@@ -1561,57 +1556,25 @@ static bool tails_on(nsk_ctx* c) {
 template <int N>
 static void launch_helm_tail(nsk_ctx* c, const Dev& d, const StepCoef& sc, int it0, int it_end) {
   if (c->ndim != 2) return;
-  if (c->cm) {
-    if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_helm_tail<N, true, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
-    else hipLaunchKernelGGL((nsk::k2::k_helm_tail<N, false, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
-    return;
-  }
-  if (d.helm_pk) hipLaunchKernelGGL((nsk::k2::k_helm_tail<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
-  else hipLaunchKernelGGL(nsk::k2::k_helm_tail<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
+  // (step() set d.helm_pk from helmpack_on, the question helm_tail_kernel asks)
+  hipLaunchKernelGGL(helm_tail_kernel<N>(c), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
 }
 template <int N>
 static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double scale, int min_iter, int ord, bool start) {
   if (c->ndim != 2) return;
   const unsigned cgrid = (d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS);
   const size_t sh = d.coarse_lda * sizeof(double);
-  const int nit = d.coarse_lda / 256;
   unsigned* sy = c->sync + SYNC_WORDS;          // (set 1; zeroes set 0 for the next velocity tail)
+  // column j0-1 is closed by a launch: a solve of exactly j0 iterations ends there (the tails: skip_a)
   if (fuse2_on(c)) {
     Dev d0 = d; d0.uc_start = (start && j0 == 0) ? 1 : 0;      // (a head of zero launches: the solve starts in this one)
-    launch_schwarz_uc<N>(c, d0, j0, scale, min_iter, ord);   // A_{j0} as a launch: closes column j0-1 (a solve of exactly j0 iterations ends here: skip_a)
-    const dim3 grid(c->nblk), blk(256);
-    if (c->cm) {
-      if (nit <= 3) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 3, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-      else if (nit <= 6) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 6, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-      else if (nit <= 9) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 9, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-      else hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 12, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-      return;
-    }
-    if (nit <= 3) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 3>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-    else if (nit <= 6) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 6>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-    else if (nit <= 9) hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 9>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-    else hipLaunchKernelGGL((nsk::k2::k_pres_tail2<N, 12>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-    return;
+    launch_schwarz_uc<N>(c, d0, j0, scale, min_iter, ord);   // A_{j0}
+  } else {
+    launch_update_coarse(c, d, j0, scale, min_iter, ord);
   }
-  launch_update_coarse(c, d, j0, scale, min_iter, ord);      // closes column j0-1 as a launch: a solve of exactly j0 iterations ends here (k_pres_tail: skip_a)
-  const dim3 grid(c->nblk), blk(nsk::k2::Cfg<N>::NT);
-  if (c->cm) {
-    if (nit <= 3) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 3, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-    else if (nit <= 6) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 6, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-    else if (nit <= 9) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 9, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-    else hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 12, true>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-    return;
-  }
-  if (nit <= 3) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 3>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-  else if (nit <= 6) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 6>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-  else if (nit <= 9) hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 9>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
-  else hipLaunchKernelGGL((nsk::k2::k_pres_tail<N, 12>), grid, blk, sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+  hipLaunchKernelGGL(pres_tail_kernel<N>(c), dim3(c->nblk), dim3(pres_tail_threads<N>(c)), sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
 }
 
-template <int N>
-static void launch_vel_update_proj_cm(nsk_ctx* c, const Dev& d, const StepCoef& sc) {      // (quadrilaterals only: nsk_ctx::cm)
-  hipLaunchKernelGGL((nsk::k2::k_vel_update_proj<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
-}
 static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_over = -1, bool tail = false, bool in_map = false) {
   Dev& d = c->d;
   const StepCoef sc = make_coef(c, istep, adjoint);
@@ -1652,7 +1615,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       launch_fused<N>(c, sc);
     } else {
       if (cfuse) launch_convect_rhs<N>(c, da, sc, absorb);
-      else if (absorb) launch_rhs_absorb<N>(c, da, sc);
+      else if (c->ndim == 2) launch_rhs<N>(c, da, sc, absorb);
       else hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc);
       if (tail) nh = std::max(1, std::min(nh, c->max_helm - 1));      // HEAD launches; the persistent tail runs launches nh .. max_helm-1
       for (int it = 0; it < nh; ++it) {
@@ -1666,9 +1629,8 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
         }
       }
       if (tail) { launch_helm_tail<N>(c, d, sc, nh, c->max_helm); nh = c->max_helm; }
-      if (absorb) launch_pres_rhs_absorb<N>(c, da, sc, (nh - 1) & 1, nh - 1);
-      else if (cfuse) launch_pres_rhs<N>(c, da, sc, (nh - 1) & 1, nh - 1);
-      else if (hpk) launch_pres_rhs<N>(c, d, sc, (nh - 1) & 1, nh - 1);
+      // (quadrilaterals: `da` is `d` with this step's absorb and bstep_late, the two k_pres_rhs reads besides helm_pk)
+      if (c->ndim == 2) launch_pres_rhs<N>(c, da, sc, absorb, (nh - 1) & 1, nh - 1);
       else hipLaunchKernelGGL(k_pres_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc, (nh - 1) & 1, nh - 1);
     }
   });
@@ -1684,7 +1646,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
   });
   if (d.nproj_max > 0) {
     DISPATCH_N(c->key, {
-      if (c->cm) launch_vel_update_proj_cm<N>(c, df, sc);
+      if (c->ndim == 2) hipLaunchKernelGGL(pick_vel_update_proj<N>(c->cm), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, df, sc);
       else hipLaunchKernelGGL(k_vel_update_proj<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, df, sc);
       if (flat) launch_proj_dots3<N>(c, df);
     });
@@ -4051,11 +4013,8 @@ int nsk_debug_stamps(nsk_ctx* c, unsigned long long* out, int nblk_max) {
     if (nblk_max < 0) {
       Dev dd = d; dd.tol_helm = 0.0; dd.tol_relative = 0;
       const StepCoef sc = make_coef(c, 3, 0);
-      const bool hpk = c->ndim == 2 && helmpack_on(c);       // the instantiation the context's steps run (option "helm_pack")
-      for (int r = 0; r < 6; ++r) {
-        if (hpk) hipLaunchKernelGGL((nsk::k2::k_helm<N, true>), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, dd, sc, r, (const double*)d.rloc);
-        else hipLaunchKernelGGL(k_helm<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, dd, sc, r, (const double*)d.rloc);
-      }
+      dd.helm_pk = helmpack_on(c) ? 1 : 0;                   // the instantiation the context's steps run (option "helm_pack")
+      for (int r = 0; r < 6; ++r) launch_helm_iter<N>(c, dd, sc, r, (const double*)d.rloc);
       nblk_max = -nblk_max;
     } else if (std::getenv("NSK_STAMP_KERNEL") && std::string(std::getenv("NSK_STAMP_KERNEL")) == "divgs_w") {
       for (int r = 0; r < 5; ++r) launch_divgs3<N>(c, d, c->nblk, (const double*)d.yl, c->wp2, -1, 0, 3);
@@ -4317,17 +4276,7 @@ int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
         else if (n == "pres_rhs") hipLaunchKernelGGL(k_pres_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc, 1, 7);
         else if (n == "rhs") hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc);
         else if (n.rfind("gs_dots", 0) == 0) launch_gs_dots3<N>(c, d, jj);
-        else {                                               // gs_lag<j>: the streaming pass alone (its totals and the column kernel are microseconds)
-          if constexpr (N <= 10) {
-            constexpr int ROWS = (nsk::k3::Cfg<N>::MM + 63) / 64;
-            constexpr int R4 = ROWS < 4 ? ROWS : 4, R2 = ROWS < 2 ? ROWS : 2;
-            const dim3 grid(std::min<unsigned>((unsigned)((c->nel + 3) / 4), 2048u)), blk(256);
-            if (jj <= 8) hipLaunchKernelGGL((nsk::k3::k_gs_lag<N, 8, R4>), grid, blk, 0, c->stream, d, jj);
-            else if (jj <= 16) hipLaunchKernelGGL((nsk::k3::k_gs_lag<N, 16, R2>), grid, blk, 0, c->stream, d, jj);
-            else if (jj <= 32) hipLaunchKernelGGL((nsk::k3::k_gs_lag<N, 32, 1>), grid, blk, 0, c->stream, d, jj);
-            else hipLaunchKernelGGL((nsk::k3::k_gs_lag<N, MAXMR, 1>), grid, blk, 0, c->stream, d, jj);
-          }
-        }
+        else launch_gs_lag_pass3<N>(c, d, jj);               // gs_lag<j>: the streaming pass alone (its totals and the column kernel are microseconds)
       }
       HIPCHK(hipEventRecord(e1, c->stream));
     });
