@@ -312,6 +312,19 @@ module nekstab_hip
       type(c_ptr), value :: q
       type(c_ptr), value :: w
     end function
+    ! SFD (core/fixedp.f:114-242, uparam(1) = 1.1): f = nsteps steps of the full equations from q under -chi (v - qbar); qbar
+    ! enters as the filter state at call 0 (a copy of q: the reference's run) and leaves as the one behind the last step.
+    ! residu: c_null_ptr or c_loc of nsteps doubles (residu of every step).  f, q, qbar: three distinct vectors
+    integer(c_int) function nsk_sfd_map(ctx, f, q, qbar, chi, omega_c, residu) bind(c, name='nsk_sfd_map')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: f
+      type(c_ptr), value :: q
+      type(c_ptr), value :: qbar
+      real(c_double), value :: chi
+      real(c_double), value :: omega_c
+      type(c_ptr), value :: residu
+    end function
     integer(c_int) function nsk_clone(ctx, lane) bind(c, name='nsk_clone')
       import
       type(c_ptr), value :: ctx
@@ -503,6 +516,15 @@ module nekstab_hip
       type(c_ptr), dimension(*) :: shards
       integer(c_int), value :: n
       type(c_ptr), dimension(*) :: q, w
+    end function
+    integer(c_int) function nsk_group_sfd_map(shards, n, f, q, qbar, chi, omega_c, residu) bind(c, name='nsk_group_sfd_map')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: f, q, qbar
+      real(c_double), value :: chi
+      real(c_double), value :: omega_c
+      type(c_ptr), value :: residu
     end function
     integer(c_int) function nsk_shard_release_parent(parent) bind(c, name='nsk_shard_release_parent')
       import

@@ -269,6 +269,35 @@ int nsk_energy_budget(nsk_ctx* ctx, nsk_vec ub, nsk_vec dRe, nsk_vec dIm, nsk_ve
  * The assembled unmasked mass (one double per velocity node) is built at a context's first call and kept until nsk_finalize;
  * nothing else is allocated, no captured step graph or launch budget is touched. */
 int nsk_vorticity(nsk_ctx* ctx, nsk_vec q, nsk_vec w);
+/* Selective frequency damping (SFD, core/fixedp.f:114-242, uparam(1) = 1.1): f = v^nsteps, the state after nsteps steps of the
+ * FULL equations from v^0 = q under the force -chi (v - qbar), qbar a low-pass-filtered copy of the velocity.  nsteps, dt and
+ * the base state of the CFL rule are nsk_nonlinear_map's (nsk_set_baseflow / nsk_set_nsteps).  The reference calls SFD after
+ * every step; call j sees v^j:
+ *   call 0:      vxo = v^0, the Adams-Bashforth lags uta = utb = utc = 0; qbar^0 is the caller's `qbar` (velocity components
+ *                read, the rest ignored) where the reference sets qbar^0 = v^0 -- pass a copy of q for the reference's run
+ *   call j >= 1: utc <- utb, utb <- uta, uta <- vxo - qbar^{j-1};  qbar^j = qbar^{j-1} + omega_c dt (a uta + b utb + c utc),
+ *                (a, b, c) = setab3 at constant dt: (3/2, -1/2, 0) for j <= 2, (23/12, -16/12, 5/12) after
+ *   every call:  the force of step j + 1 is -chi (vxo - qbar^j), added times bm1 where nekStab_forcing adds fcx (before the EXT
+ *                extrapolation).  vxo is still v^{j-1} there: the force LAGS THE VELOCITY BY ONE STEP, the reference's order,
+ *                kept.  (The force of step 1 is -chi (v^0 - qbar^0).)
+ *   call j >= 1: residu_j = sqrt(sum_c sum bm1 (v^{j-1} - v^j)_c^2 / volume) (normvc's l2: plain bm1), then vxo <- v^j
+ * qbar leaves as qbar^nsteps (its velocity components; the rest is not written).  residu: NULL or nsteps doubles, residu_1 ..
+ * residu_nsteps, accumulated on the device in a fixed order (no atomics) and copied once behind the map: no host
+ * synchronisation per step.  A following call with q <- f and the returned qbar continues the run; the seams are the restart
+ * of the BDF / EXT order ramp, which every map of this library has, and of the filter's Adams-Bashforth ramp (lags zero, second
+ * order for two calls).  Neither moves the fixed point v = qbar = steady solution.  chi = 0: f has the bits of
+ * nsk_nonlinear_map from the same context state (the filter still runs) -- an SFD map takes eager steps on the class launch
+ * budgets with convection and right-hand side as two kernels, the plain map may replay captured steps on per-step budgets or
+ * persistent tails with the two fused (option "conv_fuse"); those forms return the same bits (checked on the cylinder at
+ * lx1 = 6 with every default on).  The steps run eagerly, as nsk_forced_map's: no captured step graph and no launch budget
+ * of the unforced maps is touched -- the budgets are frozen and put back.  An SFD map whose solves outrun them is
+ * redone once with doubled budgets; those are kept aside for the SFD maps that follow on this context (they only grow).
+ * Memory: three velocity-sized arrays per context (vxo and two lags; uta is recomputed), allocated at the first call and kept
+ * until nsk_finalize -- 3 x ndim x nloc doubles, about 7 GB at BASELINE config 5's size; the filter state itself lives in f
+ * while the map runs.  Shards keep their own elements' part.
+ * NSK_EINVAL: shards (use nsk_group_sfd_map), rank-local contexts, lanes; a NULL vector; f, q, qbar not three distinct
+ * vectors; chi < 0 or omega_c < 0. */
+int nsk_sfd_map(nsk_ctx* ctx, nsk_vec f, nsk_vec q, nsk_vec qbar, double chi, double omega_c, double* residu);
 
 /* ---- lanes: independent maps in flight at once on one GPU ----
  * nsk_clone gives a context a second LANE: its own stream, time-stepper state, solver work arrays and projection space; geometry,
@@ -390,6 +419,11 @@ int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm
 int nsk_group_energy_budget(nsk_ctx** shards, int n, nsk_vec* ub, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* prod, nsk_vec* diss, double* integrals);
 int nsk_group_forced_map(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec* q, nsk_vec* force);
 int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w);
+/* nsk_sfd_map on the ranks of this process: f, q, qbar hold n handles each, every rank filters and forces its own elements (no
+ * halo exchange beyond the steps' own).  residu (NULL or nsteps doubles) holds the sums over ALL ranks -- per rank on the device
+ * in a fixed order, the ranks added in rank order (virtual ranks) or by the transport's all-reduce behind the map: every rank
+ * receives the same values.  Same refusals as nsk_sfd_map, per rank; contexts that are not shards: NSK_EINVAL. */
+int nsk_group_sfd_map(nsk_ctx** shards, int n, nsk_vec* f, nsk_vec* q, nsk_vec* qbar, double chi, double omega_c, double* residu);
 /* Once a process has cut its shard(s): free every device array of the parent that shards do not share (element-major geometry,
  * preconditioner factors, state, work arrays and ALL vectors allocated on the parent -- their handles become invalid).  The 1-D
  * bases and the replicated coarse operator stay.  The parent then only answers nsk_info / nsk_get_stats / nsk_finalize

@@ -111,6 +111,7 @@ SYMBOLS = {
     "nsk_group_energy_budget": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, _vpp, _vpp, _dp]),
     "nsk_group_forced_map": (C.c_int, [_vpp, C.c_int, C.c_int, _vpp, _vpp, _vpp]),
     "nsk_group_vorticity": (C.c_int, [_vpp, C.c_int, _vpp, _vpp]),
+    "nsk_group_sfd_map": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, C.c_double, C.c_double, _dp]),
     "nsk_comm_init_host": (C.c_int, [_vp, _vp, _vp, _vp]),
     "nsk_shard_release_parent": (C.c_int, [_vp]),
     "nsk_comm_unique_id": (C.c_int, [_vp]),
@@ -125,6 +126,7 @@ SYMBOLS = {
     "nsk_forced_map": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "nsk_energy_budget": (C.c_int, [_vp, _vp, _vp, _vp, _vpp, _vp, _dp]),
     "nsk_vorticity": (C.c_int, [_vp, _vp, _vp]),
+    "nsk_sfd_map": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _dp]),
     "nsk_bench_kernel": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),
     "nsk_get_step_iters": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nsk_get_stats": (C.c_int, [_vp, C.POINTER(NskStats)]),
@@ -453,6 +455,15 @@ class NekStabHip:
         """w = vorticity of q's velocity (nsk_vorticity; comp_vort3 of the reference's Rv files): mass-weighted average over
         shared nodes, no Dirichlet mask.  2-D: (omega, 0); 3-D: the curl; pressure and scalar slots of w are 0.  q is read only."""
         self._chk(self.lib.nsk_vorticity(self.ctx, q, w))
+
+    def sfd_map(self, f, q, qbar, chi, omega_c):
+        """f = the state after ``nsteps`` steps of the full equations from q under selective frequency damping (nsk_sfd_map):
+        force -chi (v - qbar), filter cut-off omega_c.  ``qbar`` enters as the filter state at the start (a copy of q: the
+        reference's run from istep = 0) and leaves as the one at the end; f, q, qbar are three distinct vectors.  Returns
+        residu_1 .. residu_nsteps, the l2 norm of the velocity change of every step."""
+        res = np.zeros(self.nsteps)
+        self._chk(self.lib.nsk_sfd_map(self.ctx, f, q, qbar, float(chi), float(omega_c), _p(res)))
+        return res
 
     # Lanes (nsk_clone) hold their solver settings BY VALUE: a setter called after lanes exist acts on every lane, so that
     # matvec_batch / band_arnoldi never apply different operators on different lanes (ADVICE r3).

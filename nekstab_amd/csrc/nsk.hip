@@ -30,6 +30,7 @@
 #include "nsk3_kernels.hpp"
 #include "nsk3_mfma.hpp"
 #include "nsk_sens.hpp"
+#include "nsk_sfd.hpp"
 
 using namespace nsk;
 
@@ -248,6 +249,20 @@ struct nsk_ctx {
   const double* force = nullptr;        // steady body force [ndim][nloc] of the running forced map (nsk_forced_map; eager steps only), else null
   double* budget_wrk = nullptr;         // nsk_energy_budget: divergence field [nloc; shards: cs], per-workgroup partials, 10 sums (first call; freed with the context)
   double* vort_mass = nullptr;          // nsk_vorticity: the assembled, unmasked mass [nloc] (first call; freed with the context)
+  // ---- selective frequency damping (nsk_sfd_map / nsk_group_sfd_map; nsk_sfd.hpp).  sfd_state: vxo and the two lags the next
+  // call reads, [3][ndim][nloc]; sfd_part: per-workgroup residual sums; sfd_hist: sum bm1 |v^{j-1} - v^j|^2 of steps 1..nsteps
+  // (first call; freed with the context).  `sfd` is set while such a map runs (eager steps only), else off.
+  double *sfd_state = nullptr, *sfd_part = nullptr, *sfd_hist = nullptr;
+  int sfd_hist_cap = 0;
+  int sfd_helm[NCLS] = {}, sfd_pres[NCLS] = {};     // class launch budgets the SFD maps of this context grew to (0: none yet): kept
+                                                    // apart from cur_helm / cur_pres, which belong to the unforced maps
+  struct SfdRun {
+    bool on = false;
+    const double* q0 = nullptr;         // the caller's qbar: the filter state the map starts from (read by call 0 of every attempt)
+    double* qw = nullptr;               // the filter state while the map runs: the velocity slots of the output vector, which
+                                        // nothing writes before the map's last step is done
+    double chi = 0.0, omega_c = 0.0;
+  } sfd;
   double* rc_big = nullptr;             // coarse restriction for nvert > 3072
   Dev d{};
   Stats hstats{};
@@ -1149,10 +1164,10 @@ static bool absorb_on(const nsk_ctx* c) {
   return c->max_pres > 0 && std::min(c->merged_iters, c->gmres_cycle) > 0;
 }
 // Convection and the velocity right-hand side in one launch (option "conv_fuse"): quadrilaterals on one rank whose velocity solve
-// is launched per iteration, no forcing added between the two halves.  Everything else -- hexahedra, shards, forced maps, the
+// is launched per iteration, no forcing added between the two halves.  Everything else -- hexahedra, shards, forced and SFD maps, the
 // persistent form, the operator tests -- keeps k_convect + k_rhs, whatever the option says.  Host-checked (eager) steps take it too.
 static bool convfuse_on(const nsk_ctx* c) {
-  if (c->conv_fuse == 0 || c->ndim != 2 || c->parent || c->d.nranks > 1 || c->fused || c->force || c->in_test) return false;
+  if (c->conv_fuse == 0 || c->ndim != 2 || c->parent || c->d.nranks > 1 || c->fused || c->force || c->sfd.on || c->in_test) return false;
   return true;
 }
 // The velocity solve on packed scratch arrays (option "helm_pack"): quadrilaterals on one rank whose solve is launched per
@@ -1575,6 +1590,31 @@ static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double sc
   hipLaunchKernelGGL(pres_tail_kernel<N>(c), dim3(c->nblk), dim3(pres_tail_threads<N>(c)), sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
 }
 
+// Call j of SFD (nsk_sfd.hpp) on the state after time step j of the running map: j = 0 .. nsteps - 1 behind the convection
+// kernel of step j + 1, j = nsteps behind the last step (no force; the filter state goes to the third state array, whose lag
+// no later call reads, so that the caller's qbar is still the map's input if the map has to be redone).
+static void sfd_call(nsk_ctx* c, int j) {
+  const Dev& d = c->d;
+  const long long nv = (long long)c->ndim * d.nloc;
+  const bool last = j == c->nsteps;
+  nsk::sfd::SfdCall s;
+  s.u = d.u; s.bf = d.bf; s.bm1 = d.bm1;
+  s.vxo = c->sfd_state; s.l1 = c->sfd_state + nv; s.l2 = c->sfd_state + 2 * nv;
+  s.qin = j == 0 ? c->sfd.q0 : c->sfd.qw;
+  s.qout = last ? s.l2 : c->sfd.qw;
+  s.part = c->sfd_part;
+  s.nloc = d.nloc; s.cs = d.cs;
+  // setab3 at constant dt: second order for istep <= 2 (the lags of call 0 are zero), third order after
+  if (j <= 2) { s.a = 1.5; s.b = -0.5; s.c = 0.0; }
+  else { s.a = 23.0 / 12.0; s.b = -16.0 / 12.0; s.c = 5.0 / 12.0; }
+  s.wdt = c->sfd.omega_c * c->dt; s.gain = -c->sfd.chi;
+  s.kind = j == 0 ? nsk::sfd::CALL0 : (last ? nsk::sfd::LAST : nsk::sfd::CALLJ);
+  const int v = nsk::sfd::width(s);
+  nsk::sfd::launch(c->stream, c->ndim, s, v);
+  if (j >= 1)
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)c->sfd_part, 1, (int)nsk::sfd::grid(d.nloc, v), c->sfd_hist + (j - 1));
+}
+
 static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_over = -1, bool tail = false, bool in_map = false) {
   Dev& d = c->d;
   const StepCoef sc = make_coef(c, istep, adjoint);
@@ -1609,6 +1649,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       hipLaunchKernelGGL(k_convect<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)d.u, d.bf, adjoint);
     if (c->force)                     // forced map: + B f where the sponge entered, before the EXT extrapolation (k_rhs)
       hipLaunchKernelGGL(nsk::sens::k_add_force, dim3((unsigned)((d.nloc + 255) / 256)), dim3(256), 0, c->stream, d.bf, d.cs, d.bm1, c->force, d.nloc, c->ndim);
+    if (c->sfd.on) sfd_call(c, istep - 1);      // SFD map: the filter, the residual and + B (-chi)(vxo - qbar) in the same place
     if (c->fused) {
       // persistent velocity solve: rhs + every CG iteration + pressure right-hand side in one launch
       HIPCHK(hipMemsetAsync(c->sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream));
@@ -1831,6 +1872,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
       }
     }
   }
+  if (c->sfd.on) sfd_call(c, c->nsteps);
   { int rc = flush_proj(c); if (rc) return rc; }          // the last step's update of the projection space: the context between maps is what it is without the option
   for (int cc = 0; cc < c->ndim; ++cc)
     HIPCHK(hipMemcpyAsync(f + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -3978,6 +4020,84 @@ int nsk_group_forced_map(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec*
     for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
   }
   return rc;
+}
+
+// ---- selective frequency damping (core/fixedp.f:114-242; nsk_sfd.hpp) -----------------------------------------------------
+// One body for a full-mesh context (a group of one) and for the ranks of one process.  Eager steps of the full equations with
+// sfd_call behind every convection kernel and behind the last step; the captured step graphs and the launch budgets belong to
+// the unforced maps: neither is touched (budgets a redone map doubled are put back, and kept aside for the next SFD map).  The filter state lives in the velocity
+// slots of f while the map runs and the caller's qbar is written only when the map stands, so a map redone with larger launch
+// budgets starts from the same qbar.
+static int sfd_map(std::vector<nsk_ctx*>& G, const char* who, bool group, nsk_vec* f, nsk_vec* q, nsk_vec* qbar, double chi, double omega_c,
+                   double* residu) {
+  const int n = (int)G.size(), ns = G[0]->nsteps;
+  int rc;
+  if (!f || !q || !qbar) return sfail(who, "bad argument");
+  if (!(chi >= 0.0) || !(omega_c >= 0.0)) return sfail(who, "chi and omega_c must be >= 0");
+  for (int r = 0; r < n; ++r) {
+    if (!f[r] || !q[r] || !qbar[r]) return sfail(who, "bad argument (f, q and qbar need one vector per rank)");
+    if (!distinct({f[r], q[r], qbar[r]})) return sfail(who, "f, q and qbar must be three distinct vectors");
+    if (G[r]->clone_of) return sfail(who, "not on a lane (nsk_clone)");
+    if (G[r]->nsteps != ns) return sfail(who, "the ranks differ in nsteps");
+  }
+  for (nsk_ctx* c : G) {
+    const size_t nv = (size_t)c->ndim * c->nloc;
+    if (!c->sfd_state && (rc = dalloc(c, &c->sfd_state, 3 * nv))) return rc;
+    if (!c->sfd_part && (rc = dalloc(c, &c->sfd_part, (size_t)nsk::sfd::grid(c->nloc, 1)))) return rc;
+    if (c->sfd_hist_cap < ns) {
+      if (c->sfd_hist) { HIPCHK(hipStreamSynchronize(c->stream)); nsk_vec v = c->sfd_hist; nsk_vec_free(c, 1, &v); c->sfd_hist = nullptr; c->sfd_hist_cap = 0; }
+      if ((rc = dalloc(c, &c->sfd_hist, (size_t)ns))) return rc;
+      c->sfd_hist_cap = ns;
+    }
+  }
+  struct Keep { int use_graph, freeze, helm[NCLS], pres[NCLS]; };
+  std::vector<Keep> keep(n);
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    keep[r].use_graph = c->use_graph; keep[r].freeze = c->budget_freeze;
+    for (int k = 0; k < NCLS; ++k) { keep[r].helm[k] = c->cur_helm[k]; keep[r].pres[k] = c->cur_pres[k]; }
+    c->sfd.on = true; c->sfd.q0 = (const double*)qbar[r]; c->sfd.qw = (double*)f[r]; c->sfd.chi = chi; c->sfd.omega_c = omega_c;
+    c->use_graph = 0;
+    c->budget_freeze = 1;
+    // an SFD map that outran the budgets was redone with doubled ones: the SFD maps that follow start from those (a run is a
+    // chain of hundreds of maps), the unforced maps get theirs back below
+    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = std::max(c->cur_helm[k], c->sfd_helm[k]); c->cur_pres[k] = std::max(c->cur_pres[k], c->sfd_pres[k]); }
+  }
+  if (group) rc = group_run_map(G, 2, (double* const*)f, (const double* const*)q);
+  else { G[0]->hstats = Stats{}; rc = run_map_adaptive(G[0], 2, (double*)f[0], (const double*)q[0]); }
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    c->sfd = nsk_ctx::SfdRun{};
+    c->use_graph = keep[r].use_graph; c->budget_freeze = keep[r].freeze;
+    for (int k = 0; k < NCLS; ++k) { c->sfd_helm[k] = c->cur_helm[k]; c->sfd_pres[k] = c->cur_pres[k]; }
+    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
+  }
+  if (rc) return rc;
+  std::vector<double> loc((size_t)n * ns, 0.0);
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    const size_t nv = (size_t)c->ndim * c->nloc;
+    HIPCHK(hipMemcpyAsync(qbar[r], c->sfd_state + 2 * nv, nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    if (residu) HIPCHK(hipMemcpyAsync(&loc[(size_t)r * ns], c->sfd_hist, (size_t)ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  }
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  if (residu) {
+    if ((rc = group_sum(G, loc.data(), ns, residu))) return rc;
+    for (int k = 0; k < ns; ++k) residu[k] = std::sqrt(residu[k] / G[0]->d.vol);       // normvc's l2, plain bm1
+  }
+  return 0;
+}
+int nsk_sfd_map(nsk_ctx* c, nsk_vec f, nsk_vec q, nsk_vec qbar, double chi, double omega_c, double* residu) {
+  int rc = sens_ctx_ok(c, "nsk_sfd_map");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return sfd_map(G, "nsk_sfd_map", false, &f, &q, &qbar, chi, omega_c, residu);
+}
+int nsk_group_sfd_map(nsk_ctx** shards, int n, nsk_vec* f, nsk_vec* q, nsk_vec* qbar, double chi, double omega_c, double* residu) {
+  int rc = sens_group_ok(shards, n, "nsk_group_sfd_map");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return sfd_map(G, "nsk_group_sfd_map", true, f, q, qbar, chi, omega_c, residu);
 }
 
 // diagnostic (NSK_STAMPS build): run `reps` full pressure iterations' k_divgs and dump the stamps

@@ -612,6 +612,7 @@ static int group_step(std::vector<nsk_ctx*>& G, int istep, int adjoint) {
         hipLaunchKernelGGL(k_convect<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, c->d, (const double*)c->d.u, c->d.bf, adjoint);
       if (c->force)                     // forced map (nsk_group_forced_map; eager steps only): + B f of the rank's own elements, as step()
         hipLaunchKernelGGL(nsk::sens::k_add_force, dim3((unsigned)((c->d.nloc + 255) / 256)), dim3(256), 0, c->stream, c->d.bf, c->d.cs, c->d.bm1, c->force, c->d.nloc, c->ndim);
+      if (c->sfd.on) sfd_call(c, istep - 1);      // SFD map (nsk_group_sfd_map; eager steps only): the rank's own elements, as step()
       hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, c->d, sc);
     }
     if ((rc = xchg_vel(G, &Dev::rloc, 0, nd)) || (rc = xchg_vel(G, &Dev::bloc, 0, nd))) return rc;
@@ -835,6 +836,7 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
         }
       }
     }
+    for (nsk_ctx* c : G) if (c->sfd.on) sfd_call(c, c->nsteps);
     Stats h;
     HIPCHK(hipMemcpyAsync(&h, G[0]->d.stats, sizeof(Stats), hipMemcpyDeviceToHost, G[0]->stream));
     HIPCHK(hipStreamSynchronize(G[0]->stream));

@@ -405,6 +405,14 @@ class ShardGroup:
         """w = vorticity of q's velocity, mass-averaged over ALL ranks (nsk_group_vorticity: one halo exchange per call)."""
         self._chk(self.lib.nsk_group_vorticity(self._arr, self.R, self._per_rank(q), self._per_rank(w)))
 
+    def sfd_map(self, f, q, qbar, chi, omega_c):
+        """NekStabHip.sfd_map on the shards (nsk_group_sfd_map): every rank filters and forces its own elements; the
+        residuals are sums over ALL ranks."""
+        res = np.zeros(self.nsteps)
+        self._chk(self.lib.nsk_group_sfd_map(self._arr, self.R, *[self._per_rank(v) for v in (f, q, qbar)], float(chi), float(omega_c),
+                                             res.ctypes.data_as(_dp)))
+        return res
+
     def stats(self):
         from .capi import NskStats
         st = NskStats()
@@ -656,6 +664,11 @@ class ShardRank:
 
     def vorticity(self, w, q):
         self._chk(self.lib.nsk_group_vorticity(self._one, 1, *self._one_of(q, w)))
+
+    def sfd_map(self, f, q, qbar, chi, omega_c):
+        res = np.zeros(self.nsteps)
+        self._chk(self.lib.nsk_group_sfd_map(self._one, 1, *self._one_of(f, q, qbar), float(chi), float(omega_c), res.ctypes.data_as(_dp)))
+        return res
 
     def stats(self):
         from .capi import NskStats
