@@ -325,6 +325,36 @@ module nekstab_hip
       real(c_double), value :: omega_c
       type(c_ptr), value :: residu
     end function
+    ! BoostConv (core/fixedp.f:282-468, uparam(1) = 1.2).  nsk_boostconv_init: allocate or reset X, Y, D, rot for snp = bst_snp
+    ! (1 .. 16) stored pairs; nsk_boostconv_core: boostconv_core (:331-393) on the velocity of rb, in place; nsk_boostconv_map:
+    ! f = nsteps steps of the full equations from q with one call behind every step j with mod(step0 + j, skip) = 0 (and j = 0
+    ! when step0 = 0), skip = bst_skp, step0 = the global istep at the start of the map.  residu: c_null_ptr or c_loc of
+    ! nsteps / skip + 2 doubles (one per call); ncalls: c_null_ptr or c_loc of an integer(c_int).  nsk_boostconv_rewind: the
+    ! state as the last map found it
+    integer(c_int) function nsk_boostconv_init(ctx, snp) bind(c, name='nsk_boostconv_init')
+      import
+      type(c_ptr), value :: ctx
+      integer(c_int), value :: snp
+    end function
+    integer(c_int) function nsk_boostconv_core(ctx, rb) bind(c, name='nsk_boostconv_core')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: rb
+    end function
+    integer(c_int) function nsk_boostconv_map(ctx, f, q, skip, step0, residu, ncalls) bind(c, name='nsk_boostconv_map')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: f
+      type(c_ptr), value :: q
+      integer(c_int), value :: skip
+      integer(c_long_long), value :: step0
+      type(c_ptr), value :: residu
+      type(c_ptr), value :: ncalls
+    end function
+    integer(c_int) function nsk_boostconv_rewind(ctx) bind(c, name='nsk_boostconv_rewind')
+      import
+      type(c_ptr), value :: ctx
+    end function
     integer(c_int) function nsk_clone(ctx, lane) bind(c, name='nsk_clone')
       import
       type(c_ptr), value :: ctx
@@ -525,6 +555,34 @@ module nekstab_hip
       real(c_double), value :: chi
       real(c_double), value :: omega_c
       type(c_ptr), value :: residu
+    end function
+    ! BoostConv on the ranks of this process (core/fixedp.f:282-468): as nsk_boostconv_*, one handle per rank
+    integer(c_int) function nsk_group_boostconv_init(shards, n, snp) bind(c, name='nsk_group_boostconv_init')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      integer(c_int), value :: snp
+    end function
+    integer(c_int) function nsk_group_boostconv_core(shards, n, rb) bind(c, name='nsk_group_boostconv_core')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: rb
+    end function
+    integer(c_int) function nsk_group_boostconv_map(shards, n, f, q, skip, step0, residu, ncalls) bind(c, name='nsk_group_boostconv_map')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: f, q
+      integer(c_int), value :: skip
+      integer(c_long_long), value :: step0
+      type(c_ptr), value :: residu
+      type(c_ptr), value :: ncalls
+    end function
+    integer(c_int) function nsk_group_boostconv_rewind(shards, n) bind(c, name='nsk_group_boostconv_rewind')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
     end function
     integer(c_int) function nsk_shard_release_parent(parent) bind(c, name='nsk_shard_release_parent')
       import

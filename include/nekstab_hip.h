@@ -298,6 +298,47 @@ int nsk_vorticity(nsk_ctx* ctx, nsk_vec q, nsk_vec w);
  * NSK_EINVAL: shards (use nsk_group_sfd_map), rank-local contexts, lanes; a NULL vector; f, q, qbar not three distinct
  * vectors; chi < 0 or omega_c < 0. */
 int nsk_sfd_map(nsk_ctx* ctx, nsk_vec f, nsk_vec q, nsk_vec qbar, double chi, double omega_c, double* residu);
+/* BoostConv (core/fixedp.f:282-468, uparam(1) = 1.2): the residual-recombination accelerator of the fixed-point iteration
+ * v <- v + r(v), r = the velocity behind a time step minus the velocity before it.
+ *
+ * nsk_boostconv_init (:353-368): allocate or reset the state of boostconv_core -- X(snp), Y(snp) velocity-sized and zero, the
+ * Gram matrix D = Y^T bm1 Y, rot -- so that the next call is a first call.  1 <= snp <= 16 (bst_snp).  Memory: 2 x snp x ndim x
+ * nloc doubles, about 48 GB at BASELINE config 5's size with snp = 10, kept until nsk_finalize or an init with another snp;
+ * the first nsk_boostconv_map adds a copy of the same size (below).  Shards keep their own elements' part.
+ *
+ * nsk_boostconv_core (:331-393): boostconv_core on the velocity components of rb, in place: rb = r on entry, xi on return; the
+ * rest of rb (pressure, scalars) is not touched.
+ *   first call:  Y(1) = X(1) = r;  rot = 1;  xi = r
+ *   later calls: Y(rot) -= r;  X(rot) -= Y(rot);  c = argmin |Y c - r| in the bm1 inner product (plain bm1, velocity only);
+ *                rot = mod(rot, snp) + 1;  Y(rot) = r;  xi = r + sum_j c_j X(j) (the OLD X(rot) included);  X(rot) = xi
+ * The reference finds c by a modified Gram-Schmidt QR of all snp columns at every call (qr_dec, linear_system).  Here only the
+ * column of D that changed is recomputed (2 snp + 1 sums per call, fixed order, no atomics) and D c = Y^T bm1 r is solved on
+ * the device: scaled by its diagonal, columns with D_jj < 1e-60 get c_j = 0 (the reference's rule, :436), Cholesky with
+ * diagonal pivoting, a scaled pivot below snp 2^-52 ends the factorisation and the columns left get c = 0.  ONE DEVIATION:
+ * where two stored differences are parallel to within about 1e-8 the reference divides by a tiny R_jj; this code drops the column.
+ *
+ * nsk_boostconv_map (:282-329): f = the state after nsteps steps of the FULL equations from q -- nsk_nonlinear_map's steps, run
+ * eagerly on frozen launch budgets exactly as nsk_sfd_map runs them -- with one BoostConv call behind certain steps.  step0 is
+ * the global step count at the start of the map (the reference's istep): a call follows step j = 1 .. nsteps of the map when
+ * (step0 + j) % skip == 0 (bst_skp), and j = 0 when step0 == 0.  A call behind step j:
+ *   r = v^j - v^{j-1} (the time stepper's lag slot 1; j = 0: the lag arrays of the reference are still zero at istep = 0, so
+ *   r = v^0 -- kept);  residu = sqrt(sum_c sum bm1 r_c^2 / volume) (normvc's l2);  xi = boostconv_core(r);  v^j <- v^{j-1} + xi.
+ * The lag arrays, the pressure and every other time-stepper array stay as they are, as in the reference.  residu: NULL or at
+ * least nsteps / skip + 2 doubles, one per call in call order, written on the device and copied once behind the map (no host
+ * read inside a map); ncalls: NULL or their count.  With skip > nsteps and step0 = 1 no call is made and f has the bits of
+ * nsk_nonlinear_map from the same context state.  A following map with q <- f and step0 + nsteps continues the run (the seam is
+ * the restart of the BDF / EXT ramp, as every map's).  A map whose solves outrun the launch budgets is redone once with doubled
+ * ones, kept aside for the BoostConv maps that follow; the calls of the first attempt have advanced X, Y and D, so a map copies
+ * them when it starts (the second 2 x snp velocity vectors) and a redone or failed map starts from / leaves that copy.
+ * NSK_EINVAL: shards (use nsk_group_boostconv_*), rank-local contexts, lanes; a NULL vector; f == q; skip < 1; step0 < 0;
+ * snp out of range; core or map without a prior nsk_boostconv_init. */
+int nsk_boostconv_init(nsk_ctx* ctx, int snp);
+int nsk_boostconv_core(nsk_ctx* ctx, nsk_vec rb);
+int nsk_boostconv_map(nsk_ctx* ctx, nsk_vec f, nsk_vec q, int skip, long long step0, double* residu, int* ncalls);
+/* Put X, Y, D and rot back to what the last nsk_boostconv_map of this context found when it started (the copy it took), so that
+ * the same map can be run again, shorter: how a driver stops at the call that converged (the reference ends the run there,
+ * :315-324).  NSK_EINVAL: no map since nsk_boostconv_init, and nsk_boostconv_core's refusals. */
+int nsk_boostconv_rewind(nsk_ctx* ctx);
 
 /* ---- lanes: independent maps in flight at once on one GPU ----
  * nsk_clone gives a context a second LANE: its own stream, time-stepper state, solver work arrays and projection space; geometry,
@@ -424,6 +465,15 @@ int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w);
  * in a fixed order, the ranks added in rank order (virtual ranks) or by the transport's all-reduce behind the map: every rank
  * receives the same values.  Same refusals as nsk_sfd_map, per rank; contexts that are not shards: NSK_EINVAL. */
 int nsk_group_sfd_map(nsk_ctx** shards, int n, nsk_vec* f, nsk_vec* q, nsk_vec* qbar, double chi, double omega_c, double* residu);
+/* nsk_boostconv_init / _core / _map (core/fixedp.f:282-468) on the ranks of this process: rb, f, q hold n handles each, every
+ * rank keeps X and Y of its own elements.  The 2 snp + 1 sums of a call are formed per rank on the device in a fixed order and
+ * added over the ranks in rank order (virtual ranks) or by the transport's all-reduce, inside the map; every rank then solves
+ * the same small system and gets the same bits of c and residu.  residu and ncalls as nsk_boostconv_map (one array for all
+ * ranks).  Same refusals, per rank; contexts that are not shards, ranks that differ in their BoostConv state: NSK_EINVAL. */
+int nsk_group_boostconv_init(nsk_ctx** shards, int n, int snp);
+int nsk_group_boostconv_core(nsk_ctx** shards, int n, nsk_vec* rb);
+int nsk_group_boostconv_map(nsk_ctx** shards, int n, nsk_vec* f, nsk_vec* q, int skip, long long step0, double* residu, int* ncalls);
+int nsk_group_boostconv_rewind(nsk_ctx** shards, int n);
 /* Once a process has cut its shard(s): free every device array of the parent that shards do not share (element-major geometry,
  * preconditioner factors, state, work arrays and ALL vectors allocated on the parent -- their handles become invalid).  The 1-D
  * bases and the replicated coarse operator stay.  The parent then only answers nsk_info / nsk_get_stats / nsk_finalize

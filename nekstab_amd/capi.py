@@ -112,6 +112,10 @@ SYMBOLS = {
     "nsk_group_forced_map": (C.c_int, [_vpp, C.c_int, C.c_int, _vpp, _vpp, _vpp]),
     "nsk_group_vorticity": (C.c_int, [_vpp, C.c_int, _vpp, _vpp]),
     "nsk_group_sfd_map": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, C.c_double, C.c_double, _dp]),
+    "nsk_group_boostconv_init": (C.c_int, [_vpp, C.c_int, C.c_int]),
+    "nsk_group_boostconv_core": (C.c_int, [_vpp, C.c_int, _vpp]),
+    "nsk_group_boostconv_map": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, C.c_int, C.c_longlong, _dp, _ip]),
+    "nsk_group_boostconv_rewind": (C.c_int, [_vpp, C.c_int]),
     "nsk_comm_init_host": (C.c_int, [_vp, _vp, _vp, _vp]),
     "nsk_shard_release_parent": (C.c_int, [_vp]),
     "nsk_comm_unique_id": (C.c_int, [_vp]),
@@ -127,6 +131,10 @@ SYMBOLS = {
     "nsk_energy_budget": (C.c_int, [_vp, _vp, _vp, _vp, _vpp, _vp, _dp]),
     "nsk_vorticity": (C.c_int, [_vp, _vp, _vp]),
     "nsk_sfd_map": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _dp]),
+    "nsk_boostconv_init": (C.c_int, [_vp, C.c_int]),
+    "nsk_boostconv_core": (C.c_int, [_vp, _vp]),
+    "nsk_boostconv_map": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_longlong, _dp, _ip]),
+    "nsk_boostconv_rewind": (C.c_int, [_vp]),
     "nsk_bench_kernel": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),
     "nsk_get_step_iters": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "nsk_get_stats": (C.c_int, [_vp, C.POINTER(NskStats)]),
@@ -464,6 +472,26 @@ class NekStabHip:
         res = np.zeros(self.nsteps)
         self._chk(self.lib.nsk_sfd_map(self.ctx, f, q, qbar, float(chi), float(omega_c), _p(res)))
         return res
+
+    def boostconv_init(self, snp):
+        """Allocate or reset the BoostConv state (nsk_boostconv_init): ``snp`` stored residual pairs, the next call is a first call."""
+        self._chk(self.lib.nsk_boostconv_init(self.ctx, int(snp)))
+
+    def boostconv_core(self, rb):
+        """boostconv_core on the velocity of ``rb``, in place (nsk_boostconv_core): the residual r enters, xi leaves."""
+        self._chk(self.lib.nsk_boostconv_core(self.ctx, rb))
+
+    def boostconv_map(self, f, q, skip, step0):
+        """f = the state after ``nsteps`` steps of the full equations from q with one BoostConv call behind every step j whose
+        global count ``step0`` + j is a multiple of ``skip`` (and j = 0 when ``step0`` = 0) (nsk_boostconv_map).  Returns the
+        residu of every call, in call order."""
+        res, nc = np.zeros(self.nsteps // int(skip) + 2), C.c_int(0)
+        self._chk(self.lib.nsk_boostconv_map(self.ctx, f, q, int(skip), int(step0), _p(res), C.byref(nc)))
+        return res[:nc.value]
+
+    def boostconv_rewind(self):
+        """The BoostConv state as the last boostconv_map found it (nsk_boostconv_rewind)."""
+        self._chk(self.lib.nsk_boostconv_rewind(self.ctx))
 
     # Lanes (nsk_clone) hold their solver settings BY VALUE: a setter called after lanes exist acts on every lane, so that
     # matvec_batch / band_arnoldi never apply different operators on different lanes (ADVICE r3).

@@ -31,6 +31,7 @@
 #include "nsk3_mfma.hpp"
 #include "nsk_sens.hpp"
 #include "nsk_sfd.hpp"
+#include "nsk_boostconv.hpp"
 
 using namespace nsk;
 
@@ -263,7 +264,23 @@ struct nsk_ctx {
                                         // nothing writes before the map's last step is done
     double chi = 0.0, omega_c = 0.0;
   } sfd;
-  double* rc_big = nullptr;             // coarse restriction for nvert > 3072
+  // ---- BoostConv (nsk_boostconv_* / nsk_group_boostconv_*; nsk_boostconv.hpp).  bcv_X, bcv_Y: [snp][ndim][nloc]; bcv_small: D
+  // [16][16], then c [16]; bcv_tot: the 2 snp + 1 totals of a call (all-reduced on shards); bcv_part: per-workgroup partials;
+  // bcv_hist: residu per call of the running map; bcv_save: X, Y and bcv_small as the running map found them (nsk_boostconv_init
+  // and the first map; freed with the context).  bcv_count: calls since nsk_boostconv_init (0: the next one is a first call),
+  // bcv_rot: the 0-based column the next call updates.  `bcv` is set while a map runs (eager steps only), else off.
+  double *bcv_X = nullptr, *bcv_Y = nullptr, *bcv_small = nullptr, *bcv_tot = nullptr, *bcv_part = nullptr, *bcv_hist = nullptr, *bcv_save = nullptr;
+  int bcv_snp = 0, bcv_rot = 0, bcv_hist_cap = 0;
+  long long bcv_count = 0;
+  int bcv_helm[NCLS] = {}, bcv_pres[NCLS] = {};     // class launch budgets the BoostConv maps of this context grew to (as sfd_helm)
+  struct BcvRun {
+    bool on = false;
+    int skip = 1, ncall = 0, attempt = 0;             // ncall: calls of this attempt
+    long long step0 = 0;
+  } bcv;
+  long long bcv_count0 = -1;                        // bcv_count and bcv_rot of the state in bcv_save (-1: bcv_save holds none)
+  int bcv_rot0 = 0;
+  double* rc_big = nullptr;            // coarse restriction for nvert > 3072
   Dev d{};
   Stats hstats{};
   hipStream_t stream = nullptr;
@@ -1615,6 +1632,69 @@ static void sfd_call(nsk_ctx* c, int j) {
     hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(256), 0, c->stream, (const double*)c->sfd_part, 1, (int)nsk::sfd::grid(d.nloc, v), c->sfd_hist + (j - 1));
 }
 
+// One BoostConv call (nsk_boostconv.hpp) on every rank of G.  rb: nsk_boostconv_core's vectors (r = their velocity, replaced
+// by xi); nullptr: the running map -- r = u - ulag slot 1 (`lag`; else r = u, the reference's istep = 0), u = lag + xi, residu
+// to the next entry of bcv_hist.  A full-mesh context sums its partials inside k_bcv_solve; shards sum theirs per rank in a
+// fixed order, the ranks' totals go through the step's all-reduce, and every rank solves the same system.
+static int allreduce_ptr(std::vector<nsk_ctx*>& G, double* nsk_ctx::*buf, int n);
+static int bcv_call(std::vector<nsk_ctx*>& G, const nsk_vec* rb, bool lag) {
+  const bool sharded = G[0]->parent != nullptr;
+  const bool first = G[0]->bcv_count == 0;
+  const int snp = G[0]->bcv_snp, rows = first ? 1 : 2 * snp + 1;
+  std::vector<nsk::bcv::BcvCall> S(G.size());
+  std::vector<int> W(G.size());
+  auto solve = [&](nsk_ctx* c, const double* part, int nwg) {
+    double* small = c->bcv_small;
+    hipLaunchKernelGGL(nsk::bcv::k_bcv_solve, dim3(1), dim3(256), 0, c->stream, part, nwg, c->bcv_tot, small, small + nsk::bcv::SNP_MAX * nsk::bcv::SNP_MAX,
+                       c->bcv_hist + (rb ? 0 : c->bcv.ncall), snp, c->bcv_rot, first ? 1 : 0, c->d.vol);
+  };
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r];
+    const Dev& d = c->d;
+    nsk::bcv::BcvCall& s = S[r];
+    s.u = rb ? (double*)rb[r] : d.u;
+    s.a = s.u;
+    s.b = (!rb && lag) ? d.ulag : nullptr;
+    s.bm1 = d.bm1; s.X = c->bcv_X; s.Y = c->bcv_Y; s.part = c->bcv_part;
+    s.c = c->bcv_small + nsk::bcv::SNP_MAX * nsk::bcv::SNP_MAX;
+    s.nloc = d.nloc; s.cs = rb ? d.nloc : d.cs;
+    s.snp = snp; s.rot = c->bcv_rot; s.first = first ? 1 : 0;
+    W[r] = nsk::bcv::width(s);
+    nsk::bcv::launch_dots(c->stream, c->ndim, s, W[r]);
+    const int nwg = (int)nsk::bcv::grid(d.nloc, W[r]);
+    if (!sharded) solve(c, c->bcv_part, nwg);
+    else hipLaunchKernelGGL(k_tot2, dim3(rows), dim3(256), 0, c->stream, (const double*)c->bcv_part, nwg, c->bcv_tot, (const int*)nullptr);
+  }
+  if (sharded) {
+    int rc = allreduce_ptr(G, &nsk_ctx::bcv_tot, rows);
+    if (rc) return rc;
+    for (nsk_ctx* c : G) solve(c, nullptr, 0);
+  }
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r];
+    if (!first) {
+      S[r].rot = c->bcv_rot = (c->bcv_rot + 1) % snp;
+      nsk::bcv::launch_apply(c->stream, c->ndim, S[r], W[r]);
+    }
+    c->bcv_count++;
+    if (!rb) c->bcv.ncall++;
+  }
+  return 0;
+}
+// the state of a BoostConv map's ranks as the map found it: a map that is redone starts from it again
+static int bcv_restore(nsk_ctx* c) {
+  const size_t nx = (size_t)c->bcv_snp * c->ndim * c->nloc, nsm = (size_t)nsk::bcv::SNP_MAX * (nsk::bcv::SNP_MAX + 1);
+  HIPCHK(hipMemcpyAsync(c->bcv_X, c->bcv_save, nx * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->bcv_Y, c->bcv_save + nx, nx * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->bcv_small, c->bcv_save + 2 * nx, nsm * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  c->bcv_count = c->bcv_count0; c->bcv_rot = c->bcv_rot0;
+  return 0;
+}
+static int bcv_begin_attempt(nsk_ctx* c) {
+  c->bcv.ncall = 0;
+  return c->bcv.attempt++ > 0 ? bcv_restore(c) : 0;
+}
+
 static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_over = -1, bool tail = false, bool in_map = false) {
   Dev& d = c->d;
   const StepCoef sc = make_coef(c, istep, adjoint);
@@ -1843,6 +1923,12 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
     if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
     HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
   }
+  std::vector<nsk_ctx*> G1(1, c);
+  if (c->bcv.on) {                                            // BoostConv map: the reference's call at istep = 0 (lag = 0) opens a run
+    int rc = bcv_begin_attempt(c);
+    if (!rc && c->bcv.step0 == 0) rc = bcv_call(G1, nullptr, false);
+    if (rc) return rc;
+  }
   if (absorb_on(c)) { c->up_host = true; c->absorb_maps++; }
   if (convfuse_on(c)) c->convfuse_steps += c->nsteps;
   if (helmpack_on(c)) c->helmpack_steps += c->nsteps;
@@ -1871,6 +1957,8 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
         fprintf(stderr, "step %3d: |g|=%.3e |g'|=%.3e nit=%d resid=%.3e nproj=%d pcnt=%d st_n=%.3e  helm ref %.3e %.3e\n", istep, G.gnorm0, G.beta0, G.nit, G.resid, G.nproj, G.pcnt, G.st_n, hs[16], hs[17]);
       }
     }
+    // BoostConv map (eager steps only): the call behind global step step0 + istep
+    if (c->bcv.on && (c->bcv.step0 + istep) % c->bcv.skip == 0) { int rc = bcv_call(G1, nullptr, true); if (rc) return rc; }
   }
   if (c->sfd.on) sfd_call(c, c->nsteps);
   { int rc = flush_proj(c); if (rc) return rc; }          // the last step's update of the projection space: the context between maps is what it is without the option
@@ -4098,6 +4186,165 @@ int nsk_group_sfd_map(nsk_ctx** shards, int n, nsk_vec* f, nsk_vec* q, nsk_vec* 
   if (rc) return rc;
   std::vector<nsk_ctx*> G(shards, shards + n);
   return sfd_map(G, "nsk_group_sfd_map", true, f, q, qbar, chi, omega_c, residu);
+}
+
+// ---- BoostConv (core/fixedp.f:282-468; nsk_boostconv.hpp) ------------------------------------------------------------------
+// One body per entry for a full-mesh context (a group of one) and for the ranks of one process, as sfd_map.
+static void bcv_free(nsk_ctx* c, double** p) {
+  if (*p) { nsk_vec v = *p; nsk_vec_free(c, 1, &v); *p = nullptr; }
+}
+static int bcv_init(std::vector<nsk_ctx*>& G, const char* who, int snp) {
+  int rc;
+  if (snp < 1 || snp > nsk::bcv::SNP_MAX) return sfail(who, "snp must be 1 .. 16");
+  for (nsk_ctx* c : G) if (c->clone_of) return sfail(who, "not on a lane (nsk_clone)");
+  for (nsk_ctx* c : G) {
+    const size_t nx = (size_t)snp * c->ndim * c->nloc, nsm = (size_t)nsk::bcv::SNP_MAX * (nsk::bcv::SNP_MAX + 1);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->bcv_snp != snp) {
+      bcv_free(c, &c->bcv_X); bcv_free(c, &c->bcv_Y); bcv_free(c, &c->bcv_save);
+      c->bcv_snp = 0;
+      if ((rc = dalloc(c, &c->bcv_X, nx)) || (rc = dalloc(c, &c->bcv_Y, nx))) return rc;
+    }
+    if (!c->bcv_small && ((rc = dalloc(c, &c->bcv_small, nsm)) || (rc = dalloc(c, &c->bcv_tot, (size_t)2 * nsk::bcv::SNP_MAX + 2)) ||
+                          (rc = dalloc(c, &c->bcv_part, (size_t)(2 * nsk::bcv::SNP_MAX + 1) * nsk::bcv::grid(c->nloc, 1))) || (rc = dalloc(c, &c->bcv_hist, 1))))
+      return rc;
+    if (c->bcv_hist_cap < 1) c->bcv_hist_cap = 1;
+    HIPCHK(hipMemsetAsync(c->bcv_X, 0, nx * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->bcv_Y, 0, nx * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(c->bcv_small, 0, nsm * sizeof(double), c->stream));
+    c->bcv_snp = snp; c->bcv_rot = 0; c->bcv_count = 0; c->bcv_count0 = -1;
+  }
+  return 0;
+}
+static int bcv_ready(std::vector<nsk_ctx*>& G, const char* who) {
+  for (nsk_ctx* c : G) {
+    if (c->clone_of) return sfail(who, "not on a lane (nsk_clone)");
+    if (c->bcv_snp < 1) return sfail(who, "no BoostConv state: call nsk_boostconv_init first");
+    if (c->bcv_snp != G[0]->bcv_snp || c->bcv_count != G[0]->bcv_count) return sfail(who, "the ranks differ in their BoostConv state");
+  }
+  return 0;
+}
+static int bcv_core(std::vector<nsk_ctx*>& G, const char* who, nsk_vec* rb) {
+  int rc;
+  if (!rb) return sfail(who, "bad argument");
+  for (size_t r = 0; r < G.size(); ++r) if (!rb[r]) return sfail(who, "bad argument (one vector per rank)");
+  if ((rc = bcv_ready(G, who))) return rc;
+  return bcv_call(G, rb, false);
+}
+// Eager steps of the full equations on frozen budgets, exactly as sfd_map runs them, with bcv_call behind the steps the rule
+// selects.  The state is copied when the map starts: a map redone with larger launch budgets, or one that fails, starts from /
+// leaves the state the caller had.
+static int bcv_map(std::vector<nsk_ctx*>& G, const char* who, bool group, nsk_vec* f, nsk_vec* q, int skip, long long step0, double* residu, int* ncalls) {
+  const int n = (int)G.size(), ns = G[0]->nsteps;
+  int rc;
+  if (!f || !q) return sfail(who, "bad argument");
+  if (skip < 1) return sfail(who, "skip must be >= 1");
+  if (step0 < 0) return sfail(who, "step0 must be >= 0");
+  for (int r = 0; r < n; ++r) {
+    if (!f[r] || !q[r]) return sfail(who, "bad argument (f and q need one vector per rank)");
+    if (f[r] == q[r]) return sfail(who, "needs f != q");
+    if (G[r]->nsteps != ns) return sfail(who, "the ranks differ in nsteps");
+  }
+  if ((rc = bcv_ready(G, who))) return rc;
+  const int cap = ns / skip + 2;
+  for (nsk_ctx* c : G) {
+    const size_t nx = (size_t)c->bcv_snp * c->ndim * c->nloc, nsm = (size_t)nsk::bcv::SNP_MAX * (nsk::bcv::SNP_MAX + 1);
+    if (c->bcv_hist_cap < cap) {
+      HIPCHK(hipStreamSynchronize(c->stream));
+      bcv_free(c, &c->bcv_hist); c->bcv_hist_cap = 0;
+      if ((rc = dalloc(c, &c->bcv_hist, (size_t)cap))) return rc;
+      c->bcv_hist_cap = cap;
+    }
+    if (!c->bcv_save && (rc = dalloc(c, &c->bcv_save, 2 * nx + nsm))) return rc;
+    HIPCHK(hipMemcpyAsync(c->bcv_save, c->bcv_X, nx * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bcv_save + nx, c->bcv_Y, nx * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bcv_save + 2 * nx, c->bcv_small, nsm * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  }
+  struct Keep { int use_graph, freeze, helm[NCLS], pres[NCLS]; };
+  std::vector<Keep> keep(n);
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    keep[r].use_graph = c->use_graph; keep[r].freeze = c->budget_freeze;
+    for (int k = 0; k < NCLS; ++k) { keep[r].helm[k] = c->cur_helm[k]; keep[r].pres[k] = c->cur_pres[k]; }
+    c->bcv = nsk_ctx::BcvRun{};
+    c->bcv.on = true; c->bcv.skip = skip; c->bcv.step0 = step0;
+    c->bcv_count0 = c->bcv_count; c->bcv_rot0 = c->bcv_rot;
+    c->use_graph = 0;
+    c->budget_freeze = 1;
+    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = std::max(c->cur_helm[k], c->bcv_helm[k]); c->cur_pres[k] = std::max(c->cur_pres[k], c->bcv_pres[k]); }
+  }
+  if (group) rc = group_run_map(G, 2, (double* const*)f, (const double* const*)q);
+  else { G[0]->hstats = Stats{}; rc = run_map_adaptive(G[0], 2, (double*)f[0], (const double*)q[0]); }
+  const int nc = G[0]->bcv.ncall;
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    if (rc) (void)bcv_restore(c);
+    c->bcv = nsk_ctx::BcvRun{};
+    c->use_graph = keep[r].use_graph; c->budget_freeze = keep[r].freeze;
+    for (int k = 0; k < NCLS; ++k) { c->bcv_helm[k] = c->cur_helm[k]; c->bcv_pres[k] = c->cur_pres[k]; }
+    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
+  }
+  if (rc) return rc;
+  if (ncalls) *ncalls = nc;
+  // (every rank solved the same system from the same totals: the history of the first one is everybody's)
+  if (residu && nc > 0) HIPCHK(hipMemcpyAsync(residu, G[0]->bcv_hist, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, G[0]->stream));
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+static int bcv_rewind(std::vector<nsk_ctx*>& G, const char* who) {
+  int rc = bcv_ready(G, who);
+  if (rc) return rc;
+  for (nsk_ctx* c : G) if (c->bcv_count0 < 0) return sfail(who, "no map has run since nsk_boostconv_init");
+  for (nsk_ctx* c : G) if ((rc = bcv_restore(c))) return rc;
+  return 0;
+}
+int nsk_boostconv_init(nsk_ctx* c, int snp) {
+  int rc = sens_ctx_ok(c, "nsk_boostconv_init");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return bcv_init(G, "nsk_boostconv_init", snp);
+}
+int nsk_boostconv_core(nsk_ctx* c, nsk_vec rb) {
+  int rc = sens_ctx_ok(c, "nsk_boostconv_core");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return bcv_core(G, "nsk_boostconv_core", &rb);
+}
+int nsk_boostconv_map(nsk_ctx* c, nsk_vec f, nsk_vec q, int skip, long long step0, double* residu, int* ncalls) {
+  int rc = sens_ctx_ok(c, "nsk_boostconv_map");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return bcv_map(G, "nsk_boostconv_map", false, &f, &q, skip, step0, residu, ncalls);
+}
+int nsk_boostconv_rewind(nsk_ctx* c) {
+  int rc = sens_ctx_ok(c, "nsk_boostconv_rewind");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return bcv_rewind(G, "nsk_boostconv_rewind");
+}
+int nsk_group_boostconv_rewind(nsk_ctx** shards, int n) {
+  int rc = sens_group_ok(shards, n, "nsk_group_boostconv_rewind");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return bcv_rewind(G, "nsk_group_boostconv_rewind");
+}
+int nsk_group_boostconv_init(nsk_ctx** shards, int n, int snp) {
+  int rc = sens_group_ok(shards, n, "nsk_group_boostconv_init");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return bcv_init(G, "nsk_group_boostconv_init", snp);
+}
+int nsk_group_boostconv_core(nsk_ctx** shards, int n, nsk_vec* rb) {
+  int rc = sens_group_ok(shards, n, "nsk_group_boostconv_core");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return bcv_core(G, "nsk_group_boostconv_core", rb);
+}
+int nsk_group_boostconv_map(nsk_ctx** shards, int n, nsk_vec* f, nsk_vec* q, int skip, long long step0, double* residu, int* ncalls) {
+  int rc = sens_group_ok(shards, n, "nsk_group_boostconv_map");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return bcv_map(G, "nsk_group_boostconv_map", true, f, q, skip, step0, residu, ncalls);
 }
 
 // diagnostic (NSK_STAMPS build): run `reps` full pressure iterations' k_divgs and dump the stamps

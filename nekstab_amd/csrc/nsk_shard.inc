@@ -820,6 +820,10 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
         HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
       }
     }
+    if (G[0]->bcv.on) {                                      // BoostConv map (nsk_group_boostconv_map), as run_map
+      for (nsk_ctx* c : G) { int rc = bcv_begin_attempt(c); if (rc) return rc; }
+      if (G[0]->bcv.step0 == 0) { int rc = bcv_call(G, nullptr, false); if (rc) return rc; }
+    }
     for (int istep = 1; istep <= G[0]->nsteps; ++istep) {
       if (graph) { HIPCHK(hipGraphLaunch(G[0]->graphs[adjoint][step_class(istep)].exec, G[0]->stream)); continue; }
       int rc = group_step(G, istep, adjoint);
@@ -835,6 +839,7 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
                   s2.helm_iters, s2.pres_iters, Gs.gnorm0, Gs.beta0, Gs.nit, Gs.resid, Gs.nproj, hs[16], hs[17], hs[2], hs[6], hs[3], hs[7]);
         }
       }
+      if (G[0]->bcv.on && (G[0]->bcv.step0 + istep) % G[0]->bcv.skip == 0) { int rc2 = bcv_call(G, nullptr, true); if (rc2) return rc2; }
     }
     for (nsk_ctx* c : G) if (c->sfd.on) sfd_call(c, c->nsteps);
     Stats h;

@@ -413,6 +413,24 @@ class ShardGroup:
                                              res.ctypes.data_as(_dp)))
         return res
 
+    def boostconv_init(self, snp):
+        """NekStabHip.boostconv_init on the shards (nsk_group_boostconv_init): every rank keeps X, Y of its own elements."""
+        self._chk(self.lib.nsk_group_boostconv_init(self._arr, self.R, int(snp)))
+
+    def boostconv_core(self, rb):
+        self._chk(self.lib.nsk_group_boostconv_core(self._arr, self.R, self._per_rank(rb)))
+
+    def boostconv_map(self, f, q, skip, step0):
+        """NekStabHip.boostconv_map on the shards (nsk_group_boostconv_map): the sums of a call run over ALL ranks, every rank
+        solves the same small system."""
+        res, nc = np.zeros(self.nsteps // int(skip) + 2), C.c_int(0)
+        self._chk(self.lib.nsk_group_boostconv_map(self._arr, self.R, self._per_rank(f), self._per_rank(q), int(skip), int(step0),
+                                                   res.ctypes.data_as(_dp), C.byref(nc)))
+        return res[:nc.value]
+
+    def boostconv_rewind(self):
+        self._chk(self.lib.nsk_group_boostconv_rewind(self._arr, self.R))
+
     def stats(self):
         from .capi import NskStats
         st = NskStats()
@@ -669,6 +687,20 @@ class ShardRank:
         res = np.zeros(self.nsteps)
         self._chk(self.lib.nsk_group_sfd_map(self._one, 1, *self._one_of(f, q, qbar), float(chi), float(omega_c), res.ctypes.data_as(_dp)))
         return res
+
+    def boostconv_init(self, snp):
+        self._chk(self.lib.nsk_group_boostconv_init(self._one, 1, int(snp)))
+
+    def boostconv_core(self, rb):
+        self._chk(self.lib.nsk_group_boostconv_core(self._one, 1, *self._one_of(rb)))
+
+    def boostconv_map(self, f, q, skip, step0):
+        res, nc = np.zeros(self.nsteps // int(skip) + 2), C.c_int(0)
+        self._chk(self.lib.nsk_group_boostconv_map(self._one, 1, *self._one_of(f, q), int(skip), int(step0), res.ctypes.data_as(_dp), C.byref(nc)))
+        return res[:nc.value]
+
+    def boostconv_rewind(self):
+        self._chk(self.lib.nsk_group_boostconv_rewind(self._one, 1))
 
     def stats(self):
         from .capi import NskStats
