@@ -79,14 +79,16 @@ int nsk_init(const nsk_case* c, nsk_ctx** out);
 /* The same with one Dirichlet mask per velocity component: symmetry boundaries.  On a face whose normal is a coordinate axis
  * 'SYM' fixes the normal component only, 'ON ' the tangential one only, 'v' / 'V' / 'W' all; a node takes the minimum over its
  * copies, per component; the free components get the natural (zero-stress) condition of the weak form
- * [UPSTREAM bcmask, non-stress branch: v1mask, v2mask, v3mask].  cmask[k], k < ndim: [nel*lx1*lx1], 1 free / 0 fixed;
- * c->mask is not read.  Every masked operation then takes its component's mask: Helmholtz residual and Jacobi diagonal, opbinv
- * inside E = D B^-1 D^T (and with it the Schwarz patches, the coarse operator and its image, all built from E), the velocity
- * correction, bcdirvc in nsk_seed_noise (core/utils.f:398).  cmask == NULL: nsk_init.  Equal components: the context nsk_init
- * makes of that mask, bit for bit.  Quadrilaterals (lx1 = 6, 8, 10, 12) on one rank and their nsk_clone lanes; ndim = 3:
- * NSK_EINVAL, and so are nsk_shard_create / nsk_shard_create_local, the options "fused" and "helm_fdm" and the kernel hooks
- * nsk_bench_kernel, nsk_debug_stamps, nsk_test_helm_solve on such a context.  A symmetry face that is not
- * axis-aligned needs the stress formulation, which is not built: the caller refuses it (nekstab_amd/mesh.py does). */
+ * [UPSTREAM bcmask, non-stress branch: v1mask, v2mask, v3mask].  cmask[k], k < ndim: [nel*lx1^ndim], 1 free / 0 fixed (ndim = 3:
+ * no other value, NSK_EINVAL); c->mask is not read.  Every masked operation then takes its component's mask: Helmholtz residual
+ * and Jacobi diagonal, opbinv inside E = D B^-1 D^T (and with it the Schwarz patches -- the face ratio of the component along the
+ * face normal --, the coarse operator and its image, all built from E), the velocity correction, bcdirvc in nsk_seed_noise
+ * (core/utils.f:398).  cmask == NULL: nsk_init.  Equal components: the context nsk_init makes of that mask, bit for bit.
+ * Quadrilaterals (lx1 = 6, 8, 10, 12) on one rank and their nsk_clone lanes; hexahedra (lx1 = 6, 8, 10) on one rank.  NSK_EINVAL on such
+ * a context: nsk_shard_create / nsk_shard_create_local, the options "fused" and "helm_fdm", on hexahedra also "eapply_pipe" = 3
+ * (k_divgs_w), and the kernel hooks
+ * nsk_bench_kernel, nsk_debug_stamps, nsk_test_helm_solve.  A symmetry face that is not axis-aligned needs
+ * the stress formulation, which is not built: the caller refuses it (nekstab_amd/mesh.py and mesh3d.py do). */
 int nsk_init_masks(const nsk_case* c, const double* const* cmask, nsk_ctx** out);
 int nsk_finalize(nsk_ctx* ctx);
 const char* nsk_last_error(void);

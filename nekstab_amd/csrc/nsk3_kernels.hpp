@@ -755,12 +755,25 @@ __device__ inline double corner_list_sum(const double* v, const double* __restri
 __device__ inline double lane_f64(double v, int lane) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane), __builtin_amdgcn_readlane(__double2loint(v), lane));
 }
-template <int N>
+// One Dirichlet mask per velocity component on hexahedra (contexts of nsk_init_masks; the <.., CM = true> kernel forms).  Three masks
+// and three diagonals per node would be twelve registers where the shared-mask forms hold four, and k_helm is built at its register
+// limit.  A masked array is its unmasked twin times a 0/1 flag, so the set-up (build3) stores what is not redundant:
+//   Dev::mask  [3][nloc] doubles (k_vel_update_cm, k_seed_avg_cm), then nloc 32-bit words: bit c = component c is free
+//   Dev::dinv  [3 orders][nloc], the UNMASKED Jacobi diagonal
+//   Dev::binv  [3][nloc] masked (k_vel_update_cm), then [nloc] unmasked
+// and a CM form loads the word (one register) and one unmasked value: a register less than its twin in k_helm, one more in the
+// kernels that apply B^-1.  cm_sel(bits, c, v) = mask_c * v for the 0/1 mask.  k_helm masks only what it gathers (r = mask dssum(rhs),
+// w = mask dssum(A z)): r, p, s and x of a fixed component are then zero from it = 0 on, and z = diag r needs no mask of its own.
+__device__ inline int cm_bits(const Dev& d, long long l) { return reinterpret_cast<const int*>(d.mask + 3 * d.nloc)[l]; }
+__device__ inline double cm_sel(int bits, int c, double v) { return ((bits >> c) & 1) ? v : 0.0; }
+
+template <int N, bool CM = false>
 __device__ inline void helm_first(const Dev& d, const StepCoef& sc, const double* __restrict__ rhs, double* sD, double* sDt,
                                   double* sz, double* st, double* sred, double* scv) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, NT = C::NT;
   static_assert(NT >= 128 && N * N <= NT, "corner entries and the basis: one per thread");
+  constexpr bool LATE = CM && N >= 10;
   const int tid = threadIdx.x;
   const long long e = d.boff + xcd_element(blockIdx.x, gridDim.x);
   const bool act = tid < NN;
@@ -772,9 +785,9 @@ __device__ inline void helm_first(const Dev& d, const StepCoef& sc, const double
   double bm = 0, g[6] = {0, 0, 0, 0, 0, 0}, mk = 0, mi = 0, di = 0;
   if (act) {
     tab = d.gs_tab[l];
-    bm = d.bm1[l]; mk = d.mask[l]; mi = d.minv[l];
+    if constexpr (!LATE) { bm = d.bm1[l]; if constexpr (!CM) mk = d.mask[l]; mi = d.minv[l]; }
     load_g6(d, l, g);
-    di = d.dinv[(size_t)(sc.k - 1) * d.nloc + l];
+    if constexpr (!LATE) di = d.dinv[(size_t)(sc.k - 1) * d.nloc + l];
   }
   if (tid < N * N) { sD[tid] = dv; sDt[(tid % N) * N + tid / N] = dv; }
   const int cid = act ? corner_id<N>(k, j, i) : -1;
@@ -784,6 +797,11 @@ __device__ inline void helm_first(const Dev& d, const StepCoef& sc, const double
     const long long lc = c * nl + l;
     const double* f0 = rhs + c * nl;
     const double* f1 = d.bloc + c * nl;
+    // CM (k_helm_first_cm, once per solve): the component's mask is loaded here, per component; at lx1 = 10 (LATE) so are the arrays
+    // every component reads, instead of being held across the loop -- 0 bytes of scratch where holding them costs 24 (and at
+    // lx1 = 8 the other way round: 12 against 0; compiler's numbers)
+    if constexpr (CM) { if (act) mk = d.mask[(size_t)c * d.nloc + l]; }
+    if constexpr (LATE) { if (act) { bm = d.bm1[l]; mi = d.minv[l]; di = d.dinv[(size_t)(sc.k - 1) * d.nloc + l]; } }
     if (tid < 128) scv[tid] = (cm == -2) ? __builtin_nan("") : ((cm >= 0) ? ((tid < 64) ? f0[cm] : f1[cm]) : -0.0);
     GsVals gv, gb;
     if (act && !wide) { gv = gs_load_o(f0, tab, (unsigned)l); gb = gs_load_o(f1, tab, (unsigned)l); }
@@ -825,7 +843,7 @@ __device__ inline void helm_first(const Dev& d, const StepCoef& sc, const double
 // it >= 1: every load of the three components is issued before the first is used -- two round trips to memory per workgroup (the
 // arrays addressable from the thread index, then the neighbours' values) where the component loop of rounds 2-4 had five -- and the
 // three components' A z then run one after the other on one set of LDS tiles, on the matrix cores (axhelm3_mfma).
-template <int N>
+template <int N, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm(Dev d, StepCoef sc, int it, const double* rhs) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, NT = C::NT;
@@ -838,7 +856,8 @@ __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm(Dev d, Ste
   double* sz = tiles; double* sW = tiles + 3 * EXT; double* sO = tiles + 6 * EXT;
   __shared__ double sred[12 * 16];
   __shared__ double scv[192];
-  if (it == 0) { helm_first<N>(d, sc, rhs, sW, sW + N * N, sz, sW + 2 * N * N, sred, scv); return; }
+  // (CM: it >= 1 only, it = 0 is k_helm_first_cm -- one kernel holding both paths spills 36 bytes at lx1 = 10, the two kernels none)
+  if constexpr (!CM) { if (it == 0) { helm_first<N>(d, sc, rhs, sW, sW + N * N, sz, sW + 2 * N * N, sred, scv); return; } }
   const int tid = threadIdx.x;
   const long long e = d.boff + xcd_element(blockIdx.x, gridDim.x);      // (boff: shards launch their boundary elements first, the interior behind)
   const bool act = tid < NN;
@@ -906,8 +925,11 @@ __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm(Dev d, Ste
   const int tn = k * L::PS + j * L::RS + i;
   double bm = 0, g[6] = {0, 0, 0, 0, 0, 0}, mk = 0, mi = 0, di = 0;
   double ro[3] = {0, 0, 0}, po[3] = {0, 0, 0}, so[3] = {0, 0, 0}, xo[3] = {0, 0, 0};
+  int fb = 0;                                                        // CM: the free components of the node (mk is not loaded)
   if (act) {
-    mk = d.mask[l]; di = d.dinv[(size_t)(sc.k - 1) * d.nloc + l];
+    if constexpr (CM) fb = cm_bits(d, l);
+    else mk = d.mask[l];
+    di = d.dinv[(size_t)(sc.k - 1) * d.nloc + l];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const long long lc = c * nl + l;
@@ -945,7 +967,7 @@ __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm(Dev d, Ste
         const double* wl = wl0 + (size_t)c * nl;
         const double sum = !wide ? (((gv[c].a + gv[c].b) + gv[c].c) + gv[c].d)
                                  : (from_list ? corner_list_sum(scv + c * 64 + cid * 8, wl, d, l) : gs_csr_rolled(wl, d, l));
-        const double w = mk * sum;
+        const double w = CM ? cm_sel(fb, c, sum) : mk * sum;
         const double pn = di * ro[c] + beta[c] * po[c];
         const double sn = w + beta[c] * so[c];
         d.hp[lc] = pn; d.hs[lc] = sn;
@@ -988,6 +1010,17 @@ __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm(Dev d, Ste
   }
 }
 
+// it = 0 of the component-mask velocity solve as a kernel of its own (k_helm<N, true> and k_helm_p<10, true> are it >= 1)
+template <int N>
+__global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm_first_cm(Dev d, StepCoef sc, const double* rhs) {
+  using L = SlimLay<N>;
+  constexpr int EXT = L::EXT;
+  static_assert(2 * N * N + 3 * Cfg<N>::NN <= 5 * EXT, "the tiles of helm_first");
+  __shared__ double tiles[8 * EXT];
+  __shared__ double sred[12 * 16];
+  __shared__ double scv[192];
+  helm_first<N, true>(d, sc, rhs, tiles + 3 * EXT, tiles + 3 * EXT + N * N, tiles, tiles + 3 * EXT + 2 * N * N, sred, scv);
+}
 
 // k_helm (it >= 1) as RESIDENT workgroups that walk their share of the elements, the next element's r, p, s, x (twelve arrays,
 // 96 KB at lx1 = 10) arriving in LDS by LDS-DMA (global_load_lds_dwordx4: no register is their destination) while the current
@@ -1009,7 +1042,7 @@ __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm(Dev d, Ste
 #define NSK_HP_NT_LD ""
 #define NSK_HP_ST(p, v) (*(p) = (v))
 #endif
-template <int N>
+template <int N, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm_p(Dev d, StepCoef sc, int it, int count) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, NT = C::NT;
@@ -1126,8 +1159,11 @@ __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm_p(Dev d, S
     const int wv = __builtin_amdgcn_readfirstlane(tl >> 6);
     double cv = ld_boff((wv == 0) ? w0 : ((wv == 1) ? w1 : w2), oc);         // waves 0..2: the corner lists of component wv
     const unsigned lo = (unsigned)(act ? tl : 0) * 8u;              // this lane's node of the element (lanes past it: node 0)
-    double bm, g[6], mk, mi, di;
-    mk = ld_boff(d.mask + e * NN, lo); di = ld_boff(d.dinv + (size_t)(sc.k - 1) * d.nloc + e * NN, lo);
+    double bm, g[6], mk = 0.0, mi, di;
+    int fb = 0;                                                     // CM: the free components of the node (cm_bits: one word in place of mk)
+    if constexpr (CM) fb = *reinterpret_cast<const int*>(reinterpret_cast<const char*>(reinterpret_cast<const int*>(d.mask + 3 * d.nloc) + e * NN) + (lo >> 1));
+    else mk = ld_boff(d.mask + e * NN, lo);
+    di = ld_boff(d.dinv + (size_t)(sc.k - 1) * d.nloc + e * NN, lo);
     bm = ld_boff(d.bm1 + e * NN, lo); mi = ld_boff(d.minv + e * NN, lo);
     g[0] = ld_boff(d.g1 + e * NN, lo); g[1] = ld_boff(d.g2 + e * NN, lo); g[2] = ld_boff(d.g3 + e * NN, lo);
     g[3] = (d.zmask & (1u << 9)) ? 0.0 : ld_boff(d.g4 + e * NN, lo);        // (zmask: wave-uniform branches)
@@ -1159,7 +1195,7 @@ __global__ __launch_bounds__(Cfg<N>::NT, NSK_HELM3_WAVES) void k_helm_p(Dev d, S
           const double* wl = wl0 + (size_t)c * nl;
           const double sum = !wide ? (((gv[c].a + gv[c].b) + gv[c].c) + gv[c].d)
                                    : (from_list ? corner_list_sum(scv + c * 64 + cid * 8, wl, d, l) : gs_csr_rolled(wl, d, l));
-          const double w = mk * sum;
+          const double w = CM ? cm_sel(fb, c, sum) : mk * sum;
           const double pn = di * ro + beta[c] * po;
           const double sn = w + beta[c] * so;
           NSK_HP_ST(d.hp + lc, pn); NSK_HP_ST(d.hs + lc, sn);
@@ -2431,7 +2467,7 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_gradt(Dev d, const double* __res
 // from LDS in list order (the left-to-right sum of gs_csr; a missing member is -0.0, the identity of the addition).
 // (Until round 5 the basis was a round trip of its own ahead of the table, the metric terms went out after the gather and a
 //  corner thread walked its three components' lists one after the other: five round trips, 9 of a workgroup's 14 us.)
-template <int N>
+template <int N, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_divgs(Dev d, const double* __restrict__ yl,
                                                       double* __restrict__ wout, int j, int check_done) {
   using C = Cfg<N>;
@@ -2459,7 +2495,8 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_divgs(Dev d, const double* __res
   }
   int4 tab = make_int4(0, -1, -1, -1);
   double bi = 0.0;
-  if (act) { tab = d.gs_tab[l]; bi = d.binv[l]; }
+  int fb = 7;                                                        // CM: the free components of the node, bi unmasked
+  if (act) { tab = d.gs_tab[l]; bi = d.binv[(CM ? 3 * d.nloc : 0) + l]; if constexpr (CM) fb = cm_bits(d, l); }
   double w2[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (pact) load_w2(d, q, w2);
   // ---- round trip 2
@@ -2478,12 +2515,12 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_divgs(Dev d, const double* __res
   if (tid < NM) { bJ = d.J12[tid]; bD = d.D12[tid]; }
   if (act) {
     if (!wide) {
-      su[tid] = bi * (((g0.a + g0.b) + g0.c) + g0.d);
-      su[NN + tid] = bi * (((g1.a + g1.b) + g1.c) + g1.d);
-      su[2 * NN + tid] = bi * (((g2.a + g2.b) + g2.c) + g2.d);
+      su[tid] = (CM ? cm_sel(fb, 0, bi) : bi) * (((g0.a + g0.b) + g0.c) + g0.d);
+      su[NN + tid] = (CM ? cm_sel(fb, 1, bi) : bi) * (((g1.a + g1.b) + g1.c) + g1.d);
+      su[2 * NN + tid] = (CM ? cm_sel(fb, 2, bi) : bi) * (((g2.a + g2.b) + g2.c) + g2.d);
     } else if (!from_list) {                                  // more than four co-located nodes away from the corners: the CSR lists
 #pragma unroll 1
-      for (int c = 0; c < 3; ++c) su[c * NN + tid] = bi * gs_csr_rolled(yl + (size_t)c * d.cs, d, l);
+      for (int c = 0; c < 3; ++c) su[c * NN + tid] = (CM ? cm_sel(fb, c, bi) : bi) * gs_csr_rolled(yl + (size_t)c * d.cs, d, l);
     }
   }
 #pragma unroll
@@ -2504,7 +2541,7 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_divgs(Dev d, const double* __res
 #pragma unroll
         for (int m = 0; m < 8; ++m) sum += v[m];
       }
-      su[c * NN + tid] = bi * sum;
+      su[c * NN + tid] = (CM ? cm_sel(fb, c, bi) : bi) * sum;
     }
   }
   lds_barrier();
@@ -2527,7 +2564,7 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_divgs(Dev d, const double* __res
 
 // k_divgs with the three components' pass chains side by side (opdiv3_mfma_c3): 5 workgroup barriers after the gather instead of 12.
 // Same two round trips as k_divgs (the metrics go out first, in the accumulator order of the wavefront's last-pass tiles).
-template <int N>
+template <int N, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_divgs_c3(Dev d, const double* __restrict__ yl,
                                                          double* __restrict__ wout, int j, int check_done) {
   using C = Cfg<N>;
@@ -2548,9 +2585,11 @@ __global__ __launch_bounds__(Cfg<N>::NT) __attribute__((amdgpu_waves_per_eu(8, 8
   const int cm = (d.gs_corner && tid < 192) ? d.gs_corner[(size_t)e * 64 + (tid & 63)] : -1;
   int4 tab = make_int4(0, -1, -1, -1);
   double bi = 0.0;
-  if (act) { tab = d.gs_tab[l]; bi = d.binv[l]; }
+  int fb = 7;                                                        // CM: the free components of the node, bi unmasked
+  if constexpr (CM) { if (act) { tab = d.gs_tab[l]; bi = d.binv[3 * d.nloc + l]; fb = cm_bits(d, l); } }
+  else { if (act) { tab = d.gs_tab[l]; bi = d.binv[l]; } }
   Dv3Met<N> mt;
-  dv3_metrics<N>(d, e, tid, NT, mt);
+  dv3_metrics<N, CM>(d, e, tid, NT, mt);
   // ---- round trip 2
   const double cv = (cm >= 0) ? yl[(size_t)(tid >> 6) * d.cs + cm] : -0.0;
   const int cid = act ? corner_id<N>(tid / (N * N), (tid / N) % N, tid % N) : -1;
@@ -2562,12 +2601,12 @@ __global__ __launch_bounds__(Cfg<N>::NT) __attribute__((amdgpu_waves_per_eu(8, 8
   if (tid < NM) { bJ = d.J12[tid]; bD = d.D12[tid]; }
   if (act) {
     if (!wide) {
-      buf[W::oU + tid] = bi * (((g0.a + g0.b) + g0.c) + g0.d);
-      buf[W::BUF + W::oU + tid] = bi * (((g1.a + g1.b) + g1.c) + g1.d);
-      buf[2 * W::BUF + W::oU + tid] = bi * (((g2.a + g2.b) + g2.c) + g2.d);
+      buf[W::oU + tid] = (CM ? cm_sel(fb, 0, bi) : bi) * (((g0.a + g0.b) + g0.c) + g0.d);
+      buf[W::BUF + W::oU + tid] = (CM ? cm_sel(fb, 1, bi) : bi) * (((g1.a + g1.b) + g1.c) + g1.d);
+      buf[2 * W::BUF + W::oU + tid] = (CM ? cm_sel(fb, 2, bi) : bi) * (((g2.a + g2.b) + g2.c) + g2.d);
     } else if (!from_list) {
 #pragma unroll 1
-      for (int c = 0; c < 3; ++c) buf[c * W::BUF + W::oU + tid] = bi * gs_csr_rolled(yl + (size_t)c * d.cs, d, l);
+      for (int c = 0; c < 3; ++c) buf[c * W::BUF + W::oU + tid] = (CM ? cm_sel(fb, c, bi) : bi) * gs_csr_rolled(yl + (size_t)c * d.cs, d, l);
     }
   }
   if (tid < 192) scv[tid] = (cm == -2) ? __builtin_nan("") : cv;
@@ -2575,12 +2614,12 @@ __global__ __launch_bounds__(Cfg<N>::NT) __attribute__((amdgpu_waves_per_eu(8, 8
   lds_barrier();
   if (from_list) {
 #pragma unroll 1
-    for (int c = 0; c < 3; ++c) buf[c * W::BUF + W::oU + tid] = bi * corner_list_sum(scv + c * 64 + cid * 8, yl + (size_t)c * d.cs, d, l);
+    for (int c = 0; c < 3; ++c) buf[c * W::BUF + W::oU + tid] = (CM ? cm_sel(fb, c, bi) : bi) * corner_list_sum(scv + c * 64 + cid * 8, yl + (size_t)c * d.cs, d, l);
   }
   const bool pact = tid < MM;
   const long long q = e * MM + tid;
   lds_barrier();
-  const double w = opdiv3_mfma_c3<N>(mt, sJ12, sD12, buf, tid, NT);
+  const double w = opdiv3_mfma_c3<N, CM>(mt, sJ12, sD12, buf, tid, NT);
   if (pact) wout[q] = w;
   if (j >= 0) {
     const int lane = tid & 63, wv = tid >> 6;
@@ -2850,7 +2889,7 @@ __global__ __launch_bounds__(256) void k_proj_dots(Dev d) {
 }
 
 // velocity correction fused with E*dp for the projection space
-template <int N>
+template <int N, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_vel_update_proj(Dev d, StepCoef sc) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, NT = C::NT, NM = N * M, NNM = C::NNM, NMM = C::NMM;
@@ -2866,9 +2905,11 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_vel_update_proj(Dev d, StepCoef 
     CornerList CL;
     corner_issue(d, e, corner_id<N>(tid / (N * N), (tid / N) % N, tid % N), CL);
     const int4 tab = d.gs_tab[l];
-    const double bi = d.binv[l];
+    const double bi = d.binv[(CM ? 3 * d.nloc : 0) + l];             // (CM: unmasked, with the free components of the node)
+    const int fb = CM ? cm_bits(d, l) : 7;
     const GsVals g0 = gs_load(d.yl, tab, l), g1 = gs_load(d.yl + d.cs, tab, l), g2 = gs_load(d.yl + 2 * d.cs, tab, l);
-    const double v0 = bi * gs_sum3(g0, d.yl, d, tab, l, CL), v1 = bi * gs_sum3(g1, d.yl + d.cs, d, tab, l, CL), v2 = bi * gs_sum3(g2, d.yl + 2 * d.cs, d, tab, l, CL);
+    const double v0 = (CM ? cm_sel(fb, 0, bi) : bi) * gs_sum3(g0, d.yl, d, tab, l, CL), v1 = (CM ? cm_sel(fb, 1, bi) : bi) * gs_sum3(g1, d.yl + d.cs, d, tab, l, CL),
+                 v2 = (CM ? cm_sel(fb, 2, bi) : bi) * gs_sum3(g2, d.yl + 2 * d.cs, d, tab, l, CL);
     d.u[l] += v0 / sc.h2; d.u[d.cs + l] += v1 / sc.h2; d.u[2 * d.cs + l] += v2 / sc.h2;
     su[tid] = v0; su[NN + tid] = v1; su[2 * NN + tid] = v2;
   }

@@ -683,7 +683,10 @@ template <int N> struct Dv3Met {
   static constexpr int TPW = (DvWave<N>::NT3 + (nt_min_sub<N>()) - 1) / nt_min_sub<N>();
   double wa[TPW][DvWave<N>::RQ], wb[TPW][DvWave<N>::RQ], wc[TPW][DvWave<N>::RQ];
 };
-template <int N>
+// (FORM: one instance per calling kernel form -- k_divgs_c3<N, CM> -- so that each stays the only call site of its copy and is
+//  inlined as such: with a second caller of one shared copy the compiler's inlining changes, and with it the register
+//  allocation of the shared-mask k_divgs_c3<8> (12 -> 36 bytes of scratch))
+template <int N, bool FORM = false>
 __device__ inline void dv3_metrics(const Dev& d, long long e, int tid, int nt, Dv3Met<N>& mt) {
   using W = DvWave<N>;
   constexpr int M = N - 2, MM = M * M * M;
@@ -702,7 +705,7 @@ __device__ inline void dv3_metrics(const Dev& d, long long e, int tid, int nt, D
       mt.wc[u][r] = zc ? 0.0 : d.w2m[(size_t)(2 * 3 + comp) * d.npr + q];
     }
 }
-template <int N>
+template <int N, bool FORM = false>
 __device__ inline double opdiv3_mfma_c3(const Dv3Met<N>& mt, const double* sJ12, const double* sD12, double* buf, int tid, int nt) {
   using W = DvWave<N>;
   constexpr int M = N - 2, MM = M * M * M, KQ = (N + 3) / 4, oPart = W::B;      // partial sums: [B, B + M^3) of the region (free after the s-axis)

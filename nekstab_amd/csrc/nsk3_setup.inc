@@ -698,16 +698,36 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
     for (long long l = 0; l < nloc; ++l) { double s = 0; for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) s += f[gs_idx[k]]; o[l] = s; }
     return o;
   };
-  std::vector<double> mask(nloc), minv(nloc), binv(nloc), spng(cs.spng, cs.spng + nloc), bm1s(nloc);
+  // (component masks, nsk_init_masks: mask and binv [3][nloc], component mc from the caller's cmask[mc], cs.mask is not read; behind
+  //  them what the <.., CM = true> kernel forms load -- nsk3_kernels.hpp, cm_bits: the three masks of a node as the bits of a 32-bit
+  //  word behind mask, the unmasked 1 / B as a fourth row of binv)
+  const int nmc = c->cm ? 3 : 1;
+  if (c->cm && c->local) return fail(NSK_EINVAL, "component masks: not with a rank-local set-up");
+  std::vector<double> mask((size_t)nmc * nloc + (c->cm ? (nloc + 1) / 2 : 0)), minv(nloc), binv((size_t)(c->cm ? 4 : 1) * nloc), spng(cs.spng, cs.spng + nloc), bm1s(nloc);
   std::vector<double> bs = dssum_h(bm1);
   {
     double vol = 0;
+    int* bits = c->cm ? reinterpret_cast<int*>(mask.data() + (size_t)3 * nloc) : nullptr;
     for (long long l = 0; l < nloc; ++l) {
+      // a node fixed in any copy is fixed in all
       double mk = 1.0;
-      for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) mk = std::min(mk, cs.mask[gs_idx[k]]);
-      mask[l] = mk;
+      if (c->cm) {
+        int fb = 0;
+        for (int mc = 0; mc < 3; ++mc) {
+          double m = 1.0;
+          for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) m = std::min(m, c->cmask_in[mc][gs_idx[k]]);
+          mask[(size_t)mc * nloc + l] = m;
+          binv[(size_t)mc * nloc + l] = m / bs[l];
+          if (m != 0.0) fb |= 1 << mc;
+        }
+        bits[l] = fb;
+        binv[(size_t)3 * nloc + l] = 1.0 / bs[l];
+      } else {
+        for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) mk = std::min(mk, cs.mask[gs_idx[k]]);
+        mask[l] = mk;
+        binv[l] = mk / bs[l];
+      }
       minv[l] = 1.0 / (gs_off[l + 1] - gs_off[l]);
-      binv[l] = mk / bs[l];
       bm1s[l] = (spng[l] != 0.0) ? 0.0 : bm1[l];
       vol += bm1[l];
       if (c->local && c->local_own[l / NN]) c->vol_own += bm1[l];
@@ -772,11 +792,14 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
           }
     });
     std::vector<double> dAs = dssum_h(dA);
-    c->h_dAs = dAs; c->h_bs = bs; c->h_mask = mask;
+    c->h_dAs = dAs; c->h_bs = bs; c->h_mask.assign(mask.begin(), mask.begin() + (size_t)nmc * nloc);
     const double bd0[3] = {1.0, 1.5, 11.0 / 6.0};
-    for (int k = 0; k < 3; ++k)
-      for (long long l = 0; l < nloc; ++l) dinv[(size_t)k * nloc + l] = mask[l] / (d.nu * dAs[l] + bd0[k] / c->dt * bs[l]);
+    for (int k = 0; k < 3; ++k)      // (component masks: the unmasked diagonal, as jacobi_diagonals rebuilds it)
+      for (long long l = 0; l < nloc; ++l) dinv[(size_t)k * nloc + l] = (c->cm ? 1.0 : mask[l]) / (d.nu * dAs[l] + bd0[k] / c->dt * bs[l]);
   }
+  // (component masks: `mask` and `binv` are uploaded WHOLE -- [3][nloc] plus the packed words / the unmasked fourth row that the CM
+  //  kernel forms read, nsk3_kernels.hpp cm_bits; code that slices or copies Dev::mask / Dev::binv by [nmc][nloc] would lose that tail:
+  //  nsk_clone takes quadrilaterals only and the shards refuse such a context, see there)
   if ((rc = dupload(c, &d.g1, G[0])) || (rc = dupload(c, &d.g2, G[1])) || (rc = dupload(c, &d.g3, G[2])) ||
       (rc = dupload(c, &d.g4, G[3])) || (rc = dupload(c, &d.g5, G[4])) || (rc = dupload(c, &d.g6, G[5])) ||
       (rc = dupload(c, &d.bm1, bm1)) || (rc = dupload(c, &d.mask, mask)) || (rc = dupload(c, &d.minv, minv)) ||
@@ -850,12 +873,30 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
         const int st = (a == 0) ? 1 : (a == 1 ? N : N * N);
         const int s1 = (a == 0) ? N : 1, s2 = (a == 2) ? N : N * N;
         double L = 0.0, rlo = 0.0, rhi = 0.0; int nf = 0;
+        // component masks: the ratio of the component along the face's normal (the one D B^-1 D^T couples across the face) -- the
+        // coordinate that varies least over the face; a boundary face that fixes only some components is planar and axis-aligned,
+        // on every other face the three masks agree
+        size_t clo = 0, chi = 0;
+        if (c->cm)
+          for (int side = 0; side < 2; ++side) {
+            double best = 0.0; int comp = 0;
+            for (int x = 0; x < 3; ++x) {
+              double mn = 1e300, mx = -1e300;
+              for (int p = 0; p < N; ++p)
+                for (int q = 0; q < N; ++q) {
+                  const double v = X[x][o + (size_t)p * s1 + (size_t)q * s2 + (size_t)(side ? N - 1 : 0) * st];
+                  mn = std::min(mn, v); mx = std::max(mx, v);
+                }
+              if (x == 0 || mx - mn < best) { best = mx - mn; comp = x; }
+            }
+            (side ? chi : clo) = (size_t)comp * nloc;
+          }
         for (int p = 0; p < N; ++p)
           for (int q = 0; q < N; ++q) {
             const size_t lo = o + (size_t)p * s1 + (size_t)q * s2, hi = lo + (size_t)(N - 1) * st;
             double d2 = 0; for (int x = 0; x < 3; ++x) d2 += (X[x][hi] - X[x][lo]) * (X[x][hi] - X[x][lo]);
             L += std::sqrt(d2);
-            if (p > 0 && p < N - 1 && q > 0 && q < N - 1) { rlo += binv[lo] * bm1[lo]; rhi += binv[hi] * bm1[hi]; ++nf; }
+            if (p > 0 && p < N - 1 && q > 0 && q < N - 1) { rlo += binv[clo + lo] * bm1[lo]; rhi += binv[chi + hi] * bm1[hi]; ++nf; }
           }
         Ld[(size_t)e * 3 + a] = L / (N * N);
         rho[(size_t)e * 6 + 2 * a] = rlo / nf; rho[(size_t)e * 6 + 2 * a + 1] = rhi / nf;
@@ -942,6 +983,7 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
       // Measured (round 4): NOT a gain.  Blocks without overlap plateau at the element interfaces: 24^3 box (cell ratio 15) 26 against
       // 36 Jacobi iterations per step at 1.7x the cost per iteration (115 against 106 ms per step); config 5 at full size (ratio 29)
       // 49 against 64 iterations, 1.32 against 1.17 s per step.  Kept as an option (NSK_HELM_FDM=1 / "helm_fdm"), never chosen by itself.
+      if (c->cm && c->helm_fdm > 0) return fail(NSK_EINVAL, "helm_fdm (NSK_HELM_FDM): k_helm_fa / k_helm_fb have no component-mask form (context of nsk_init_masks)");
       const bool on = !c->local && c->helm_fdm > 0;
       if (std::getenv("NSK_DEBUG")) fprintf(stderr, "velocity solves: largest element aspect ratio %.1f -> %s\n", aspect, on ? "fast-diagonalisation blocks" : "Jacobi");
       d.helm_fdm = 0;
@@ -1113,6 +1155,12 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
   if (const char* g = std::getenv("NSK_EAPPLY_PIPE")) c->eapply_pipe = std::atoi(g);
   if (const char* g = std::getenv("NSK_DIVGS_C3")) c->divgs_c3 = std::atoi(g);
   if (const char* g = std::getenv("NSK_HELM_PF")) c->helm_pf = std::atoi(g);
+  if (c->cm) {
+    // component masks (nsk_init_masks): k_divgs_w has no such form.  Asked for through the environment: refused.
+    const char* dw = std::getenv("NSK_DIVGS_WAVE");
+    if (c->eapply_pipe == 3 || (dw && std::atoi(dw) != 0))
+      return fail(NSK_EINVAL, "NSK_EAPPLY_PIPE=3 / NSK_DIVGS_WAVE: the wavefront divergence kernel (k_divgs_w) has no component-mask form (context of nsk_init_masks)");
+  }
   if (const char* g = std::getenv("NSK_GRAPH_STEPS")) c->graph_steps = std::max(1, std::min(std::atoi(g), 64));
   if (const char* g = std::getenv("NSK_HOSTCHECK")) c->hostcheck = std::atoi(g);
   if (const char* g = std::getenv("NSK_DEBUG")) c->debug = std::atoi(g);

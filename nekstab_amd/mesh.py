@@ -351,6 +351,7 @@ def build_case_2d(mesh: nekio.Re2Mesh, vlex: np.ndarray, bf_u: np.ndarray, lx1: 
     m = dict(meta or {})
     m["vert"] = vlex - 1
     m["nvert"] = int(vlex.max())
+    m["face_codes"] = [(int(e), int(f), code) for (e, f, _prm, code) in mesh.bcs]      # (mesh3d.extrude_case: the third component's mask)
     return Case(ndim=2, nel=mesh.nel, lx1=lx1, x=x, y=y, gid=gid, nglob=nglob, mask=mask,
                 ub=ub, spng=spng, re=re, endtime=endtime, cfl=cfl, lxd=3 * lx1 // 2,
                 has_outflow=has_out, adjoint=adjoint, meta=m, cmask=cmask)
@@ -462,6 +463,9 @@ def refine_case_2x2(case: Case) -> Case:
     m = dict(case.meta)
     m["vert"] = vlex - 1
     m["nvert"] = int(vlex.max())
+    if "face_codes" in m:                  # a parent's face f belongs to the two children (qs, qr) on that side: child 4 e + 2 qs + qr
+        kids = {0: (0, 1), 1: (1, 3), 2: (2, 3), 3: (0, 2)}
+        m["face_codes"] = [(4 * e + k, f, code) for (e, f, code) in m["face_codes"] for k in kids[f]]
     return Case(ndim=2, nel=4 * nel, lx1=n, x=x, y=y, gid=gid, nglob=nglob, mask=mask, ub=ub, spng=spng,
                 re=case.re, endtime=case.endtime, cfl=case.cfl, lxd=case.lxd, has_outflow=case.has_outflow,
                 adjoint=case.adjoint, meta=m, cmask=cmask)
