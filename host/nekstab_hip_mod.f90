@@ -312,6 +312,17 @@ module nekstab_hip
       type(c_ptr), value :: q
       type(c_ptr), value :: w
     end function
+    ! vortex_core('lambda2' / 'q' / 'omega') of nekStab_outpost's vox and omg files (core/usr_extra.f:269-281): w = (lambda2, Q
+    ! [, Omega]), omega (c_null_ptr or a vector) = (Omega, 0 ...), each filtered as filter_s0 with weight wght (0: no filter);
+    ! q is read only; q, w, omega distinct
+    integer(c_int) function nsk_vortex_criteria(ctx, q, wght, w, omega) bind(c, name='nsk_vortex_criteria')
+      import
+      type(c_ptr), value :: ctx
+      type(c_ptr), value :: q
+      real(c_double), value :: wght
+      type(c_ptr), value :: w
+      type(c_ptr), value :: omega
+    end function
     ! SFD (core/fixedp.f:114-242, uparam(1) = 1.1): f = nsteps steps of the full equations from q under -chi (v - qbar); qbar
     ! enters as the filter state at call 0 (a copy of q: the reference's run) and leaves as the one behind the last step.
     ! residu: c_null_ptr or c_loc of nsteps doubles (residu of every step).  f, q, qbar: three distinct vectors
@@ -546,6 +557,16 @@ module nekstab_hip
       type(c_ptr), dimension(*) :: shards
       integer(c_int), value :: n
       type(c_ptr), dimension(*) :: q, w
+    end function
+    ! omega: c_null_ptr or c_loc of an array of n handles
+    integer(c_int) function nsk_group_vortex_criteria(shards, n, q, wght, w, omega) bind(c, name='nsk_group_vortex_criteria')
+      import
+      type(c_ptr), dimension(*) :: shards
+      integer(c_int), value :: n
+      type(c_ptr), dimension(*) :: q
+      real(c_double), value :: wght
+      type(c_ptr), dimension(*) :: w
+      type(c_ptr), value :: omega
     end function
     integer(c_int) function nsk_group_sfd_map(shards, n, f, q, qbar, chi, omega_c, residu) bind(c, name='nsk_group_sfd_map')
       import

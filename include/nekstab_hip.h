@@ -271,6 +271,25 @@ int nsk_energy_budget(nsk_ctx* ctx, nsk_vec ub, nsk_vec dRe, nsk_vec dIm, nsk_ve
  * The assembled unmasked mass (one double per velocity node) is built at a context's first call and kept until nsk_finalize;
  * nothing else is allocated, no captured step graph or launch budget is touched. */
 int nsk_vorticity(nsk_ctx* ctx, nsk_vec q, nsk_vec w);
+/* vortex_core('lambda2'), ('q') and ('omega') as nekStab_outpost calls them for the vox and omg files (core/usr_extra.f:256-281)
+ * on q's velocity.  With g[i][j] = d u_i / d x_j at the GLL nodes, element-local and unaveraged (comp_gije; metrics derived from
+ * the element's own coordinates), S = (g + g^T) / 2, O = (g - g^T) / 2, ndim x ndim (2 x 2 on quadrilaterals):
+ *   lambda2  the second largest eigenvalue of S S + O O (Jeong & Hussain): the middle of three, the smaller of two; cyclic Jacobi
+ *            sweeps, accurate where eigenvalues coincide (a z-invariant divergence-free field: at every node)
+ *   Q        compute_q -> compute_secondInv (core/postproc.f:374-403): 3-D the sum of the three principal 2 x 2 minors of g;
+ *            2-D (g11 + g22)^2 - 2 g12 g21 - g11^2 - g22^2 = 2 det g, the reference's form: twice the 3-D value of the same
+ *            field made z-invariant
+ *   Omega    compute_omega_jc (core/postproc.f:31-79): b / (a + b + 1e-5), a = (||S||_F^2)^2, b = (||O||_F^2)^2 (1e-5 unscaled)
+ * each then filtered as filter_s0(f, wght, 1, .) does (the reference: wght = 0.5), element by element along the reference
+ * directions with F = Phi diag(1, ..., 1, 1 - wght) Phi^-1, Phi[j][k] = phi_k(xi_j), phi_0 = L_0, phi_1 = L_1,
+ * phi_k = L_k - L_{k-2}: polynomials of degree <= lx1 - 2 stay, phi_{lx1-1} is multiplied by 1 - wght.  wght = 0: no filter, the
+ * criteria bit for bit.  wght outside [0, 1] or not finite: NSK_EINVAL.
+ * Layout: w gets vx = lambda2, vy = Q and in 3-D vz = Omega; omega (NULL or a vector) gets Omega in vx -- the omg file, and the
+ * only way to Omega in 2-D.  Pressure, scalar and unused velocity slots of both are 0.  q is read only; w == q, omega == q,
+ * omega == w, a NULL q or w: NSK_EINVAL.  Contexts of nsk_init_masks are accepted (no mask is read).  One launch, no gather, no
+ * atomics: two calls give the same bits.  F (lx1^2 doubles, built on the host for the weight of the call and kept until the
+ * weight changes or nsk_finalize) is the only allocation; no captured step graph, launch budget or option is touched. */
+int nsk_vortex_criteria(nsk_ctx* ctx, nsk_vec q, double wght, nsk_vec w, nsk_vec omega);
 /* Selective frequency damping (SFD, core/fixedp.f:114-242, uparam(1) = 1.1): f = v^nsteps, the state after nsteps steps of the
  * FULL equations from v^0 = q under the force -chi (v - qbar), qbar a low-pass-filtered copy of the velocity.  nsteps, dt and
  * the base state of the CFL rule are nsk_nonlinear_map's (nsk_set_baseflow / nsk_set_nsteps).  The reference calls SFD after
@@ -437,7 +456,7 @@ int nsk_group_set_orbit_fourier(nsk_ctx** shards, int n, nsk_vec* q0, double spn
 int nsk_group_set_orbit_modes(nsk_ctx** shards, int n, int nmodes, double period, const nsk_vec* A, const nsk_vec* B);
 int nsk_group_get_orbit_modes(nsk_ctx** shards, int n, int* nmodes, double* period, nsk_vec* A, nsk_vec* B);
 /* Eigenmode post-processing on shards (uparam(1) = 4.0 / 4.1 / 4.2 / 4.3 / 4.41 / 4.42 under the element decomposition): the
- * twins of nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity, nsk_energy_budget, nsk_forced_map and nsk_vorticity for the ranks living in
+ * twins of nsk_biorthogonalize, nsk_wavemaker, nsk_bf_sensitivity, nsk_energy_budget, nsk_forced_map, nsk_vorticity and nsk_vortex_criteria for the ranks living in
  * this process -- same argument checks, NULL rules and outputs, every vector argument an array of n handles (rank r's at [r];
  * n = 1 with a transport attached: one process per GPU).  Shards of full-mesh and of rank-local parents alike, before and after
  * nsk_shard_release_parent (every shard keeps the GLL coordinates of its own elements); other contexts: NSK_EINVAL ("needs
@@ -455,13 +474,17 @@ int nsk_group_get_orbit_modes(nsk_ctx** shards, int n, int* nmodes, double* peri
  *   nsk_group_vorticity: q and w hold n handles each (a NULL entry, or w[r] == q[r]: NSK_EINVAL); ONE halo exchange per call
  *   carrying every curl component (1 in 2-D, 3 in 3-D) in one message per peer.  The divisor is the mass assembled over ALL
  *   ranks: the first call of a group builds it with one further exchange of one component, every shard keeps it (one double per
- *   velocity node) until it is finalised. */
+ *   velocity node) until it is finalised.
+ *   nsk_group_vortex_criteria: q, w and (when not NULL) omega hold n handles each; the refusals of nsk_vortex_criteria, per
+ *   rank.  The criteria and their filter are element-local (comp_gije, pointwise, filter_s0): NO exchange happens, every rank
+ *   computes its own elements; the component stride of the outputs is the shard's own nloc. */
 int nsk_group_biorthogonalize(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, double* gamma_delta);
 int nsk_group_wavemaker(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* wm);
 int nsk_group_bf_sensitivity(nsk_ctx** shards, int n, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* aRe, nsk_vec* aIm, nsk_vec* sr, nsk_vec* si, nsk_vec* parts);
 int nsk_group_energy_budget(nsk_ctx** shards, int n, nsk_vec* ub, nsk_vec* dRe, nsk_vec* dIm, nsk_vec* prod, nsk_vec* diss, double* integrals);
 int nsk_group_forced_map(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec* q, nsk_vec* force);
 int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w);
+int nsk_group_vortex_criteria(nsk_ctx** shards, int n, nsk_vec* q, double wght, nsk_vec* w, nsk_vec* omega);
 /* nsk_sfd_map on the ranks of this process: f, q, qbar hold n handles each, every rank filters and forces its own elements (no
  * halo exchange beyond the steps' own).  residu (NULL or nsteps doubles) holds the sums over ALL ranks -- per rank on the device
  * in a fixed order, the ranks added in rank order (virtual ranks) or by the transport's all-reduce behind the map: every rank

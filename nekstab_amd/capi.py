@@ -111,6 +111,7 @@ SYMBOLS = {
     "nsk_group_energy_budget": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, _vpp, _vpp, _dp]),
     "nsk_group_forced_map": (C.c_int, [_vpp, C.c_int, C.c_int, _vpp, _vpp, _vpp]),
     "nsk_group_vorticity": (C.c_int, [_vpp, C.c_int, _vpp, _vpp]),
+    "nsk_group_vortex_criteria": (C.c_int, [_vpp, C.c_int, _vpp, C.c_double, _vpp, _vpp]),
     "nsk_group_sfd_map": (C.c_int, [_vpp, C.c_int, _vpp, _vpp, _vpp, C.c_double, C.c_double, _dp]),
     "nsk_group_boostconv_init": (C.c_int, [_vpp, C.c_int, C.c_int]),
     "nsk_group_boostconv_core": (C.c_int, [_vpp, C.c_int, _vpp]),
@@ -130,6 +131,7 @@ SYMBOLS = {
     "nsk_forced_map": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
     "nsk_energy_budget": (C.c_int, [_vp, _vp, _vp, _vp, _vpp, _vp, _dp]),
     "nsk_vorticity": (C.c_int, [_vp, _vp, _vp]),
+    "nsk_vortex_criteria": (C.c_int, [_vp, _vp, C.c_double, _vp, _vp]),
     "nsk_sfd_map": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_double, _dp]),
     "nsk_boostconv_init": (C.c_int, [_vp, C.c_int]),
     "nsk_boostconv_core": (C.c_int, [_vp, _vp]),
@@ -463,6 +465,12 @@ class NekStabHip:
         """w = vorticity of q's velocity (nsk_vorticity; comp_vort3 of the reference's Rv files): mass-weighted average over
         shared nodes, no Dirichlet mask.  2-D: (omega, 0); 3-D: the curl; pressure and scalar slots of w are 0.  q is read only."""
         self._chk(self.lib.nsk_vorticity(self.ctx, q, w))
+
+    def vortex_criteria(self, w, q, wght=0.5, omega=None):
+        """Vortex identification of q's velocity (nsk_vortex_criteria; vortex_core of the reference's vox / omg files): w gets
+        vx = lambda2, vy = Q and in 3-D vz = Omega, ``omega`` (optional) gets Omega in vx; each filtered with filter_s0's weight
+        ``wght`` (0: no filter).  Every other slot of the outputs is 0.  q is read only."""
+        self._chk(self.lib.nsk_vortex_criteria(self.ctx, q, float(wght), w, omega))
 
     def sfd_map(self, f, q, qbar, chi, omega_c):
         """f = the state after ``nsteps`` steps of the full equations from q under selective frequency damping (nsk_sfd_map):

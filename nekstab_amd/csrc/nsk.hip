@@ -263,6 +263,8 @@ struct nsk_ctx {
   const double* force = nullptr;        // steady body force [ndim][nloc] of the running forced map (nsk_forced_map; eager steps only), else null
   double* budget_wrk = nullptr;         // nsk_energy_budget: divergence field [nloc; shards: cs], per-workgroup partials, 10 sums (first call; freed with the context)
   double* vort_mass = nullptr;          // nsk_vorticity: the assembled, unmasked mass [nloc] (first call; freed with the context)
+  double* vox_filt = nullptr;           // nsk_vortex_criteria: the filter matrix of filter_s0 [lx1][lx1] for weight vox_wght (first call with wght != 0; freed with the context)
+  double vox_wght = 0.0;
   // ---- selective frequency damping (nsk_sfd_map / nsk_group_sfd_map; nsk_sfd.hpp).  sfd_state: vxo and the two lags the next
   // call reads, [3][ndim][nloc]; sfd_part: per-workgroup residual sums; sfd_hist: sum bm1 |v^{j-1} - v^j|^2 of steps 1..nsteps
   // (first call; freed with the context).  `sfd` is set while such a map runs (eager steps only), else off.
@@ -4107,6 +4109,55 @@ int nsk_group_vorticity(nsk_ctx** shards, int n, nsk_vec* q, nsk_vec* w) {
   if (rc) return rc;
   std::vector<nsk_ctx*> G(shards, shards + n);
   return sens_vorticity(G, "nsk_group_vorticity", q, w);
+}
+
+// vortex_core('lambda2' / 'q' / 'omega') of nekStab_outpost (core/usr_extra.f:269-281; core/postproc.f:31-79, 374-403): ONE launch
+// of k_vortex per rank, element-local -- no exchange.  The filter matrix (lx1^2 doubles, built on the host in double precision
+// for the weight of the call and kept while the weight stays) is the only allocation; wght = 0 passes no matrix.
+static int sens_vortex(std::vector<nsk_ctx*>& G, const char* who, nsk_vec* q, double wght, nsk_vec* w, nsk_vec* omega) {
+  const int n = (int)G.size();
+  int rc;
+  if (!q || !w) return sfail(who, "bad argument");
+  if (!(std::isfinite(wght) && wght >= 0.0 && wght <= 1.0)) return sfail(who, "the filter weight must lie in [0, 1]");
+  for (int r = 0; r < n; ++r) {
+    if (!q[r] || !w[r] || (omega && !omega[r])) return sfail(who, "bad argument (q, w and omega need one vector per rank)");
+    if (q[r] == w[r] || (omega && (omega[r] == q[r] || omega[r] == w[r]))) return sfail(who, "q, w and omega must be distinct vectors");
+    if (!G[r]->xyz) return sfail(who, "context holds no coordinates");
+  }
+  if (sens_key_ok(G[0]->key)) return sfail(who, "unsupported lx1");
+  for (nsk_ctx* c : G) {
+    if (wght == 0.0 || (c->vox_filt && c->vox_wght == wght)) continue;
+    std::vector<double> z, wq;
+    zwgll(c->N, z, wq);
+    const std::vector<double> F = filter_matrix(z, wght);
+    if (!c->vox_filt && (rc = dalloc(c, &c->vox_filt, F.size()))) return rc;
+    HIPCHK(hipMemcpy(c->vox_filt, F.data(), F.size() * sizeof(double), hipMemcpyHostToDevice));   // (every call ends synchronised: no reader in flight)
+    c->vox_wght = wght;
+  }
+  for (int r = 0; r < n; ++r) {
+    nsk_ctx* c = G[r];
+    const long long nv = (long long)c->ndim * c->nloc;
+    double* o = omega ? (double*)omega[r] : nullptr;
+    HIPCHK(hipMemsetAsync((double*)w[r] + nv, 0, (c->nstate - nv) * sizeof(double), c->stream));
+    if (o) HIPCHK(hipMemsetAsync(o + c->nloc, 0, (c->nstate - c->nloc) * sizeof(double), c->stream));
+    DISPATCH_SENS(c->key, { nsk::sens::launch_vortex<N, NDIM>(c->stream, c->nel, c->d.D, c->xyz, (const double*)q[r],
+                                                              wght == 0.0 ? nullptr : (const double*)c->vox_filt, (double*)w[r], o, c->nloc); });
+  }
+  HIPCHK(hipGetLastError());
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+int nsk_vortex_criteria(nsk_ctx* c, nsk_vec q, double wght, nsk_vec w, nsk_vec omega) {
+  int rc = sens_ctx_ok(c, "nsk_vortex_criteria");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(1, c);
+  return sens_vortex(G, "nsk_vortex_criteria", &q, wght, &w, omega ? &omega : nullptr);
+}
+int nsk_group_vortex_criteria(nsk_ctx** shards, int n, nsk_vec* q, double wght, nsk_vec* w, nsk_vec* omega) {
+  int rc = sens_group_ok(shards, n, "nsk_group_vortex_criteria");
+  if (rc) return rc;
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  return sens_vortex(G, "nsk_group_vortex_criteria", q, wght, w, omega);
 }
 
 int nsk_forced_map(nsk_ctx* c, int mode, nsk_vec fv, nsk_vec qv, nsk_vec force) {

@@ -4,6 +4,7 @@
 // dgll, igllm] -- restated from the published formulas, not from Nek source.
 #pragma once
 #include <cmath>
+#include <utility>
 #include <vector>
 
 namespace nsk {
@@ -104,6 +105,43 @@ inline std::vector<double> deriv_matrix(const std::vector<double>& x) {
     D[(size_t)i * n + i] = -s;
   }
   return D;
+}
+
+// The 1-D matrix of Nek5000's filter_s0(f, wght, 1, .) on the n GLL points z, row-major: F = Phi diag(1, ..., 1, 1 - wght) Phi^-1,
+// Phi[j][k] = phi_k(z_j), phi_0 = L_0, phi_1 = L_1, phi_k = L_k - L_{k-2} (L: Legendre).  Built in its rank-one form
+// F = I - wght phi_{n-1} y^T, y^T the last row of Phi^-1 (Phi^T y = e_{n-1}, Gaussian elimination with partial pivoting).
+inline std::vector<double> filter_matrix(const std::vector<double>& z, double wght) {
+  const int n = (int)z.size();
+  std::vector<double> phi((size_t)n * n), M((size_t)n * n), y(n, 0.0), F((size_t)n * n, 0.0);
+  for (int j = 0; j < n; ++j) {
+    std::vector<double> L(n);
+    for (int k = 0; k < n; ++k) L[k] = k == 0 ? 1.0 : k == 1 ? z[j] : ((2 * k - 1) * z[j] * L[k - 1] - (k - 1) * L[k - 2]) / k;
+    for (int k = 0; k < n; ++k) phi[(size_t)j * n + k] = k < 2 ? L[k] : L[k] - L[k - 2];
+  }
+  for (int j = 0; j < n; ++j)
+    for (int k = 0; k < n; ++k) M[(size_t)k * n + j] = phi[(size_t)j * n + k];   // M = Phi^T
+  y[n - 1] = 1.0;
+  for (int c = 0; c < n; ++c) {
+    int piv = c;
+    for (int r = c + 1; r < n; ++r) if (std::fabs(M[(size_t)r * n + c]) > std::fabs(M[(size_t)piv * n + c])) piv = r;
+    if (piv != c) {
+      for (int k = 0; k < n; ++k) std::swap(M[(size_t)c * n + k], M[(size_t)piv * n + k]);
+      std::swap(y[c], y[piv]);
+    }
+    for (int r = c + 1; r < n; ++r) {
+      const double f = M[(size_t)r * n + c] / M[(size_t)c * n + c];
+      for (int k = c; k < n; ++k) M[(size_t)r * n + k] -= f * M[(size_t)c * n + k];
+      y[r] -= f * y[c];
+    }
+  }
+  for (int r = n - 1; r >= 0; --r) {
+    double s = y[r];
+    for (int k = r + 1; k < n; ++k) s -= M[(size_t)r * n + k] * y[k];
+    y[r] = s / M[(size_t)r * n + r];
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) F[(size_t)i * n + j] = (i == j ? 1.0 : 0.0) - wght * phi[(size_t)i * n + n - 1] * y[j];
+  return F;
 }
 
 inline std::vector<double> matmul(const std::vector<double>& A, const std::vector<double>& B, int m, int k, int n) {

@@ -1,6 +1,7 @@
 // Sensitivity post-processing on the device (core/sensitivity.f): wavemaker, base-flow sensitivity, biorthogonalisation,
 // the steady body force of the forced linearised maps (core/utils.f:160-162), and the stability energy budget
-// (core/postproc.f:657-872, at the end of this file).
+// (core/postproc.f:657-872), followed by the vorticity of the Rv files (comp_vort3) and, at the end of this file, the
+// vortex-identification criteria of the vox / omg files (vortex_core: lambda2, Q, Omega; core/postproc.f:2-79, 374-403).
 //
 // The base-flow sensitivity is linear in each mode's gradient times the other modes' values, so it is built one mode
 // COMPONENT at a time: k_sens_grad writes the element-local physical gradient of that component (ndim fields, gradm1 with
@@ -412,6 +413,166 @@ __global__ void k_vort_avg(const Dev d, const double* __restrict__ g, long long 
     for (int c = 0; c < NC; ++c) w[c * d.nloc + l] = gs_gather(g + c * gs, d, l) / mi;
   }
   if (l >= NC * d.nloc) w[l] = 0.0;
+}
+
+// ---- vortex_core('lambda2' / 'q' / 'omega') of nekStab_outpost (the vox and omg files, core/usr_extra.f:269-281) -------------
+// With g[i][j] = d u_i / d x_j at the element-local node (comp_gije: no averaging), S = (g + g^T) / 2, O = (g - g^T) / 2,
+// ndim x ndim (2 x 2 on quadrilaterals):
+//   lambda2  the second largest eigenvalue of A = S S + O O (Jeong & Hussain): the middle of three, the smaller of two
+//   Q        compute_secondInv (core/postproc.f:374-403): 3-D the sum of the three principal 2 x 2 minors of g; 2-D the
+//            reference's (g11 + g22)^2 - 2 g12 g21 - g11^2 - g22^2 = 2 det g, which is TWICE the 3-D expression of a z-invariant
+//            field (its minors with the third direction vanish and one det g is left) -- kept as the reference has it
+//   Omega    compute_omega_jc (core/postproc.f:31-79): b / (a + b + 1e-5), a = (||S||_F^2)^2, b = (||O||_F^2)^2; the constant
+//            is the reference's and is not scaled
+// each then filtered as filter_s0(f, wght, 1, .) does: f <- (F x F [x F]) f along the reference directions of the element.
+// Everything is element-local and pointwise: no gather, no exchange on shards, no atomics, one order of operations.
+//
+// Eigenvalues: cyclic Jacobi sweeps on the six (three) entries of A in registers, eigenvalues only.  The closed-form
+// trigonometric root formula loses half its digits where two eigenvalues meet -- and for a z-invariant, divergence-free field
+// A = diag(c, c, 0) at EVERY node; a Jacobi rotation is an orthogonal similarity whatever the gaps are, so the diagonal it
+// leaves is within a few ulp of ||A|| of the eigenvalues, degenerate or not.  A 2 x 2 matrix is diagonal after one rotation.
+// For 3 x 3, JACOBI_SWEEPS = 5: over 4e5 random matrices S S + O O the largest off-diagonal norm after sweeps 1 .. 4 is
+// 5e-1, 7e-2, 2e-5, 6e-21 of ||A|| (the convergence is quadratic and better), nearly degenerate ones are there after two; the
+// fifth sweep is margin, and a rotation whose pivot is already 0 changes nothing.
+constexpr int JACOBI_SWEEPS = 5;
+
+// one rotation in the (p, q) plane of a symmetric matrix, annihilating apq; arp, arq: the entries coupling p and q to the third
+// index (2 x 2: pass two dummies).  t = tan of the smaller angle (|t| <= 1); apq = 0, or so small that theta^2 overflows: t = 0.
+__device__ inline void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq) {
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double t = apq == 0.0 ? 0.0 : copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app -= t * apq;
+  aqq += t * apq;
+  apq = 0.0;
+  const double p = arp, q = arq;
+  arp = c * p - s * q;
+  arq = s * p + c * q;
+}
+
+// (lambda2, Q, Omega) of the velocity gradient g[i][j] = d u_i / d x_j at one node
+template <int NDIM>
+__device__ inline void vortex_point(const double (&g)[NDIM][NDIM], double (&v)[3]) {
+  double S[NDIM][NDIM], O[NDIM][NDIM];
+  double ns = 0.0, no = 0.0;
+#pragma unroll
+  for (int i = 0; i < NDIM; ++i)
+#pragma unroll
+    for (int j = 0; j < NDIM; ++j) {
+      S[i][j] = 0.5 * (g[i][j] + g[j][i]);
+      O[i][j] = 0.5 * (g[i][j] - g[j][i]);
+      ns += S[i][j] * S[i][j];
+      no += O[i][j] * O[i][j];
+    }
+  double A[NDIM][NDIM];                                          // the upper triangle is used
+#pragma unroll
+  for (int i = 0; i < NDIM; ++i)
+#pragma unroll
+    for (int j = i; j < NDIM; ++j) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < NDIM; ++k) s += S[i][k] * S[k][j] + O[i][k] * O[k][j];
+      A[i][j] = s;
+    }
+  if constexpr (NDIM == 2) {
+    double d0 = 0.0, d1 = 0.0;
+    jacobi_rotate(A[0][0], A[1][1], A[0][1], d0, d1);
+    v[0] = fmin(A[0][0], A[1][1]);
+    v[1] = (g[0][0] + g[1][1]) * (g[0][0] + g[1][1]) - 2.0 * g[0][1] * g[1][0] - g[0][0] * g[0][0] - g[1][1] * g[1][1];
+  } else {
+#pragma unroll
+    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+      jacobi_rotate(A[0][0], A[1][1], A[0][1], A[0][2], A[1][2]);
+      jacobi_rotate(A[0][0], A[2][2], A[0][2], A[0][1], A[1][2]);
+      jacobi_rotate(A[1][1], A[2][2], A[1][2], A[0][1], A[0][2]);
+    }
+    const double lo = fmin(A[0][0], A[1][1]), hi = fmax(A[0][0], A[1][1]);
+    v[0] = fmax(lo, fmin(hi, A[2][2]));                           // the middle of three
+    v[1] = (g[1][1] * g[2][2] - g[1][2] * g[2][1]) + (g[0][0] * g[1][1] - g[0][1] * g[1][0]) + (g[2][2] * g[0][0] - g[0][2] * g[2][0]);
+  }
+  const double a = ns * ns, b = no * no;
+  v[2] = b / (a + b + 1.0e-5);
+}
+
+// w: lambda2 and Q in the first two velocity components and, in 3-D, Omega in the third (component stride nloc); om (may be
+// null): Omega in its first component.  F: null (no filter: the criteria leave as they were computed) or the lx1 x lx1 filter
+// matrix, row-major.  One workgroup per element; D, the ndim velocity components and the ndim coordinates in LDS, the gradient
+// in registers as in k_vort; the three filtered fields then pass through the first three of those LDS buffers, which are free
+// once every thread holds its gradient: one tensor-product pass per direction for all three fields, each thread keeping its
+// results in registers across the barrier that ends the reads of the pass.
+template <int N, int NDIM>
+__global__ void __launch_bounds__((SensCfg<N, NDIM>::NT)) k_vortex(const double* __restrict__ D, const double* __restrict__ xyz,
+                                                                 const double* __restrict__ u, const double* __restrict__ F,
+                                                                 double* __restrict__ w, double* __restrict__ om, long long nloc) {
+  constexpr int NP = SensCfg<N, NDIM>::NP;
+  __shared__ double sD[N * N], sF[N * N];
+  __shared__ double sb[2 * NDIM][NP];                            // [0, NDIM): velocity, then x, y [, z]; the filter: [0, 3)
+  static_assert(2 * NDIM >= 3, "three buffers for the filter passes");
+  const int tid = threadIdx.x;
+  const long long e0 = (long long)blockIdx.x * NP, l = e0 + tid;
+  const bool act = tid < NP;
+  elem_load_geom<N, NDIM>(D, xyz, e0, nloc, tid, sD, sb[NDIM], sb[NDIM + 1], sb[2 * NDIM - 1]);
+  if (F && tid < N * N) sF[tid] = F[tid];
+  if (act) {
+#pragma unroll
+    for (int c = 0; c < NDIM; ++c) sb[c][tid] = u[c * nloc + l];
+  }
+  __syncthreads();
+  double v[3] = {0.0, 0.0, 0.0};
+  if (act) {
+    double m[NDIM][NDIM];
+    elem_inv_metric<N, NDIM>(sD, sb[NDIM], sb[NDIM + 1], sb[2 * NDIM - 1], tid, m);
+    double g[NDIM][NDIM];                                        // g[c][a] = d u_c / d x_a
+#pragma unroll
+    for (int c = 0; c < NDIM; ++c) {
+      double fd[NDIM];
+      elem_ref_deriv<N, NDIM>(sD, sb[c], tid, fd);
+#pragma unroll
+      for (int a = 0; a < NDIM; ++a) {
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < NDIM; ++q) s += m[q][a] * fd[q];
+        g[c][a] = s;
+      }
+    }
+    vortex_point<NDIM>(g, v);
+  }
+  if (F) {                                                       // (the same for every thread of the grid)
+    const int i = tid % N, j = (tid / N) % N, k = NDIM == 3 ? tid / (N * N) : 0;
+    // lines through this node: over i (stride 1), over j (stride N), over k (stride N * N)
+    const int base[3] = {tid - i, NDIM == 3 ? k * N * N + i : i, j * N + i};
+    const int stride[3] = {1, N, N * N};
+    const int row[3] = {i, j, k};
+#pragma unroll
+    for (int dir = 0; dir < NDIM; ++dir) {
+      __syncthreads();                                           // the reads of the gradients / of the last pass are over
+      if (act) {
+#pragma unroll
+        for (int f = 0; f < 3; ++f) sb[f][tid] = v[f];
+      }
+      __syncthreads();
+      if (act) {
+#pragma unroll
+        for (int f = 0; f < 3; ++f) {
+          double t = 0.0;
+#pragma unroll
+          for (int q = 0; q < N; ++q) t += sF[row[dir] * N + q] * sb[f][base[dir] + q * stride[dir]];
+          v[f] = t;
+        }
+      }
+    }
+  }
+  if (!act) return;
+  w[l] = v[0];
+  w[nloc + l] = v[1];
+  if constexpr (NDIM == 3) w[2 * nloc + l] = v[2];
+  if (om) om[l] = v[2];
+}
+
+template <int N, int NDIM>
+inline void launch_vortex(hipStream_t st, int nel, const double* D, const double* xyz, const double* u, const double* F, double* w,
+                          double* om, long long nloc) {
+  hipLaunchKernelGGL((k_vortex<N, NDIM>), dim3(nel), dim3(SensCfg<N, NDIM>::NT), 0, st, D, xyz, u, F, w, om, nloc);
 }
 
 }  // namespace sens

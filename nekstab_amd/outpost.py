@@ -7,6 +7,8 @@ them unchanged.
   Spectre_NS<op>_conv.dat  (2E15.7)  converged & outposted <= maxmodes   :601-604
   <op>Re<session>0.f0000i / <op>Im...  eigenmode i = Q y_i, |Re|^2+|Im|^2 = 1 (bm1s), time = i  :607-642
   <op>Rv<session>0.f0000i  vorticity of the real part of eigenmode i (comp_vort3; ``ifvor=True``)   :629-637
+  <op>Rx<session>0.f0000i  lambda2, Q [, Omega] of the real part of eigenmode i (``ifvox=True``; 2-D: <op>Ro..., Omega as temperature)
+  vox / omg<session>0.f0000n  ``outpost_vox``: the vortex-identification files of nekStab_outpost (core/usr_extra.f:269-281)
   Spectre_<op>.info        key=value manifest of the run (mesh, uparam, solver, eigensolver)   :664-717
 """
 from __future__ import annotations
@@ -70,12 +72,38 @@ def read_info(path):
     return out
 
 
+def outpost_vox(be, q, case, outdir, *, session, num=1, wght=0.5, prefix="vox", prefix_omg="omg", time=0.0, istep=0, wdsize=4):
+    """The vortex-identification files of nekStab_outpost with ``ifvox = .true.`` (core/usr_extra.f:269-281) for the velocity of
+    the device vector ``q`` (a context or a ``ShardGroup`` as ``be``; ``be.vortex_criteria``):
+      vox<session>0.f0000n   lambda2, Q [, Omega] in the velocity slots, no pressure and no temperature (read code XU)
+      omg<session>0.f0000n   2-D only: Omega as the temperature field, no velocity (read code XT)
+    ``wght``: the weight of filter_s0 (the reference's 0.5; 0: unfiltered).  Returns the paths written."""
+    os.makedirs(outdir, exist_ok=True)
+    nd = int(getattr(case, "ndim", 2))
+    w, om = be.alloc(2)
+    try:
+        be.vortex_criteria(w, q, wght, omega=om if nd == 2 else None)
+        x, u, _ = state_to_fields(be, case, w)
+        out = [os.path.join(outdir, "%s%s0.f%05d" % (prefix, session, num))]
+        nekio.write_fld(out[0], x=x, u=u, time=time, istep=istep, wdsize=wdsize)
+        if nd == 2:
+            _, uo, _ = state_to_fields(be, case, om)
+            out.append(os.path.join(outdir, "%s%s0.f%05d" % (prefix_omg, session, num)))
+            nekio.write_fld(out[1], x=x, t=uo[0], time=time, istep=istep, wdsize=wdsize)
+    finally:
+        be.free([w, om])
+    return out
+
+
 def outpost_ks(be, res, case, outdir, *, evop="d", sampling_period=1.0, eigen_tol=1e-6, maxmodes=20,
                session="1cyl", wdsize=4, schur_tgt=0, schur_del=0.10, uparam=None, tol_pres=None, tol_vel=None, nranks=1,
-               ifvor=False):
+               ifvor=False, ifvox=False):
     """``ifvor``: also write, for every converged mode, ``<evop>Rv<session>0.f0000i`` = the vorticity of its real part
     (comp_vort3 + outpost(vort, 'Rv') with ifpo = ifto = .false., core/eigensolvers.f:629-637: read code XU, time / istep / wdsize
-    of the Re file), computed on the device (``be.vorticity``).  Returns the Re / Im paths, then the Rv paths."""
+    of the Re file), computed on the device (``be.vorticity``).
+    ``ifvox``: also write ``<evop>Rx<session>0.f0000i`` = the vox file of its real part (lambda2, Q [, Omega]; ``outpost_vox``)
+    and, in 2-D, ``<evop>Ro<session>0.f0000i`` = its omg file (Omega as temperature), with the header of the Re file.
+    Returns the Re / Im paths, then the Rv paths, then the Rx (and Ro) paths."""
     os.makedirs(outdir, exist_ok=True)
     k = res.H.shape[1]
     lam = log_transform(res.vals, sampling_period)
@@ -84,7 +112,7 @@ def outpost_ks(be, res, case, outdir, *, evop="d", sampling_period=1.0, eigen_to
     conv = []
     re, im = be.alloc(2)
     vor = be.alloc(1) if ifvor else []
-    written, written_rv = [], []
+    written, written_rv, written_rx = [], [], []
     for i in range(k):
         if res.residual[i] < eigen_tol and len(conv) < maxmodes:
             conv.append(lam[i])
@@ -101,9 +129,12 @@ def outpost_ks(be, res, case, outdir, *, evop="d", sampling_period=1.0, eigen_to
                 f = os.path.join(outdir, "%sRv%s0.f%05d" % (evop, session, idx))
                 nekio.write_fld(f, x=x, u=u, time=float(i + 1), istep=be.nsteps + 1, wdsize=wdsize)
                 written_rv.append(f)
+            if ifvox:
+                written_rx += outpost_vox(be, re, case, outdir, session=session, num=idx, prefix=evop + "Rx",
+                                          prefix_omg=evop + "Ro", time=float(i + 1), istep=be.nsteps + 1, wdsize=wdsize)
     nekio.write_spectre(os.path.join(outdir, f"Spectre_NS{evop}_conv.dat"), np.array(conv))
     write_info(os.path.join(outdir, f"Spectre_{evop}.info"), be, case, res, evop=evop, sampling_period=sampling_period,
                eigen_tol=eigen_tol, schur_tgt=schur_tgt, schur_del=schur_del, outposted=len(conv), uparam=uparam,
                tol_pres=tol_pres, tol_vel=tol_vel, nranks=nranks)
     be.free([re, im] + vor)
-    return written + written_rv
+    return written + written_rv + written_rx

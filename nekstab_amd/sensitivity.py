@@ -12,7 +12,8 @@ nsk_forced_map; on element shards their nsk_group_* twins: every driver below ta
 single-rank context and writes the same files); delta_forcing is pointwise and stays on the host.  Output files carry the reference's prefixes (KIN, wm_, tr_,
 ti_, pr_, pi_, sr_, si_, fsr, fsi, dfr) so that nekStab's own scripts read them.  ``np_*`` functions are the numpy
 restatement the device is tested against; ``np_vorticity`` is that of nsk_vorticity (comp_vort3, the Rv files that
-``outpost.outpost_ks(..., ifvor=True)`` writes).
+``outpost.outpost_ks(..., ifvor=True)`` writes), ``np_vortex_criteria`` with ``gll_filter_matrix`` that of nsk_vortex_criteria
+(lambda2, Q, Omega of vortex_core: the vox / omg files of ``outpost.outpost_vox``).
 
 Three departures from the reference, all deliberate:
   * in 3-D the transport term uses d v / d z where core/sensitivity.f:219, 222, 228, 231 read d w / d z (Marquet's formula;
@@ -191,6 +192,55 @@ def np_vorticity(geom: NpGeom, u):
     dssum = lambda f: np.bincount(geom.gid.ravel(), weights=f.ravel(), minlength=geom.nglob)[geom.gid]
     mass = dssum(geom.bm1)
     return np.array([dssum(c * geom.bm1) / mass for c in curl])
+
+
+def gll_filter_matrix(lx1: int, wght: float) -> np.ndarray:
+    """The 1-D matrix of Nek5000's filter_s0(f, wght, 1, .) on the lx1 GLL points: F = Phi diag(1, ..., 1, 1 - wght) Phi^-1 with
+    Phi[j][k] = phi_k(xi_j), phi_0 = L_0, phi_1 = L_1, phi_k = L_k - L_{k-2} (L: Legendre).  F leaves every polynomial of degree
+    <= lx1 - 2 as it is and multiplies phi_{lx1-1} by 1 - wght; wght = 0 gives the identity exactly."""
+    if not (np.isfinite(wght) and 0.0 <= wght <= 1.0):
+        raise ValueError("wght must lie in [0, 1]")
+    if wght == 0.0:
+        return np.eye(lx1)
+    z = gauss_lobatto_legendre(lx1)[0]
+    L = np.polynomial.legendre.legvander(z, lx1 - 1)               # L[j][k] = L_k(xi_j)
+    phi = L.copy()
+    phi[:, 2:] -= L[:, :-2]
+    diag = np.ones(lx1)
+    diag[-1] = 1.0 - wght
+    return np.linalg.solve(phi.T, (phi * diag).T).T
+
+
+def np_vortex_criteria(geom: NpGeom, u, wght=0.5):
+    """vortex_core('lambda2' / 'q' / 'omega') of nekStab_outpost (core/usr_extra.f:269-273) on a velocity field [ndim, nel, ...]:
+    returns (lambda2, q, omega), each [nel, ...].  g[i][j] = d u_i / d x_j element-local (comp_gije), S and O its symmetric and
+    antisymmetric parts, ndim x ndim:
+      lambda2   the second largest eigenvalue of S S + O O (Jeong & Hussain): the middle of three, the smaller of two
+      q         compute_secondInv (core/postproc.f:374-403): 3-D the sum of the principal 2 x 2 minors of g; 2-D
+                (g11 + g22)^2 - 2 g12 g21 - g11^2 - g22^2, twice the determinant (twice the 3-D value of a z-invariant field)
+      omega     compute_omega_jc (core/postproc.f:31-79): b / (a + b + 1e-5), a = (||S||_F^2)^2, b = (||O||_F^2)^2
+    each then filtered element by element with ``gll_filter_matrix(lx1, wght)`` along every reference direction."""
+    nd = geom.ndim
+    g = np.array([geom.grad(np.asarray(u[c], dtype=np.float64)) for c in range(nd)])       # g[i][j]
+    gm = np.moveaxis(g, (0, 1), (-2, -1))                                                   # [nel, ..., i, j]
+    S, O = 0.5 * (gm + np.swapaxes(gm, -1, -2)), 0.5 * (gm - np.swapaxes(gm, -1, -2))
+    lam = np.linalg.eigvalsh(S @ S + O @ O)[..., nd - 2]                                    # ascending: index nd - 2 is the second largest
+    if nd == 3:
+        q = (g[1][1] * g[2][2] - g[1][2] * g[2][1]) + (g[0][0] * g[1][1] - g[0][1] * g[1][0]) + (g[2][2] * g[0][0] - g[0][2] * g[2][0])
+    else:
+        q = (g[0][0] + g[1][1]) * (g[0][0] + g[1][1]) - 2 * g[0][1] * g[1][0] - g[0][0] * g[0][0] - g[1][1] * g[1][1]
+    a, b = np.sum(S * S, axis=(-1, -2)) ** 2, np.sum(O * O, axis=(-1, -2)) ** 2
+    om = b / (a + b + 1e-5)
+    if wght == 0.0:
+        return lam, q, om
+    F = gll_filter_matrix(geom.D.shape[0], wght)
+
+    def filt(f):
+        if nd == 2:
+            return np.einsum("ai,bj,eji->eba", F, F, f, optimize=True)
+        return np.einsum("ai,bj,ck,ekji->ecba", F, F, F, f, optimize=True)
+
+    return filt(lam), filt(q), filt(om)
 
 
 def delta_forcing(ub, fsr, fsi, alpha=1.0):

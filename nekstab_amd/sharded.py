@@ -405,6 +405,11 @@ class ShardGroup:
         """w = vorticity of q's velocity, mass-averaged over ALL ranks (nsk_group_vorticity: one halo exchange per call)."""
         self._chk(self.lib.nsk_group_vorticity(self._arr, self.R, self._per_rank(q), self._per_rank(w)))
 
+    def vortex_criteria(self, w, q, wght=0.5, omega=None):
+        """NekStabHip.vortex_criteria on the shards (nsk_group_vortex_criteria): element-local, no halo exchange."""
+        self._chk(self.lib.nsk_group_vortex_criteria(self._arr, self.R, self._per_rank(q), float(wght), self._per_rank(w),
+                                                     None if omega is None else self._per_rank(omega)))
+
     def sfd_map(self, f, q, qbar, chi, omega_c):
         """NekStabHip.sfd_map on the shards (nsk_group_sfd_map): every rank filters and forces its own elements; the
         residuals are sums over ALL ranks."""
@@ -682,6 +687,10 @@ class ShardRank:
 
     def vorticity(self, w, q):
         self._chk(self.lib.nsk_group_vorticity(self._one, 1, *self._one_of(q, w)))
+
+    def vortex_criteria(self, w, q, wght=0.5, omega=None):
+        self._chk(self.lib.nsk_group_vortex_criteria(self._one, 1, self._one_of(q)[0], float(wght), self._one_of(w)[0],
+                                                     None if omega is None else self._one_of(omega)[0]))
 
     def sfd_map(self, f, q, qbar, chi, omega_c):
         res = np.zeros(self.nsteps)
