@@ -394,6 +394,58 @@ static int dupload(nsk_ctx* c, const T** p, const std::vector<T>& h) {
   *p = q;
   return 0;
 }
+namespace {
+// a device array that lives as long as a scope (on every return path), unless release() hands it on
+struct DevTmp {
+  nsk_ctx* c; double* p = nullptr;
+  explicit DevTmp(nsk_ctx* c_) : c(c_) {}
+  DevTmp(DevTmp&& o) : c(o.c), p(o.release()) {}
+  ~DevTmp() { if (p) { nsk_vec v = p; nsk_vec_free(c, 1, &v); } }
+  double* release() { double* q = p; p = nullptr; return q; }
+};
+// Maps with something behind their steps (a force, SFD, BoostConv) run eager steps on frozen launch budgets: the captured step
+// graphs and the budgets belong to the unforced maps.  Saved here, put back by restore() or at the end of the scope (a map that
+// outgrew its budgets doubled them for its redo).
+struct EagerRun {
+  struct Saved { int use_graph, freeze, helm[NCLS], pres[NCLS]; };
+  std::vector<nsk_ctx*>& G; std::vector<Saved> keep; bool done = false;
+  explicit EagerRun(std::vector<nsk_ctx*>& G_) : G(G_), keep(G_.size()) {
+    for (size_t r = 0; r < G.size(); ++r) {
+      nsk_ctx* c = G[r];
+      keep[r].use_graph = c->use_graph; keep[r].freeze = c->budget_freeze;
+      for (int k = 0; k < NCLS; ++k) { keep[r].helm[k] = c->cur_helm[k]; keep[r].pres[k] = c->cur_pres[k]; }
+      c->use_graph = 0;                                          // group_graph_ok: eager
+      c->budget_freeze = 1;
+    }
+  }
+  void restore() {
+    if (done) return;
+    done = true;
+    for (size_t r = 0; r < G.size(); ++r) {
+      nsk_ctx* c = G[r];
+      c->use_graph = keep[r].use_graph; c->budget_freeze = keep[r].freeze;
+      for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
+    }
+  }
+  ~EagerRun() { restore(); }
+};
+}  // namespace
+
+// a state vector (velocity components with stride nloc, then the pressure) into the stepper's field (stride cs) and back, on the stream
+static int state_load(nsk_ctx* c, const double* q) {
+  const Dev& d = c->d;
+  for (int cc = 0; cc < c->ndim; ++cc)
+    HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d.p, q + c->ndim * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+static int state_store(nsk_ctx* c, double* f) {
+  const Dev& d = c->d;
+  for (int cc = 0; cc < c->ndim; ++cc)
+    HIPCHK(hipMemcpyAsync(f + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(f + c->ndim * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
 
 static bool lda_ok_for_ecv(const nsk_ctx* c) { return c->ndim == 2 && c->coarse_lda > 0 && c->coarse_lda <= 3072 && !c->local; }      // where k_update_coarse runs
 
@@ -445,7 +497,12 @@ static int eapply(nsk_ctx* c, const double* pin, double* wout) {
 // Jacobi diagonals of H for the three BDF orders from the host copies (h_mask, h_dAs, h_bs) and the context's dt: [3][nloc], or
 // with one mask per component [3][2][nloc] on quadrilaterals and [3][nloc] UNMASKED on hexahedra (whose kernel forms take the
 // masks from the packed word behind Dev::mask: nsk3_kernels.hpp, cm_bits)
+// The host copies (and h_cflg) are the context's own, node for node, on a full-mesh context; a shard (of a rank-local parent
+// too) reads its parent's, node k of its element le at elems[le] * NN + k.
+static const nsk_ctx* host_geom(const nsk_ctx* c) { return c->parent ? c->parent : c; }
+static long long host_node(const nsk_ctx* c, int le, int k) { return (long long)(c->parent ? c->elems[le] : le) * c->NN + k; }
 static void jacobi_diagonals(const nsk_ctx* c, std::vector<double>& dinv) {
+  const nsk_ctx* H = host_geom(c);
   const bool unmasked = c->cm && c->ndim == 3;
   const int nmc = (c->cm && !unmasked) ? c->ndim : 1;
   const long long nloc = c->nloc;
@@ -453,8 +510,12 @@ static void jacobi_diagonals(const nsk_ctx* c, std::vector<double>& dinv) {
   dinv.resize((size_t)3 * nmc * nloc);
   for (int k = 0; k < 3; ++k)
     for (int mc = 0; mc < nmc; ++mc)
-      for (long long l = 0; l < nloc; ++l)
-        dinv[((size_t)k * nmc + mc) * nloc + l] = (unmasked ? 1.0 : c->h_mask[(size_t)mc * nloc + l]) / (c->d.nu * c->h_dAs[l] + bd0[k] / c->dt * c->h_bs[l]);
+      for (int le = 0; le < c->nel; ++le)
+        for (int i = 0; i < c->NN; ++i) {
+          const long long lg = host_node(c, le, i);
+          dinv[((size_t)k * nmc + mc) * nloc + (size_t)le * c->NN + i] =
+              (unmasked ? 1.0 : H->h_mask[(size_t)mc * H->nloc + lg]) / (c->d.nu * H->h_dAs[lg] + bd0[k] / c->dt * H->h_bs[lg]);
+        }
 }
 
 // dense in-place inverse (Gauss-Jordan, partial pivoting), n small
@@ -1946,9 +2007,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
     for (int k = 0; k < NCLS; ++k) { int rc = ensure_graph(c, k, adjoint); if (rc) return rc; }
   const int gsteps = (use_graph && !per_step && c->graph_steps > 1 && c->nsteps >= CLS_ISTEP[NCLS - 1] + 2 * c->graph_steps) ? c->graph_steps : 1;
   if (gsteps > 1) { int rc = ensure_graph_multi(c, adjoint); if (rc) return rc; }
-  for (int cc = 0; cc < c->ndim; ++cc)
-    HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(d.p, q + c->ndim * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  { int rc = state_load(c, q); if (rc) return rc; }
   if (d.bf_stride || d.forb) {
     if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
     HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
@@ -1992,10 +2051,8 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   }
   if (c->sfd.on) sfd_call(c, c->nsteps);
   { int rc = flush_proj(c); if (rc) return rc; }          // the last step's update of the projection space: the context between maps is what it is without the option
-  for (int cc = 0; cc < c->ndim; ++cc)
-    HIPCHK(hipMemcpyAsync(f + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(f + c->ndim * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  if (c->nscal > 0) {                         // ifheat = .false.: the stepper leaves the scalars alone (core/matvec.f nopcopy in / out)
+  { int rc = state_store(c, f); if (rc) return rc; }
+  if (c->nscal > 0) {                       // ifheat = .false.: the stepper leaves the scalars alone (core/matvec.f nopcopy in / out)
     const long long toff = (long long)c->ndim * d.nloc + d.npr;
     HIPCHK(hipMemcpyAsync(f + toff, q + toff, (size_t)c->nscal * d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   }
@@ -2335,160 +2392,6 @@ static int group_allmax(std::vector<nsk_ctx*>& G, double* vals) {
   double m = 0.0;
   for (double v : slot) m = std::max(m, v);
   for (size_t r = 0; r < G.size(); ++r) vals[r] = m;
-  return 0;
-}
-
-// New linearisation point on element shards (nsk_set_baseflow for the ranks of this process): every rank recomputes the
-// base-flow constants of its own elements; dt / nsteps follow from the CFL maximum over ALL ranks (compute_cfl is a glmax).
-static int group_set_baseflow(std::vector<nsk_ctx*>& G, const double* const* q) {
-  std::vector<double> ctarg(G.size(), 0.0);
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r]; nsk_ctx* P = c->parent; Dev& d = c->d;
-    if (!P) return fail(NSK_EINVAL, "needs shard contexts");
-    const int nd = c->ndim, NN = c->NN;
-    d.bfmask = 0;                                          // (the new constants are not scanned for zero arrays on shards)
-    d.forb = 0;                                            // a Fourier orbit ends here (nsk_group_set_orbit comes through here too)
-    DISPATCH_N(c->key, {                                   // (hexahedra: Dev::cUr aliases the 12-constant array bfc)
-      hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, q[r], (double*)d.cUr, (double*)d.cUs,
-                         (double*)d.GUx, (double*)d.GUy, (double*)d.GVx, (double*)d.GVy);
-    });
-    std::vector<double> u((size_t)nd * c->nloc);
-    HIPCHK(hipMemcpyAsync(u.data(), q[r], (size_t)nd * c->nloc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    double ct = 0.0;
-    for (int le = 0; le < c->nel; ++le)
-      for (int k = 0; k < NN; ++k) {
-        const long long l = (long long)le * NN + k, lg = (long long)c->elems[le] * NN + k;
-        double sm = 0.0;
-        for (int a = 0; a < nd; ++a) {
-          double t = 0.0;
-          for (int cc = 0; cc < nd; ++cc) t += u[(size_t)cc * c->nloc + l] * P->h_cflg[(size_t)nd * nd * lg + a * nd + cc];
-          sm += std::fabs(t);
-        }
-        ct = std::max(ct, sm);
-      }
-    ctarg[r] = ct;
-  }
-  int rc = group_allmax(G, ctarg.data());
-  if (rc) return rc;
-  if (!(ctarg[0] > 0.0)) return fail(NSK_EINVAL, "base flow is zero");
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r]; nsk_ctx* P = c->parent; Dev& d = c->d;
-    const int NN = c->NN;
-    const double dt0 = P->cfl_target / ctarg[r];
-    c->nsteps = (int)std::ceil(c->endtime / dt0);
-    c->dt = c->endtime / c->nsteps;
-    d.dt = c->dt;
-    std::vector<double> dinv((size_t)3 * c->nloc);
-    const double bd0[3] = {1.0, 1.5, 11.0 / 6.0};
-    for (int k = 0; k < 3; ++k)
-      for (int le = 0; le < c->nel; ++le)
-        for (int i = 0; i < NN; ++i) {
-          const long long lg = (long long)c->elems[le] * NN + i;
-          dinv[(size_t)k * c->nloc + (size_t)le * NN + i] = P->h_mask[lg] / (d.nu * P->h_dAs[lg] + bd0[k] / c->dt * P->h_bs[lg]);
-        }
-    HIPCHK(hipMemcpy((double*)d.dinv, dinv.data(), dinv.size() * sizeof(double), hipMemcpyHostToDevice));
-    invalidate_graphs(c);
-    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
-    c->bh_n = 0;
-  }
-  return 0;
-}
-int nsk_group_set_baseflow(nsk_ctx** shards, int n, nsk_vec* q) {
-  if (!shards || n < 1 || !q) return fail(NSK_EINVAL, "bad argument");
-  std::vector<nsk_ctx*> G(shards, shards + n);
-  for (int r = 0; r < n; ++r) if (!G[r] || !q[r]) return fail(NSK_EINVAL, "bad argument");
-  if (G[0]->d.bf_stride) return fail(NSK_EINVAL, "a stored orbit is active: call nsk_group_set_orbit again instead");
-  return group_set_baseflow(G, (const double* const*)q);
-}
-
-// a stored orbit ends: the base-flow pointers go back to the steady arrays (the caller decides about the captured graphs)
-static void steady_back(nsk_ctx* c) {
-  Dev& d = c->d;
-  if (!d.bf_stride) return;
-  if (c->ndim == 3) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; }
-  else { d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5]; }
-  d.bf_stride = 0;
-}
-
-// Time-periodic base flow on element shards (nsk_set_orbit for the ranks of this process): the full equations are integrated
-// over one period by the sharded stepper and every rank stores the base-flow constants of its own elements per step.
-int nsk_group_set_orbit(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, nsk_vec* end) {
-  if (!shards || n < 1 || !q0) return fail(NSK_EINVAL, "bad argument");
-  std::vector<nsk_ctx*> G(shards, shards + n);
-  for (int r = 0; r < n; ++r)
-    if (!G[r] || !q0[r] || !G[r]->parent) return fail(NSK_EINVAL, "needs shard contexts");
-  const int nd = G[0]->ndim;
-  // quadrilaterals: six arrays of nel*lxd^2 per step; hexahedra: one array of 12*nel*lxd^3 per step behind Dev::bfc (= cUr)
-  const int narr = nd == 3 ? 1 : 6;
-  int rc;
-  for (nsk_ctx* c : G) steady_back(c);
-  if ((rc = group_set_baseflow(G, (const double* const*)q0))) return rc;
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r]; Dev& d = c->d;
-    const long long per_step = nd == 3 ? 12 * d.nfine : (long long)c->nel * c->NDD;
-    for (int k = 0; k < narr; ++k) {
-      if (c->orbit[k]) { nsk_vec v = c->orbit[k]; nsk_vec_free(c, 1, &v); c->orbit[k] = nullptr; }
-      if ((rc = dalloc(c, &c->orbit[k], (size_t)c->nsteps * per_step))) return rc;
-    }
-    double* vr = const_cast<double*>(d.spng_vr);
-    if (!vr && (rc = dalloc(c, &vr, nd * d.cs))) return rc;
-    const double* q = (const double*)q0[r];
-    for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(vr + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    d.spng_vr = vr; d.nl_spng_str = spng_str;
-    if (!d.bstep && (rc = dalloc(c, &d.bstep, 4))) return rc;
-    HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
-    for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d.p, q + nd * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  const int nsteps = G[0]->nsteps;
-  for (int istep = 1; istep <= nsteps; ++istep) {
-    for (nsk_ctx* c : G) {
-      Dev& d = c->d;
-      const long long off = (long long)(istep - 1) * (nd == 3 ? 12 * d.nfine : (long long)c->nel * c->NDD);
-      // k_baseflow reads a state vector (component stride nloc); the stepper's field has stride cs = nloc + ghost slots
-      for (int cc = 0; cc < nd; ++cc)
-        HIPCHK(hipMemcpyAsync(c->scratch + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      if (nd == 3) {
-        DISPATCH_N(c->key, {
-          hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)c->scratch, c->orbit[0] + off,
-                             (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr);
-        });
-      } else {
-        DISPATCH_N(c->key, {
-          hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)c->scratch, c->orbit[0] + off, c->orbit[1] + off,
-                             c->orbit[2] + off, c->orbit[3] + off, c->orbit[4] + off, c->orbit[5] + off);
-        });
-      }
-    }
-    if ((rc = group_step(G, istep, 2))) return rc;
-  }
-  Stats h;
-  HIPCHK(hipMemcpyAsync(&h, G[0]->d.stats, sizeof(Stats), hipMemcpyDeviceToHost, G[0]->stream));
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r]; Dev& d = c->d;
-    if (end && end[r]) {
-      double* f = (double*)end[r];
-      for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(f + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(f + nd * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-  }
-  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
-  if (h.unconverged > 0) return fail(NSK_ENOCONV, "inner solve hit its iteration cap while integrating the base-flow orbit (sharded)");
-  for (nsk_ctx* c : G) {
-    Dev& d = c->d;
-    if (nd == 3) {
-      c->steady[0] = d.bfc;
-      d.bfc = c->orbit[0]; d.cUr = c->orbit[0]; d.bfmask = 0;
-      d.bf_stride = 12 * d.nfine;
-    } else {
-      c->steady[0] = d.cUr; c->steady[1] = d.cUs; c->steady[2] = d.GUx; c->steady[3] = d.GUy; c->steady[4] = d.GVx; c->steady[5] = d.GVy;
-      d.cUr = c->orbit[0]; d.cUs = c->orbit[1]; d.GUx = c->orbit[2]; d.GUy = c->orbit[3]; d.GVx = c->orbit[4]; d.GVy = c->orbit[5];
-      d.bf_stride = (long long)c->nel * c->NDD;
-    }
-    c->orbit_steps = c->nsteps;
-    invalidate_graphs(c);
-  }
   return 0;
 }
 
@@ -3100,44 +3003,73 @@ static int scan_bfmask(nsk_ctx* c) {
   return 0;
 }
 
+// k_baseflow<N> of a state vector q into six arrays (quadrilaterals) or into the 12-constant array `to[0]` (hexahedra: the rest NULL)
+static int launch_baseflow(nsk_ctx* c, const double* q, double* const to[6]) {
+  DISPATCH_N(c->key, { hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, c->d, q, to[0], to[1], to[2], to[3], to[4], to[5]); });
+  return 0;
+}
 // New linearisation point (core/newton_krylov.f:371-372 + prepare_linearized_solver): base-flow
 // constants of the convection kernels, dt / nsteps from the CFL rule, Jacobi diagonals for the new dt.
+// One body for a full-mesh context (a group of one, sharded = false) and for the ranks of one process: every rank recomputes
+// the constants of its own elements; dt / nsteps follow from the CFL maximum over ALL ranks (compute_cfl is a glmax).
+static int set_baseflow_body(std::vector<nsk_ctx*>& G, bool sharded, const double* const* q) {
+  std::vector<double> ctarg(G.size(), 0.0);
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r]; Dev& d = c->d;
+    if (sharded && !c->parent) return fail(NSK_EINVAL, "needs shard contexts");
+    if (!sharded && (c->parent || c->nranks > 1)) return fail(NSK_EINVAL, "shards: use nsk_group_set_baseflow");
+    if (!sharded && c->clone_of) return fail(NSK_EINVAL, "lanes share the base-flow constants of the context they were cloned from: set the base flow there, before nsk_clone");
+    const nsk_ctx* H = host_geom(c);
+    const int nd = c->ndim;
+    d.forb = 0;                                            // a Fourier orbit ends here (the orbit setters come through here too)
+    if (sharded) d.bfmask = 0;                             // the new constants are scanned for zero arrays on full-mesh contexts only (below)
+    double* const steady[6] = {(double*)d.cUr, (double*)d.cUs, (double*)d.GUx, (double*)d.GUy, (double*)d.GVx, (double*)d.GVy};
+    { const int rc = launch_baseflow(c, q[r], steady); if (rc) return rc; }       // (hexahedra: Dev::cUr aliases the 12-constant array bfc)
+    std::vector<double> u((size_t)nd * c->nloc);
+    HIPCHK(hipMemcpyAsync(u.data(), q[r], (size_t)nd * c->nloc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int le = 0; le < c->nel; ++le)
+      for (int k = 0; k < c->NN; ++k) {
+        const long long l = (long long)le * c->NN + k, lg = host_node(c, le, k);
+        double s = 0.0;
+        for (int a = 0; a < nd; ++a) {
+          double t = 0.0;
+          for (int cc = 0; cc < nd; ++cc) t += u[(size_t)cc * c->nloc + l] * H->h_cflg[(size_t)nd * nd * lg + a * nd + cc];
+          s += std::fabs(t);
+        }
+        ctarg[r] = std::max(ctarg[r], s);
+      }
+  }
+  if (sharded) { int rc = group_allmax(G, ctarg.data()); if (rc) return rc; }      // shards: the CFL maximum is over all ranks
+  if (!(ctarg[0] > 0.0)) return fail(NSK_EINVAL, "base flow is zero");
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r]; Dev& d = c->d;
+    const double dt0 = host_geom(c)->cfl_target / ctarg[r];
+    c->nsteps = (int)std::ceil(c->endtime / dt0);
+    c->dt = c->endtime / c->nsteps;
+    d.dt = c->dt;
+    std::vector<double> dinv;
+    jacobi_diagonals(c, dinv);
+    HIPCHK(hipMemcpy((double*)d.dinv, dinv.data(), dinv.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (!sharded) { const int rc = scan_bfmask(c); if (rc) return rc; }
+    invalidate_graphs(c);                                  // coefficients are baked into the captured graphs
+    // shards start again from the full launch budgets; a full-mesh context keeps its own: Newton sets a base flow every iteration
+    if (sharded) { for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; } c->bh_n = 0; }
+  }
+  return 0;
+}
 int nsk_set_baseflow(nsk_ctx* c, nsk_vec qv) {
   if (!c || !qv) return fail(NSK_EINVAL, "bad argument");
-  if (c->parent || c->nranks > 1) return fail(NSK_EINVAL, "shards: use nsk_group_set_baseflow");
-  if (c->clone_of) return fail(NSK_EINVAL, "lanes share the base-flow constants of the context they were cloned from: set the base flow there, before nsk_clone");
-  Dev& d = c->d;
-  d.forb = 0;                     // a Fourier orbit ends here (nsk_set_orbit comes through here too)
+  std::vector<nsk_ctx*> G(1, c);
   const double* q = (const double*)qv;
-  DISPATCH_N(c->key, {
-    hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, q, (double*)d.cUr, (double*)d.cUs,
-                       (double*)d.GUx, (double*)d.GUy, (double*)d.GVx, (double*)d.GVy);
-  });
-  const int nd = c->ndim;
-  std::vector<double> u((size_t)nd * c->nloc);
-  HIPCHK(hipMemcpyAsync(u.data(), q, (size_t)nd * c->nloc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  double ctarg = 0.0;
-  for (long long l = 0; l < c->nloc; ++l) {
-    double s = 0.0;
-    for (int a = 0; a < nd; ++a) {
-      double t = 0.0;
-      for (int cc = 0; cc < nd; ++cc) t += u[(size_t)cc * c->nloc + l] * c->h_cflg[(size_t)nd * nd * l + a * nd + cc];
-      s += std::fabs(t);
-    }
-    ctarg = std::max(ctarg, s);
-  }
-  if (!(ctarg > 0.0)) return fail(NSK_EINVAL, "base flow is zero");
-  const double dt0 = c->cfl_target / ctarg;
-  c->nsteps = (int)std::ceil(c->endtime / dt0);
-  c->dt = c->endtime / c->nsteps;
-  d.dt = c->dt;
-  std::vector<double> dinv;
-  jacobi_diagonals(c, dinv);
-  HIPCHK(hipMemcpy((double*)d.dinv, dinv.data(), dinv.size() * sizeof(double), hipMemcpyHostToDevice));
-  { const int rc = scan_bfmask(c); if (rc) return rc; }
-  invalidate_graphs(c);           // coefficients are baked into the captured graphs
-  return 0;
+  return set_baseflow_body(G, false, &q);
+}
+int nsk_group_set_baseflow(nsk_ctx** shards, int n, nsk_vec* q) {
+  if (!shards || n < 1 || !q) return fail(NSK_EINVAL, "bad argument");
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  for (int r = 0; r < n; ++r) if (!G[r] || !q[r]) return fail(NSK_EINVAL, "bad argument");
+  if (G[0]->d.bf_stride) return fail(NSK_EINVAL, "a stored orbit is active: call nsk_group_set_orbit again instead");
+  return set_baseflow_body(G, true, (const double* const*)q);
 }
 
 // ---- Fourier-compressed periodic base flow (core/fourier.f) --------------------------------------------------------------
@@ -3182,7 +3114,8 @@ static int forb_alloc(nsk_ctx* c, int M) {
   return 0;
 }
 // the modes are in place: linearised maps take them from now on; amp (NULL or 2M+1 doubles) = bm1-weighted L2 norms of
-// A_0, A_1, B_1, .. over all velocity components (amp_real / amp_img, core/fourier.f:46-53)
+// A_0, A_1, B_1, .. over all velocity components (amp_real / amp_img, core/fourier.f:46-53), summed on the host (a full-mesh
+// context; shards: group_mode_amp, which adds in another order)
 static int forb_activate(nsk_ctx* c, int M, double T, double* amp) {
   Dev& d = c->d;
   if (!d.bstep) { int rc = dalloc(c, &d.bstep, 4); if (rc) return rc; }
@@ -3203,177 +3136,6 @@ static int forb_activate(nsk_ctx* c, int M, double T, double* amp) {
     }
   }
   return 0;
-}
-
-// Time-periodic base flow for Floquet analysis (uparam(1)=3.11, core/matvec.f:191-236, core/eigensolvers.f:201-210):
-// integrate the full equations from q0 over one period T = endtime (DNS sponge towards the initial field with
-// strength spng_str, core/utils.f:165-170) and store the base-flow constants of every step; the linearised
-// maps then read slot istep-1 at step istep.  Returns Phi_T(q0) in `end` (periodicity check) if not NULL.
-// nmodes >= 0 (nsk_set_orbit_fourier): the same integration, but every step's field is added into the lowest nmodes temporal
-// Fourier modes (k_orbit_dft) instead of its constants being stored.
-static int set_orbit_impl(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end, int nmodes, double* amp) {
-  Dev& d = c->d;
-  const double* q0 = (const double*)q0v;
-  const bool four = nmodes >= 0;
-  const int nm = 2 * nmodes + 1;
-  double* dftw = nullptr;                                       // [nsteps][nm] coefficient rows of k_orbit_dft (Fourier form)
-  // dt, nsteps are known once the base flow is set: the rows c_k / N cos, sin (2 pi k n / N), c_k = 2 except c_0 = c_{N/2} = 1
-  auto four_begin = [&]() -> int {
-    if (nmodes > c->nsteps / 2) return fail(NSK_EINVAL, "nsk_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2 (" + std::to_string(c->nsteps / 2) + ")");
-    for (int k = 0; k < 6; ++k) if (c->orbit[k]) { nsk_vec v = c->orbit[k]; nsk_vec_free(c, 1, &v); c->orbit[k] = nullptr; }
-    c->orbit_steps = 0;
-    int rc = forb_alloc(c, nmodes);
-    if (rc) return rc;
-    const std::vector<double> w = forb_dft_rows(c->nsteps, nmodes);
-    if ((rc = dalloc(c, &dftw, w.size()))) return rc;
-    HIPCHK(hipMemcpy(dftw, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-    return 0;
-  };
-  auto four_add = [&](int istep) {
-    const long long nv = (long long)c->ndim * d.nloc;
-    hipLaunchKernelGGL(k_orbit_dft, dim3((unsigned)std::min<long long>((nv + 255) / 256, 4096)), dim3(256), 0, c->stream, c->forb_modes, (const double*)d.u,
-                       (const double*)(dftw + (size_t)(istep - 1) * nm), nm, d.nloc, d.cs, c->ndim);
-  };
-  auto four_end = [&]() { if (dftw) { nsk_vec v = dftw; nsk_vec_free(c, 1, &v); dftw = nullptr; } };
-  if (c->ndim == 3) {
-    // hexahedra: the twelve dealiasing-mesh constants of every time step of the orbit, [nsteps][12][nfine] behind Dev::bfc
-    steady_back(c);
-    int rc = nsk_set_baseflow(c, q0v);                          // dt, nsteps from the CFL of the initial field
-    if (rc) return rc;
-    const long long nfine = d.nfine;
-    if (four) { if ((rc = four_begin())) return rc; }
-    else {
-      if (c->orbit[0]) { nsk_vec v = c->orbit[0]; nsk_vec_free(c, 1, &v); c->orbit[0] = nullptr; }
-      if ((rc = dalloc(c, &c->orbit[0], (size_t)c->nsteps * 12 * nfine))) return rc;
-    }
-    double* vr = const_cast<double*>(d.spng_vr);
-    if (!vr && (rc = dalloc(c, &vr, 3 * d.cs))) return rc;
-    for (int cc = 0; cc < 3; ++cc) HIPCHK(hipMemcpyAsync(vr + cc * d.cs, q0 + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    d.spng_vr = vr; d.nl_spng_str = spng_str;
-    if (!d.bstep && (rc = dalloc(c, &d.bstep, 4))) return rc;
-    invalidate_graphs(c);
-    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
-    c->bh_n = 0;
-    HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
-    for (int cc = 0; cc < 3; ++cc) HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q0 + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d.p, q0 + 3 * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    for (int istep = 1; istep <= c->nsteps; ++istep) {
-      if (four) four_add(istep);
-      else DISPATCH_N(c->key, {
-        hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)d.u, c->orbit[0] + (size_t)(istep - 1) * 12 * nfine,
-                           (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr, (double*)nullptr);
-      });
-      if ((rc = step(c, istep, 2))) { four_end(); return rc; }
-    }
-    Stats h;
-    HIPCHK(hipMemcpyAsync(&h, d.stats, sizeof(Stats), hipMemcpyDeviceToHost, c->stream));
-    if (end) {
-      double* f = (double*)end;
-      for (int cc = 0; cc < 3; ++cc) HIPCHK(hipMemcpyAsync(f + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(f + 3 * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    four_end();
-    if (h.unconverged > 0) return fail(NSK_ENOCONV, "inner solve hit its iteration cap while integrating the base-flow orbit");
-    if (four) return forb_activate(c, nmodes, c->endtime, amp);
-    c->steady[0] = d.bfc;
-    d.bfc = c->orbit[0]; d.cUr = c->orbit[0]; d.bfmask = 0;
-    d.bf_stride = 12 * nfine; c->orbit_steps = c->nsteps;
-    invalidate_graphs(c);
-    return 0;
-  }
-  steady_back(c);                                               // back to the steady arrays first
-  int rc = nsk_set_baseflow(c, q0v);                            // dt, nsteps from the CFL of the initial field
-  if (rc) return rc;
-  const long long nfine = (long long)c->nel * c->NDD;
-  if (four) { if ((rc = four_begin())) return rc; }
-  else for (int k = 0; k < 6; ++k) {
-    if (c->orbit[k]) { nsk_vec v = c->orbit[k]; nsk_vec_free(c, 1, &v); c->orbit[k] = nullptr; }
-    if ((rc = dalloc(c, &c->orbit[k], (size_t)c->nsteps * nfine))) return rc;
-  }
-  double* vr = const_cast<double*>(d.spng_vr);                  // one buffer per context: Newton calls this every iteration
-  if (!vr && (rc = dalloc(c, &vr, 2 * d.cs))) return rc;
-  HIPCHK(hipMemcpyAsync(vr, q0, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(vr + d.cs, q0 + d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  d.spng_vr = vr; d.nl_spng_str = spng_str;
-  if (!d.bstep && (rc = dalloc(c, &d.bstep, 4))) return rc;
-  invalidate_graphs(c);
-  for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
-  c->bh_n = 0;
-  HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
-  HIPCHK(hipMemcpyAsync(d.u, q0, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(d.u + d.cs, q0 + d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(d.p, q0 + 2 * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  for (int istep = 1; istep <= c->nsteps; ++istep) {
-    const long long off = (long long)(istep - 1) * nfine;
-    if (four) four_add(istep);
-    else DISPATCH_N(c->key, {
-      hipLaunchKernelGGL(k_baseflow<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)d.u, c->orbit[0] + off, c->orbit[1] + off,
-                         c->orbit[2] + off, c->orbit[3] + off, c->orbit[4] + off, c->orbit[5] + off);
-    });
-    if ((rc = step(c, istep, 2))) { four_end(); return rc; }
-  }
-  Stats h;
-  HIPCHK(hipMemcpyAsync(&h, d.stats, sizeof(Stats), hipMemcpyDeviceToHost, c->stream));
-  if (end) {
-    double* f = (double*)end;
-    HIPCHK(hipMemcpyAsync(f, d.u, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(f + d.nloc, d.u + d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(f + 2 * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIPCHK(hipStreamSynchronize(c->stream));
-  four_end();
-  if (h.unconverged > 0) return fail(NSK_ENOCONV, "inner solve hit its iteration cap while integrating the base-flow orbit");
-  if (four) return forb_activate(c, nmodes, c->endtime, amp);
-  c->steady[0] = d.cUr; c->steady[1] = d.cUs; c->steady[2] = d.GUx; c->steady[3] = d.GUy; c->steady[4] = d.GVx; c->steady[5] = d.GVy;
-  d.cUr = c->orbit[0]; d.cUs = c->orbit[1]; d.GUx = c->orbit[2]; d.GUy = c->orbit[3]; d.GVx = c->orbit[4]; d.GVy = c->orbit[5];
-  d.bf_stride = nfine; c->orbit_steps = c->nsteps;
-  invalidate_graphs(c);
-  return 0;
-}
-
-int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
-  if (!c || !q0v) return fail(NSK_EINVAL, "bad argument");
-  if (c->parent) return fail(NSK_EINVAL, "shards: use nsk_group_set_orbit");
-  if (c->clone_of) return fail(NSK_EINVAL, "not on a lane (nsk_clone)");
-  return set_orbit_impl(c, q0v, spng_str, end, -1, nullptr);
-}
-
-// The orbit of nsk_set_orbit kept as its lowest nmodes temporal harmonics (fourier_decomposition, core/fourier.f:23-88):
-// (2 nmodes + 1) ndim nloc doubles on the device whatever the number of steps; period T = endtime.
-int nsk_set_orbit_fourier(nsk_ctx* c, nsk_vec q0v, double spng_str, int nmodes, nsk_vec end, double* amp) {
-  if (!c || !q0v) return fail(NSK_EINVAL, "bad argument");
-  { const int rc = forb_refuse(c, "nsk_set_orbit_fourier"); if (rc) return rc; }
-  if (nmodes < 0) return fail(NSK_EINVAL, "nsk_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2");
-  return set_orbit_impl(c, q0v, spng_str, end, nmodes, amp);
-}
-
-// Modes computed elsewhere (the reference's fRe / fIm files, a coarser DNS; fourier_reconstruction, core/fourier.f:2-21):
-// A[0..nmodes], B[0..nmodes-1] = B_1.. are state vectors whose velocity components are taken.  dt / nsteps: the rule of
-// nsk_set_baseflow applied to U(0) = sum_k A_k with `endtime` as set; `period` is the orbit's T and need not equal endtime.
-int nsk_set_orbit_modes(nsk_ctx* c, int nmodes, double period, const nsk_vec* A, const nsk_vec* B) {
-  if (!c || !A || nmodes < 0 || (nmodes > 0 && !B)) return fail(NSK_EINVAL, "bad argument");
-  { const int rc = forb_refuse(c, "nsk_set_orbit_modes"); if (rc) return rc; }
-  if (!(period > 0.0)) return fail(NSK_EINVAL, "nsk_set_orbit_modes: period must be positive");
-  for (int k = 0; k <= nmodes; ++k) if (!A[k] || (k < nmodes && !B[k])) return fail(NSK_EINVAL, "nsk_set_orbit_modes: null mode vector");
-  const long long nv = (long long)c->ndim * c->nloc;
-  // the modes first (A or B may be the vectors nsk_get_orbit_modes filled from the arrays replaced here: staged through a new array)
-  double* fresh = nullptr;
-  int rc = dalloc(c, &fresh, (size_t)(2 * nmodes + 1) * nv);
-  if (rc) return rc;
-  for (int k = 0; k <= nmodes; ++k) {
-    HIPCHK(hipMemcpyAsync(fresh + (size_t)(k ? 2 * k - 1 : 0) * nv, A[k], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    if (k) HIPCHK(hipMemcpyAsync(fresh + (size_t)(2 * k) * nv, B[k - 1], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  HIPCHK(hipMemsetAsync(c->scratch, 0, c->nstate * sizeof(double), c->stream));
-  for (int k = 0; k <= nmodes; ++k)                             // U(0) = sum_k A_k
-    hipLaunchKernelGGL(k_axpby, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, c->scratch, 1.0, (const double*)A[k], 1.0, nv);
-  steady_back(c);                                               // back to the steady arrays first (as nsk_set_orbit)
-  if ((rc = nsk_set_baseflow(c, c->scratch))) { nsk_vec v = fresh; nsk_vec_free(c, 1, &v); return rc; }
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->forb_modes) { nsk_vec v = c->forb_modes; nsk_vec_free(c, 1, &v); }
-  c->forb_modes = fresh; c->forb_modes_cap = (size_t)(2 * nmodes + 1) * nv;
-  return forb_activate(c, nmodes, period, nullptr);
 }
 
 // The modes of the active Fourier orbit into state vectors (velocity components; the rest is zeroed).  A, B NULL: count and period only.
@@ -3405,11 +3167,7 @@ int nsk_get_orbit_modes(nsk_ctx* c, int* nmodes, double* period, nsk_vec* A, nsk
 
 // ---- the Fourier form on element shards: every rank keeps the modes of its own elements, [2M+1][ndim][nloc of the shard], and
 // its own table of cos / sin factors (group_run_map); group_step reconstructs per rank in front of the convection kernel.
-static void shard_steady_back(nsk_ctx* c) {                     // steady_back, and the captured graphs read the old pointers
-  if (!c->d.bf_stride) return;
-  steady_back(c);
-  invalidate_graphs(c);
-}
+
 // amp[0 .. 2M] = bm1s-weighted L2 norms of A_0, A_1, B_1, .. over ALL ranks: per rank one pass of k_mode_norm2 over its mode
 // arrays and the fixed-order row totals, then the squares are added over the ranks (virtual ranks: on the host in rank order;
 // a transport: nsk_allreduce_host) -- every rank gets the same values, no mode leaves the device
@@ -3434,69 +3192,188 @@ static int group_mode_amp(std::vector<nsk_ctx*>& G, int M, double* amp) {
   return 0;
 }
 
-// nsk_set_orbit_fourier for the ranks of this process: the integration of nsk_group_set_orbit, every rank adding its own
-// elements' field into its own mode arrays in front of every step (k_orbit_dft reads the stepper's field with its stride cs:
-// no scratch copy, no snapshot, no per-step constants).
+// a stored orbit ends: the base-flow pointers go back to the steady arrays (the captured graphs read the old ones)
+static void steady_back(nsk_ctx* c) {
+  Dev& d = c->d;
+  if (!d.bf_stride) return;
+  if (c->ndim == 3) { d.bfc = c->steady[0]; d.cUr = c->steady[0]; }
+  else { d.cUr = c->steady[0]; d.cUs = c->steady[1]; d.GUx = c->steady[2]; d.GUy = c->steady[3]; d.GVx = c->steady[4]; d.GVy = c->steady[5]; }
+  d.bf_stride = 0;
+  invalidate_graphs(c);
+}
+
+// Time-periodic base flow for Floquet analysis (uparam(1)=3.11, core/matvec.f:191-236, core/eigensolvers.f:201-210):
+// integrate the full equations from q0 over one period T = endtime (DNS sponge towards the initial field with
+// strength spng_str, core/utils.f:165-170) and store the base-flow constants of every step; the linearised
+// maps then read slot istep-1 at step istep.  Returns Phi_T(q0) in `end` (periodicity check) where not NULL.
+// nmodes >= 0 (the Fourier form): the same integration, but every step's field is added into the lowest nmodes temporal
+// Fourier modes (k_orbit_dft reads the stepper's field with its stride cs) instead of its constants being stored.
+// One body for a full-mesh context (a group of one, sharded = false) and for the ranks of one process, each storing the
+// constants / modes of its own elements.  Quadrilaterals: six arrays of nel*lxd^2 per step; hexahedra: one array of
+// 12*nel*lxd^3 per step behind Dev::bfc (= cUr).
+static int orbit_integrate(std::vector<nsk_ctx*>& G, bool sharded, const double* const* q0, double spng_str, double* const* end, int nmodes, double* amp) {
+  const bool four = nmodes >= 0;
+  const int nd = G[0]->ndim, narr = nd == 3 ? 1 : 6, nm = 2 * nmodes + 1;
+  auto per_step = [nd](const nsk_ctx* c) { return nd == 3 ? 12 * c->d.nfine : (long long)c->nel * c->NDD; };
+  int rc;
+  for (nsk_ctx* c : G) steady_back(c);                          // back to the steady arrays first
+  if ((rc = set_baseflow_body(G, sharded, q0))) return rc;      // dt, nsteps from the CFL of the initial field (all ranks)
+  const int nsteps = G[0]->nsteps;
+  if (four && nmodes > nsteps / 2)
+    return fail(NSK_EINVAL, std::string(sharded ? "nsk_group_set_orbit_fourier" : "nsk_set_orbit_fourier") + ": nmodes must be in 0 .. nsteps / 2 (" + std::to_string(nsteps / 2) + ")");
+  const std::vector<double> w = four ? forb_dft_rows(nsteps, nmodes) : std::vector<double>();
+  std::vector<DevTmp> dftw;                                     // per rank: [nsteps][nm] coefficient rows of k_orbit_dft (Fourier form)
+  dftw.reserve(G.size());
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r]; Dev& d = c->d;
+    dftw.emplace_back(c);
+    for (int k = 0; k < narr; ++k) {
+      if (c->orbit[k]) { nsk_vec v = c->orbit[k]; nsk_vec_free(c, 1, &v); c->orbit[k] = nullptr; }
+      if (!four && (rc = dalloc(c, &c->orbit[k], (size_t)nsteps * per_step(c)))) return rc;
+    }
+    if (four) {
+      c->orbit_steps = 0;
+      if ((rc = forb_alloc(c, nmodes)) || (rc = dalloc(c, &dftw[r].p, w.size()))) return rc;
+      HIPCHK(hipMemcpy(dftw[r].p, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    double* vr = const_cast<double*>(d.spng_vr);                // one buffer per context: Newton calls this every iteration
+    if (!vr && (rc = dalloc(c, &vr, nd * d.cs))) return rc;
+    for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(vr + cc * d.cs, q0[r] + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    d.spng_vr = vr; d.nl_spng_str = spng_str;
+    if (!d.bstep && (rc = dalloc(c, &d.bstep, 4))) return rc;
+    invalidate_graphs(c);
+    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
+    c->bh_n = 0;
+    HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
+    if ((rc = state_load(c, q0[r]))) return rc;
+  }
+  for (int istep = 1; istep <= nsteps; ++istep) {
+    for (size_t r = 0; r < G.size(); ++r) {
+      nsk_ctx* c = G[r]; Dev& d = c->d;
+      if (four) {
+        const long long nv = (long long)nd * d.nloc;
+        hipLaunchKernelGGL(k_orbit_dft, dim3((unsigned)std::min<long long>((nv + 255) / 256, 4096)), dim3(256), 0, c->stream, c->forb_modes, (const double*)d.u,
+                           (const double*)(dftw[r].p + (size_t)(istep - 1) * nm), nm, d.nloc, d.cs, nd);
+        continue;
+      }
+      // k_baseflow reads a state vector (component stride nloc): the stepper's field itself, or a copy where it has ghost slots (cs > nloc)
+      const double* u = d.u;
+      if (d.cs != d.nloc) {
+        for (int cc = 0; cc < nd; ++cc)
+          HIPCHK(hipMemcpyAsync(c->scratch + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        u = c->scratch;
+      }
+      double* to[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+      for (int k = 0; k < narr; ++k) to[k] = c->orbit[k] + (size_t)(istep - 1) * per_step(c);
+      if ((rc = launch_baseflow(c, u, to))) return rc;
+    }
+    if ((rc = sharded ? group_step(G, istep, 2) : step(G[0], istep, 2))) return rc;
+  }
+  Stats h;
+  HIPCHK(hipMemcpyAsync(&h, G[0]->d.stats, sizeof(Stats), hipMemcpyDeviceToHost, G[0]->stream));
+  for (size_t r = 0; r < G.size(); ++r)
+    if (end && end[r] && (rc = state_store(G[r], end[r]))) return rc;
+  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
+  if (h.unconverged > 0) return fail(NSK_ENOCONV, std::string("inner solve hit its iteration cap while integrating the base-flow orbit") + (sharded ? " (sharded)" : ""));
+  if (four) {
+    // the amplitudes are summed on the host for a full-mesh context and per rank on the device for shards: two orders, two sets of bits
+    for (nsk_ctx* c : G) if ((rc = forb_activate(c, nmodes, c->endtime, sharded ? nullptr : amp))) return rc;
+    return sharded && amp ? group_mode_amp(G, nmodes, amp) : 0;
+  }
+  for (nsk_ctx* c : G) {
+    Dev& d = c->d;
+    if (nd == 3) {
+      c->steady[0] = d.bfc;
+      d.bfc = c->orbit[0]; d.cUr = c->orbit[0]; d.bfmask = 0;
+    } else {
+      c->steady[0] = d.cUr; c->steady[1] = d.cUs; c->steady[2] = d.GUx; c->steady[3] = d.GUy; c->steady[4] = d.GVx; c->steady[5] = d.GVy;
+      d.cUr = c->orbit[0]; d.cUs = c->orbit[1]; d.GUx = c->orbit[2]; d.GUy = c->orbit[3]; d.GVx = c->orbit[4]; d.GVy = c->orbit[5];
+    }
+    d.bf_stride = per_step(c); c->orbit_steps = nsteps;
+    invalidate_graphs(c);
+  }
+  return 0;
+}
+int nsk_set_orbit(nsk_ctx* c, nsk_vec q0v, double spng_str, nsk_vec end) {
+  if (!c || !q0v) return fail(NSK_EINVAL, "bad argument");
+  if (c->parent) return fail(NSK_EINVAL, "shards: use nsk_group_set_orbit");
+  if (c->clone_of) return fail(NSK_EINVAL, "not on a lane (nsk_clone)");
+  std::vector<nsk_ctx*> G(1, c);
+  const double* q0 = (const double*)q0v; double* e = (double*)end;
+  return orbit_integrate(G, false, &q0, spng_str, &e, -1, nullptr);
+}
+int nsk_group_set_orbit(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, nsk_vec* end) {
+  if (!shards || n < 1 || !q0) return fail(NSK_EINVAL, "bad argument");
+  std::vector<nsk_ctx*> G(shards, shards + n);
+  for (int r = 0; r < n; ++r)
+    if (!G[r] || !q0[r] || !G[r]->parent) return fail(NSK_EINVAL, "needs shard contexts");
+  return orbit_integrate(G, true, (const double* const*)q0, spng_str, (double* const*)end, -1, nullptr);
+}
+
+// The orbit of nsk_set_orbit kept as its lowest nmodes temporal harmonics (fourier_decomposition, core/fourier.f:23-88):
+// (2 nmodes + 1) ndim nloc doubles on the device whatever the number of steps; period T = endtime.
+int nsk_set_orbit_fourier(nsk_ctx* c, nsk_vec q0v, double spng_str, int nmodes, nsk_vec end, double* amp) {
+  if (!c || !q0v) return fail(NSK_EINVAL, "bad argument");
+  { const int rc = forb_refuse(c, "nsk_set_orbit_fourier"); if (rc) return rc; }
+  if (nmodes < 0) return fail(NSK_EINVAL, "nsk_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2");
+  std::vector<nsk_ctx*> G(1, c);
+  const double* q0 = (const double*)q0v; double* e = (double*)end;
+  return orbit_integrate(G, false, &q0, spng_str, &e, nmodes, amp);
+}
 int nsk_group_set_orbit_fourier(nsk_ctx** shards, int n, nsk_vec* q0, double spng_str, int nmodes, nsk_vec* end, double* amp) {
   if (!shards || n < 1 || !q0) return fail(NSK_EINVAL, "bad argument");
   std::vector<nsk_ctx*> G(shards, shards + n);
   for (int r = 0; r < n; ++r)
     if (!G[r] || !q0[r] || !G[r]->parent) return fail(NSK_EINVAL, "needs shard contexts");
   if (nmodes < 0) return fail(NSK_EINVAL, "nsk_group_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2");
-  const int nd = G[0]->ndim, nm = 2 * nmodes + 1;
-  int rc;
-  for (nsk_ctx* c : G) shard_steady_back(c);
-  if ((rc = group_set_baseflow(G, (const double* const*)q0))) return rc;          // dt, nsteps: CFL maximum over all ranks
-  const int nsteps = G[0]->nsteps;
-  if (nmodes > nsteps / 2) return fail(NSK_EINVAL, "nsk_group_set_orbit_fourier: nmodes must be in 0 .. nsteps / 2 (" + std::to_string(nsteps / 2) + ")");
-  const std::vector<double> w = forb_dft_rows(nsteps, nmodes);
-  std::vector<double*> dftw(G.size(), nullptr);                 // per rank: [nsteps][nm] coefficient rows of k_orbit_dft
-  auto four_end = [&]() {
-    for (size_t r = 0; r < G.size(); ++r) if (dftw[r]) { nsk_vec v = dftw[r]; nsk_vec_free(G[r], 1, &v); dftw[r] = nullptr; }
-  };
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r]; Dev& d = c->d;
-    for (int k = 0; k < 6; ++k) if (c->orbit[k]) { nsk_vec v = c->orbit[k]; nsk_vec_free(c, 1, &v); c->orbit[k] = nullptr; }
-    c->orbit_steps = 0;
-    if ((rc = forb_alloc(c, nmodes)) || (rc = dalloc(c, &dftw[r], w.size()))) { four_end(); return rc; }
-    HIPCHK(hipMemcpy(dftw[r], w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
-    double* vr = const_cast<double*>(d.spng_vr);
-    if (!vr && (rc = dalloc(c, &vr, nd * d.cs))) { four_end(); return rc; }
-    const double* q = (const double*)q0[r];
-    for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(vr + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    d.spng_vr = vr; d.nl_spng_str = spng_str;
-    if (!d.bstep && (rc = dalloc(c, &d.bstep, 4))) { four_end(); return rc; }
-    HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
-    for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d.p, q + nd * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
-  for (int istep = 1; istep <= nsteps; ++istep) {
-    for (size_t r = 0; r < G.size(); ++r) {
-      nsk_ctx* c = G[r]; Dev& d = c->d;
-      const long long nv = (long long)nd * d.nloc;
-      hipLaunchKernelGGL(k_orbit_dft, dim3((unsigned)std::min<long long>((nv + 255) / 256, 4096)), dim3(256), 0, c->stream, c->forb_modes, (const double*)d.u,
-                         (const double*)(dftw[r] + (size_t)(istep - 1) * nm), nm, d.nloc, d.cs, nd);
-    }
-    if ((rc = group_step(G, istep, 2))) { four_end(); return rc; }
-  }
-  Stats h;
-  HIPCHK(hipMemcpyAsync(&h, G[0]->d.stats, sizeof(Stats), hipMemcpyDeviceToHost, G[0]->stream));
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r]; Dev& d = c->d;
-    if (end && end[r]) {
-      double* f = (double*)end[r];
-      for (int cc = 0; cc < nd; ++cc) HIPCHK(hipMemcpyAsync(f + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(f + nd * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-  }
-  for (nsk_ctx* c : G) HIPCHK(hipStreamSynchronize(c->stream));
-  four_end();
-  if (h.unconverged > 0) return fail(NSK_ENOCONV, "inner solve hit its iteration cap while integrating the base-flow orbit (sharded)");
-  for (nsk_ctx* c : G) if ((rc = forb_activate(c, nmodes, c->endtime, nullptr))) return rc;
-  return amp ? group_mode_amp(G, nmodes, amp) : 0;
+  return orbit_integrate(G, true, (const double* const*)q0, spng_str, (double* const*)end, nmodes, amp);
 }
 
-// nsk_set_orbit_modes for the ranks of this process; A, B rank-major: A[r * (nmodes + 1) + k], B[r * nmodes + k - 1]
+// Modes computed elsewhere (the reference's fRe / fIm files, a coarser DNS; fourier_reconstruction, core/fourier.f:2-21):
+// A[0..nmodes], B[0..nmodes-1] = B_1.. are state vectors whose velocity components are taken; rank-major for the ranks of one
+// process, A[r * (nmodes + 1) + k], B[r * nmodes + k - 1] (one rank: the layout of nsk_set_orbit_modes).  dt / nsteps: the rule
+// of nsk_set_baseflow applied to U(0) = sum_k A_k with `endtime` as set; `period` is the orbit's T and need not equal endtime.
+static int set_orbit_modes_body(std::vector<nsk_ctx*>& G, bool sharded, int nmodes, double period, const nsk_vec* A, const nsk_vec* B) {
+  // the modes first (A or B may be the vectors nsk_get_orbit_modes filled from the arrays replaced here: staged through new arrays)
+  std::vector<DevTmp> fresh;
+  fresh.reserve(G.size());
+  std::vector<const double*> u0(G.size());
+  int rc;
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r];
+    const long long nv = (long long)c->ndim * c->nloc;
+    const nsk_vec* Ar = A + r * (nmodes + 1);
+    const nsk_vec* Br = nmodes ? B + r * nmodes : nullptr;
+    fresh.emplace_back(c);
+    if ((rc = dalloc(c, &fresh[r].p, (size_t)(2 * nmodes + 1) * nv))) return rc;
+    for (int k = 0; k <= nmodes; ++k) {
+      HIPCHK(hipMemcpyAsync(fresh[r].p + (size_t)(k ? 2 * k - 1 : 0) * nv, Ar[k], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      if (k) HIPCHK(hipMemcpyAsync(fresh[r].p + (size_t)(2 * k) * nv, Br[k - 1], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIPCHK(hipMemsetAsync(c->scratch, 0, c->nstate * sizeof(double), c->stream));
+    for (int k = 0; k <= nmodes; ++k)                           // U(0) = sum_k A_k
+      hipLaunchKernelGGL(k_axpby, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, c->scratch, 1.0, (const double*)Ar[k], 1.0, nv);
+    u0[r] = c->scratch;
+  }
+  for (nsk_ctx* c : G) steady_back(c);                          // back to the steady arrays first (as nsk_set_orbit)
+  if ((rc = set_baseflow_body(G, sharded, u0.data()))) return rc;                 // dt, nsteps: CFL maximum over all ranks
+  for (size_t r = 0; r < G.size(); ++r) {
+    nsk_ctx* c = G[r];
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->forb_modes) { nsk_vec v = c->forb_modes; nsk_vec_free(c, 1, &v); }
+    c->forb_modes = fresh[r].release(); c->forb_modes_cap = (size_t)(2 * nmodes + 1) * (size_t)c->ndim * (size_t)c->nloc;
+    if ((rc = forb_activate(c, nmodes, period, nullptr))) return rc;
+  }
+  return 0;
+}
+int nsk_set_orbit_modes(nsk_ctx* c, int nmodes, double period, const nsk_vec* A, const nsk_vec* B) {
+  if (!c || !A || nmodes < 0 || (nmodes > 0 && !B)) return fail(NSK_EINVAL, "bad argument");
+  { const int rc = forb_refuse(c, "nsk_set_orbit_modes"); if (rc) return rc; }
+  if (!(period > 0.0)) return fail(NSK_EINVAL, "nsk_set_orbit_modes: period must be positive");
+  for (int k = 0; k <= nmodes; ++k) if (!A[k] || (k < nmodes && !B[k])) return fail(NSK_EINVAL, "nsk_set_orbit_modes: null mode vector");
+  std::vector<nsk_ctx*> G(1, c);
+  return set_orbit_modes_body(G, false, nmodes, period, A, B);
+}
 int nsk_group_set_orbit_modes(nsk_ctx** shards, int n, int nmodes, double period, const nsk_vec* A, const nsk_vec* B) {
   if (!shards || n < 1 || !A || nmodes < 0 || (nmodes > 0 && !B)) return fail(NSK_EINVAL, "bad argument");
   std::vector<nsk_ctx*> G(shards, shards + n);
@@ -3505,37 +3382,7 @@ int nsk_group_set_orbit_modes(nsk_ctx** shards, int n, int nmodes, double period
   for (int r = 0; r < n; ++r)
     for (int k = 0; k <= nmodes; ++k)
       if (!A[(size_t)r * (nmodes + 1) + k] || (k < nmodes && !B[(size_t)r * nmodes + k])) return fail(NSK_EINVAL, "nsk_group_set_orbit_modes: null mode vector");
-  // the modes first (A or B may be the vectors nsk_group_get_orbit_modes filled from the arrays replaced here: staged through new arrays)
-  std::vector<double*> fresh(G.size(), nullptr);
-  auto drop = [&]() { for (size_t r = 0; r < G.size(); ++r) if (fresh[r]) { nsk_vec v = fresh[r]; nsk_vec_free(G[r], 1, &v); fresh[r] = nullptr; } };
-  std::vector<const double*> u0(G.size());
-  int rc;
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r];
-    const long long nv = (long long)c->ndim * c->nloc;
-    const nsk_vec* Ar = A + r * (nmodes + 1);
-    const nsk_vec* Br = nmodes ? B + r * nmodes : nullptr;
-    if ((rc = dalloc(c, &fresh[r], (size_t)(2 * nmodes + 1) * nv))) { drop(); return rc; }
-    for (int k = 0; k <= nmodes; ++k) {
-      HIPCHK(hipMemcpyAsync(fresh[r] + (size_t)(k ? 2 * k - 1 : 0) * nv, Ar[k], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      if (k) HIPCHK(hipMemcpyAsync(fresh[r] + (size_t)(2 * k) * nv, Br[k - 1], nv * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    HIPCHK(hipMemsetAsync(c->scratch, 0, c->nstate * sizeof(double), c->stream));
-    for (int k = 0; k <= nmodes; ++k)                           // U(0) = sum_k A_k
-      hipLaunchKernelGGL(k_axpby, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, c->stream, c->scratch, 1.0, (const double*)Ar[k], 1.0, nv);
-    u0[r] = c->scratch;
-  }
-  for (nsk_ctx* c : G) shard_steady_back(c);
-  if ((rc = group_set_baseflow(G, u0.data()))) { drop(); return rc; }             // dt, nsteps: CFL maximum over all ranks
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r];
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->forb_modes) { nsk_vec v = c->forb_modes; nsk_vec_free(c, 1, &v); }
-    c->forb_modes = fresh[r]; c->forb_modes_cap = (size_t)(2 * nmodes + 1) * (size_t)c->ndim * (size_t)c->nloc;
-    fresh[r] = nullptr;
-    if ((rc = forb_activate(c, nmodes, period, nullptr))) { drop(); return rc; }
-  }
-  return 0;
+  return set_orbit_modes_body(G, true, nmodes, period, A, B);
 }
 
 // nsk_get_orbit_modes per rank; A, B rank-major as above, or both NULL: count and period only
@@ -4189,23 +4036,10 @@ int nsk_group_forced_map(nsk_ctx** shards, int n, int mode, nsk_vec* f, nsk_vec*
     if (force[r] == f[r]) return fail(NSK_EINVAL, "nsk_group_forced_map: the force may not be the output vector");
   }
   std::vector<nsk_ctx*> G(shards, shards + n);
-  struct Keep { int use_graph, freeze, helm[NCLS], pres[NCLS]; };
-  std::vector<Keep> keep(n);
-  for (int r = 0; r < n; ++r) {
-    nsk_ctx* c = G[r];
-    keep[r].use_graph = c->use_graph; keep[r].freeze = c->budget_freeze;
-    for (int k = 0; k < NCLS; ++k) { keep[r].helm[k] = c->cur_helm[k]; keep[r].pres[k] = c->cur_pres[k]; }
-    c->force = (const double*)force[r];
-    c->use_graph = 0;                                            // group_graph_ok: eager
-    c->budget_freeze = 1;                                        // (a forced map that outgrows the budgets doubles them for its redo; put back below)
-  }
+  EagerRun eager(G);
+  for (int r = 0; r < n; ++r) G[r]->force = (const double*)force[r];
   rc = group_run_map(G, mode == NSK_ADJOINT ? 1 : 0, (double* const*)f, (const double* const*)q);
-  for (int r = 0; r < n; ++r) {
-    nsk_ctx* c = G[r];
-    c->force = nullptr;
-    c->use_graph = keep[r].use_graph; c->budget_freeze = keep[r].freeze;
-    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
-  }
+  for (nsk_ctx* c : G) c->force = nullptr;
   return rc;
 }
 
@@ -4237,28 +4071,21 @@ static int sfd_map(std::vector<nsk_ctx*>& G, const char* who, bool group, nsk_ve
       c->sfd_hist_cap = ns;
     }
   }
-  struct Keep { int use_graph, freeze, helm[NCLS], pres[NCLS]; };
-  std::vector<Keep> keep(n);
+  EagerRun eager(G);
   for (int r = 0; r < n; ++r) {
     nsk_ctx* c = G[r];
-    keep[r].use_graph = c->use_graph; keep[r].freeze = c->budget_freeze;
-    for (int k = 0; k < NCLS; ++k) { keep[r].helm[k] = c->cur_helm[k]; keep[r].pres[k] = c->cur_pres[k]; }
     c->sfd.on = true; c->sfd.q0 = (const double*)qbar[r]; c->sfd.qw = (double*)f[r]; c->sfd.chi = chi; c->sfd.omega_c = omega_c;
-    c->use_graph = 0;
-    c->budget_freeze = 1;
     // an SFD map that outran the budgets was redone with doubled ones: the SFD maps that follow start from those (a run is a
     // chain of hundreds of maps), the unforced maps get theirs back below
     for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = std::max(c->cur_helm[k], c->sfd_helm[k]); c->cur_pres[k] = std::max(c->cur_pres[k], c->sfd_pres[k]); }
   }
   if (group) rc = group_run_map(G, 2, (double* const*)f, (const double* const*)q);
   else { G[0]->hstats = Stats{}; rc = run_map_adaptive(G[0], 2, (double*)f[0], (const double*)q[0]); }
-  for (int r = 0; r < n; ++r) {
-    nsk_ctx* c = G[r];
+  for (nsk_ctx* c : G) {
     c->sfd = nsk_ctx::SfdRun{};
-    c->use_graph = keep[r].use_graph; c->budget_freeze = keep[r].freeze;
     for (int k = 0; k < NCLS; ++k) { c->sfd_helm[k] = c->cur_helm[k]; c->sfd_pres[k] = c->cur_pres[k]; }
-    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
   }
+  eager.restore();
   if (rc) return rc;
   std::vector<double> loc((size_t)n * ns, 0.0);
   for (int r = 0; r < n; ++r) {
@@ -4359,30 +4186,22 @@ static int bcv_map(std::vector<nsk_ctx*>& G, const char* who, bool group, nsk_ve
     HIPCHK(hipMemcpyAsync(c->bcv_save + nx, c->bcv_Y, nx * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(c->bcv_save + 2 * nx, c->bcv_small, nsm * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   }
-  struct Keep { int use_graph, freeze, helm[NCLS], pres[NCLS]; };
-  std::vector<Keep> keep(n);
-  for (int r = 0; r < n; ++r) {
-    nsk_ctx* c = G[r];
-    keep[r].use_graph = c->use_graph; keep[r].freeze = c->budget_freeze;
-    for (int k = 0; k < NCLS; ++k) { keep[r].helm[k] = c->cur_helm[k]; keep[r].pres[k] = c->cur_pres[k]; }
+  EagerRun eager(G);
+  for (nsk_ctx* c : G) {
     c->bcv = nsk_ctx::BcvRun{};
     c->bcv.on = true; c->bcv.skip = skip; c->bcv.step0 = step0;
     c->bcv_count0 = c->bcv_count; c->bcv_rot0 = c->bcv_rot;
-    c->use_graph = 0;
-    c->budget_freeze = 1;
     for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = std::max(c->cur_helm[k], c->bcv_helm[k]); c->cur_pres[k] = std::max(c->cur_pres[k], c->bcv_pres[k]); }
   }
   if (group) rc = group_run_map(G, 2, (double* const*)f, (const double* const*)q);
   else { G[0]->hstats = Stats{}; rc = run_map_adaptive(G[0], 2, (double*)f[0], (const double*)q[0]); }
   const int nc = G[0]->bcv.ncall;
-  for (int r = 0; r < n; ++r) {
-    nsk_ctx* c = G[r];
+  for (nsk_ctx* c : G) {
     if (rc) (void)bcv_restore(c);
     c->bcv = nsk_ctx::BcvRun{};
-    c->use_graph = keep[r].use_graph; c->budget_freeze = keep[r].freeze;
     for (int k = 0; k < NCLS; ++k) { c->bcv_helm[k] = c->cur_helm[k]; c->bcv_pres[k] = c->cur_pres[k]; }
-    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
   }
+  eager.restore();
   if (rc) return rc;
   if (ncalls) *ncalls = nc;
   // (every rank solved the same system from the same totals: the history of the first one is everybody's)

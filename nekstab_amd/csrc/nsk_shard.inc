@@ -812,9 +812,7 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
       nsk_ctx* c = G[r];
       Dev& d = c->d;
       HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
-      for (int cc = 0; cc < c->ndim; ++cc)
-        HIPCHK(hipMemcpyAsync(d.u + cc * d.cs, q[r] + cc * d.nloc, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      HIPCHK(hipMemcpyAsync(d.p, q[r] + c->ndim * d.nloc, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      { int rc = state_load(c, q[r]); if (rc) return rc; }
       if (d.bf_stride || d.forb) {                           // time-periodic base flow: step counter of the stored orbit / row of the trig table
         if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
         HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
@@ -879,13 +877,7 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
     }
     if (!grow) break;
   }
-  for (size_t r = 0; r < G.size(); ++r) {
-    nsk_ctx* c = G[r];
-    Dev& d = c->d;
-    for (int cc = 0; cc < c->ndim; ++cc)
-      HIPCHK(hipMemcpyAsync(f[r] + cc * d.nloc, d.u + cc * d.cs, d.nloc * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(f[r] + c->ndim * d.nloc, d.p, d.npr * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-  }
+  for (size_t r = 0; r < G.size(); ++r) { int rc = state_store(G[r], f[r]); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(G[0]->stream));
   return 0;
 }
