@@ -38,6 +38,7 @@ module nekstab_hip
     integer(c_long_long) :: absorb_maps
     integer(c_long_long) :: convfuse_steps
     integer(c_long_long) :: helmpack_steps
+    integer(c_long_long) :: leanargs_steps
   end type
 
   interface

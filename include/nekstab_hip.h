@@ -406,6 +406,9 @@ typedef struct {
   long long helmpack_steps;                 /* time steps since init whose velocity solve ran on the packed scratch arrays (option "helm_pack": 16-byte
                                                accesses in k_helm / k_helm_tail / k_pres_rhs; a redone map counts again).  0 wherever the option does not
                                                apply: hexahedra, shards, the persistent velocity solve, and lx1 = 12 unless the option is 1 */
+  long long leanargs_steps;                 /* time steps since init whose iteration kernels (k_helm, k_schwarz_uc, k_divgs_t) took their arguments as compact
+                                               blocks (option "lean_args"; a redone map counts again).  0 wherever the option does not apply: hexahedra,
+                                               shards, the persistent velocity solve */
 } nsk_stats;
 int nsk_get_stats(nsk_ctx* ctx, nsk_stats* s);
 

@@ -103,6 +103,42 @@ template <int N> static auto pick_pres_tail(int nit, bool cm) {
 template <int N> static auto pick_pres_tail2(int nit, bool cm) {
   return with_nit(nit, [&](auto NIT) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_pres_tail2<N, decltype(NIT)::value, decltype(CM)::value>; }); });
 }
+// option "lean_args": the wrappers of the same bodies on the compact argument blocks (nsk_dev.hpp), and what fills a block from Dev
+template <int N> static auto pick_helm_lean(bool pk, bool cm) {
+  return with_bool(pk, [&](auto PK) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_helm_l<N, decltype(PK)::value, decltype(CM)::value>; }); });
+}
+template <int N> static auto pick_divgs_t_lean(bool t32, bool cm) {
+  return with_bool(t32, [&](auto T32) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_divgs_t_l<N, decltype(T32)::value, decltype(CM)::value>; }); });
+}
+template <int N> static auto pick_schwarz_uc_lean(int nit) { return with_nit(nit, [](auto NIT) { return &nsk::k2::k_schwarz_uc_l<N, decltype(NIT)::value>; }); }
+static nsk::HelmRest helm_rest(const nsk::Dev& d, const nsk::StepCoef& sc, const double* rhs) {
+  nsk::HelmRest r{};
+  r.bm1 = d.bm1; r.g1 = d.g1; r.g2 = d.g2; r.g4 = d.g4; r.mask = d.mask; r.minv = d.minv; r.dinv = d.dinv; r.D = d.D;
+  r.hr = d.hr; r.hp = d.hp; r.hs = d.hs; r.hx = d.hx; r.hwl = d.hwl; r.hpart = d.hpart; r.htot = d.htot; r.bloc = d.bloc;
+  r.rhs = rhs; r.gs_off = d.gs_off; r.gs_idx = d.gs_idx; r.stats = d.stats; r.stepctr = d.stepctr; r.step_iters = d.step_iters; r.dbg = d.dbg;
+  r.cs = d.cs; r.nloc = d.nloc; r.nu = d.nu; r.vol = d.vol; r.tol_helm = d.tol_helm;
+  r.sc.h2 = sc.h2; r.sc.k = sc.k; r.sc.cls = sc.cls;
+  r.nblk = d.nblk; r.nranks = d.nranks; r.use_tot = d.use_tot; r.tol_relative = d.tol_relative; r.step_cap = d.step_cap;
+  return r;
+}
+static nsk::UcRest uc_rest(const nsk::Dev& d, double scale, int min_iter, int ord) {
+  nsk::UcRest r{};
+  r.J12 = d.J12; r.D12 = d.D12; r.w2rx = d.w2rx; r.w2sx = d.w2sx; r.w2ry = d.w2ry; r.w2sy = d.w2sy;
+  r.Wr = d.Wr; r.V = d.V; r.Z = d.Z; r.yl = d.yl; r.rch = d.rch; r.ecv = d.ecv; r.xc = d.xc; r.p_inv = d.p_inv; r.Acif = d.Acif;
+  r.ps = d.ps; r.npr = d.npr; r.cs = d.cs; r.nvert = d.nvert; r.coarse_lda = d.coarse_lda;
+  r.tol_pres = d.tol_pres; r.tol_pres_floor = d.tol_pres_floor; r.scale = scale;
+  r.tol_relative = d.tol_relative; r.pres_cap = d.pres_cap; r.nproj_max = d.nproj_max; r.min_iter = min_iter; r.ord = ord; r.step_cap = d.step_cap;
+  r.stats = d.stats; r.stepctr = d.stepctr; r.step_iters = d.step_iters; r.dbg = d.dbg;
+  return r;
+}
+static nsk::DivgsRest divgs_rest(const nsk::Dev& d) {
+  nsk::DivgsRest r{};
+  r.binv = d.binv; r.w2rx = d.w2rx; r.w2sx = d.w2sx; r.w2ry = d.w2ry; r.w2sy = d.w2sy; r.Tc = d.Tc; r.J12 = d.J12; r.D12 = d.D12; r.hat = d.hat;
+  r.Tc32 = d.Tc32; r.ecslot = d.ecslot; r.evl = d.evl; r.evert = d.evert; r.gs_off = d.gs_off; r.gs_idx = d.gs_idx;
+  r.Z = d.Z; r.V = d.V; r.yl = d.yl; r.xc = d.xc; r.Wr = d.Wr; r.ec = d.ec; r.ecv = d.ecv; r.gpart = d.gpart; r.dbg = d.dbg;
+  r.nloc = d.nloc; r.npr = d.npr; r.ps = d.ps; r.cs = d.cs; r.nblk = d.nblk;
+  return r;
+}
 template <int N> static auto pick_schwarz_uc(int nit) { return with_nit(nit, [](auto NIT) { return &nsk::k2::k_schwarz_uc<N, decltype(NIT)::value>; }); }
 static auto pick_update_coarse(int nit) { return with_nit(nit, [](auto NIT) { return &nsk::k_update_coarse<decltype(NIT)::value>; }); }
 template <int N> static auto pick_divgs(bool cm) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_divgs<N, decltype(CM)::value>; }); }
@@ -212,6 +248,8 @@ struct nsk_ctx {
   long long tail_maps = 0;
   long long absorb_maps = 0;             // maps run with the deferred update of the projection space (option "proj_absorb")
   long long helmpack_steps = 0;          // time steps whose velocity solve ran on the packed scratch arrays (option "helm_pack")
+  long long leanargs_steps = 0;          // time steps whose iteration kernels took the compact argument blocks (option "lean_args")
+  int lean_args = -1;                   // k_helm, k_schwarz_uc and k_divgs_t on compact argument blocks (k_helm_l, k_schwarz_uc_l, k_divgs_t_l; nsk_dev.hpp) instead of Dev by value: -1 = where allowed (leanargs_on), 0 = never, 1 = the same as -1 (every other context ignores it); option "lean_args"
   int helm_pack = -1;                   // 16-byte accesses in the quadrilateral velocity solve (k_helm<N, true>, k_helm_tail<N, true>, k_pres_rhs<N, .., true>): -1 = where allowed and where it pays (helmpack_on: lx1 <= 10), 0 = never, 1 = wherever allowed; option "helm_pack"
   long long convfuse_steps = 0;          // time steps run with convection and the velocity right-hand side in one launch (option "conv_fuse")
   long long sb_maps = 0, sb_steps = 0, sb_launch_h = 0, sb_launch_p = 0;     // maps / time steps run on per-step budgets and their budgeted launches (diagnostics)
@@ -1180,6 +1218,12 @@ static void launch_update_coarse(nsk_ctx* c, const Dev& d, int j, double scale, 
   hipLaunchKernelGGL(pick_update_coarse(d.coarse_lda / 256), dim3(cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord);
 }
 
+// The iteration kernels on compact argument blocks (option "lean_args"): quadrilaterals on one rank, clones and host-checked
+// (eager) steps included.  Shards, hexahedra and the persistent velocity solve (k_helm_fused) never reach these launches or keep
+// Dev, whatever the option says; the persistent tails keep Dev and share the bodies.
+static bool leanargs_on(const nsk_ctx* c) {
+  return c->lean_args != 0 && c->ndim == 2 && !c->parent && c->d.nranks <= 1 && !c->fused;
+}
 // round 6, the merged iteration in two launches: A_j (Schwarz workgroups + coarse workgroups) and B_j
 // (needs: the coarse image Tc with nsk::k2::UC_NVL columns, coarse_lda a multiple of 768, two overlap layers of the Schwarz patches)
 static bool fuse2_on(const nsk_ctx* c) {
@@ -1196,6 +1240,11 @@ static void launch_schwarz_uc(nsk_ctx* c, const Dev& d, int j, double scale, int
   const int nit = d.coarse_lda / 256;
   // (fuse2_on: nit is exactly 3, 6, 9 or 12, the table size itself; any other value has never launched anything)
   if (nit < 3 || nit > 12 || nit % 3 != 0) return;
+  if (leanargs_on(c)) {
+    hipLaunchKernelGGL(pick_schwarz_uc_lean<N>(nit), dim3(nsw + cgrid), dim3(256), sh, c->stream, d.gsc, d.p_idx, d.gpart, d.uc_start, d.nel, d.boff, d.nblk,
+                       nsw, j, uc_rest(d, scale, min_iter, ord));
+    return;
+  }
   hipLaunchKernelGGL(pick_schwarz_uc<N>(nit), dim3(nsw + cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord, nsw, cgrid);
 }
 template <int N>
@@ -1218,6 +1267,10 @@ static void launch_pres_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool a
 template <int N>
 static void launch_divgs_t(nsk_ctx* c, const Dev& d, int j) {
   if (c->ndim != 2) return;
+  if (leanargs_on(c)) {
+    hipLaunchKernelGGL(pick_divgs_t_lean<N>(d.tc32, c->cm), dim3(c->nblk), dim3(256), 0, c->stream, d.gsc, d.gs_tab, d.nel, d.boff, (unsigned)c->nblk, j, divgs_rest(d));
+    return;
+  }
   hipLaunchKernelGGL(pick_divgs_t<N>(d.tc32, c->cm), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
 }
 
@@ -1440,6 +1493,11 @@ static void launch_helm_iter(nsk_ctx* c, const Dev& d, const StepCoef& sc, int i
     }
     if constexpr (N <= 10) hipLaunchKernelGGL(pick_helm3<N>(c->cm), dim3(c->nblk), dim3(nsk::k3::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
   } else {                          // quadrilaterals: the packed layout (Dev::helm_pk), one mask per component (nsk_init_masks)
+    if (leanargs_on(c)) {
+      hipLaunchKernelGGL(pick_helm_lean<N>(d.helm_pk, c->cm), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d.hscal, d.gs_tab, d.nel, d.boff, (unsigned)c->nblk, it,
+                         helm_rest(d, sc, rhs));
+      return;
+    }
     hipLaunchKernelGGL(pick_helm<N>(d.helm_pk, c->cm), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
   }
 }
@@ -1801,6 +1859,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
   const bool hpk = helmpack_on(c);
   d.helm_pk = da.helm_pk = hpk ? 1 : 0;
   if (hpk && !in_map) c->helmpack_steps++;
+  if (leanargs_on(c) && !in_map) c->leanargs_steps++;
   if (cfuse) da.bstep_late = ((d.bf_stride || d.forb) && adjoint != 2) ? 1 : 0;
   if (cfuse && !in_map) c->convfuse_steps++;            // (the steps of a map are counted by run_map: a captured step is replayed)
   int nh = hc ? c->max_helm : (nh_over > 0 ? nh_over : c->cur_helm[sc.cls]);
@@ -2021,6 +2080,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   if (absorb_on(c)) { c->up_host = true; c->absorb_maps++; }
   if (convfuse_on(c)) c->convfuse_steps += c->nsteps;
   if (helmpack_on(c)) c->helmpack_steps += c->nsteps;
+  if (leanargs_on(c)) c->leanargs_steps += c->nsteps;
   for (int istep = 1; istep <= c->nsteps; ++istep) {
     if (per_step) {
       HIPCHK(hipGraphLaunch(plan[istep - 1], c->stream));
@@ -2756,6 +2816,11 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
     c->tail_ok = -1;                  // (the residency of the tail is asked of the instantiation that runs)
     invalidate_graphs(c);
   }
+  else if (n == "lean_args") {
+    if (value != -1.0 && value != 0.0 && value != 1.0) return fail(NSK_EINVAL, "lean_args: -1, 0 or 1");
+    c->lean_args = (int)value;
+    invalidate_graphs(c);
+  }
   else if (n == "fuse2_start") { c->fuse2_start = (int)value; invalidate_graphs(c); }
   else if (n == "sb_pct") { c->sb_pct = (int)value; }
   else if (n == "skip_close") { c->skip_close = (int)value; invalidate_graphs(c); }
@@ -2926,6 +2991,7 @@ int nsk_get_stats(nsk_ctx* c, nsk_stats* s) {
   s->absorb_maps = c->absorb_maps;
   s->convfuse_steps = c->convfuse_steps;
   s->helmpack_steps = c->helmpack_steps;
+  s->leanargs_steps = c->leanargs_steps;
   s->zero_arrays = (long long)c->d.zmask | ((long long)c->d.bfmask << 12);
   s->step_budget_helm_mean = c->sb_maps ? (double)c->sb_launch_h / ((double)c->sb_steps) : 0.0;
   s->step_budget_pres_mean = c->sb_maps ? (double)c->sb_launch_p / ((double)c->sb_steps) : 0.0;

@@ -200,8 +200,102 @@ struct Dev {
   int step_cap;
 };
 
+// ---------------------------------------------------------------------------
+// Compact argument blocks (option "lean_args"): Dev is ~1.3 KB by value, 21 lines of 64 B in the kernel-argument segment, and
+// a kernel reads its fields where it uses them -- four to six dependent trips for cold argument lines ahead of the first vector
+// load.  The iteration kernels of the quadrilateral step take instead
+//   Head: what the flag-first exit and the first addresses need, as LEADING scalar / pointer parameters of the kernel (these are
+//         preloaded into SGPRs: -amdgpu-kernarg-preload-count), and
+//   Rest: every other field the family reads, by value on four or five lines, pinned (pin()) so that all of it is requested in ONE
+//         batch together with the flag.
+// Member names are Dev's: the bodies are templates on the argument type and the same text serves Dev (tails, shards, hexahedra).
+// ---------------------------------------------------------------------------
+template <class T> __device__ __forceinline__ void arg_pin(T& x) { asm volatile("" : "+s"(x)); }
+// (a pointer that went through the asm statement is no longer known to be an argument, and its loads would become flat ones, which
+//  count against the LDS counter as well: say again that it points to global memory)
+template <class T> __device__ __forceinline__ void arg_pin(T*& p) {
+  auto g = (__attribute__((address_space(1))) T*)p;
+  asm volatile("" : "+s"(g));
+  p = (T*)g;
+}
+
+struct HelmCoef { double h2; int k, cls; };          // what helm_body reads of StepCoef
+struct HelmHead {
+  double* hscal; const int4* gs_tab;
+  int nel, boff;
+};
+struct HelmRest {
+  const double *bm1, *g1, *g2, *g4, *mask, *minv, *dinv, *D;
+  double *hr, *hp, *hs, *hx, *hwl, *hpart, *htot, *bloc;
+  const double* rhs;
+  const int *gs_off, *gs_idx;
+  Stats* stats;
+  int *stepctr, *step_iters;
+  unsigned long long* dbg;
+  long long cs, nloc;
+  double nu, vol, tol_helm;
+  HelmCoef sc;
+  int nblk, nranks, use_tot, tol_relative, step_cap;
+  __device__ __forceinline__ void pin() {
+    arg_pin(bm1); arg_pin(g1); arg_pin(g2); arg_pin(g4); arg_pin(mask); arg_pin(minv); arg_pin(dinv); arg_pin(D);
+    arg_pin(hr); arg_pin(hp); arg_pin(hs); arg_pin(hx); arg_pin(hwl); arg_pin(hpart);
+    arg_pin(cs); arg_pin(nloc); arg_pin(sc.k); arg_pin(nblk); arg_pin(nranks); arg_pin(use_tot);
+  }                                    // (not pinned: what one lane of one workgroup books, the CSR fallback, launch 0's right-hand sides)
+};
+struct HelmArgs : HelmHead, HelmRest {};
+
+struct UcHead {
+  GmresScal* gsc; const int* p_idx; double* gpart;
+  int uc_start, nel, boff, nblk;
+};
+struct UcRest {
+  const double *J12, *D12, *w2rx, *w2sx, *w2ry, *w2sy;
+  double *Wr, *V, *Z, *yl, *rch, *ecv, *xc;
+  const float *p_inv, *Acif;
+  long long ps, npr, cs;
+  int nvert, coarse_lda;
+  double tol_pres, tol_pres_floor, scale;
+  int tol_relative, pres_cap, nproj_max, min_iter, ord, step_cap;
+  Stats* stats;
+  int *stepctr, *step_iters;
+  unsigned long long* dbg;
+  __device__ __forceinline__ void pin() {
+    arg_pin(J12); arg_pin(D12); arg_pin(Wr); arg_pin(V); arg_pin(rch); arg_pin(ecv); arg_pin(p_inv); arg_pin(Acif);
+    arg_pin(ps); arg_pin(nvert); arg_pin(coarse_lda);
+  }                                    // (not pinned: what ONE lane needs to close the column -- pinned too, the block no longer fits the scalar
+                                       //  registers and spills into vector lanes; those fields share their lines with pinned ones -- and what
+                                       //  the recording lane books)
+};
+struct UcArgs : UcHead, UcRest {};
+
+struct DivgsHead {
+  GmresScal* gsc; const int4* gs_tab;
+  int nel, boff;
+};
+struct DivgsRest {
+  const double *binv, *w2rx, *w2sx, *w2ry, *w2sy, *Tc, *J12, *D12, *hat;
+  const float* Tc32;
+  const int *ecslot, *evl, *evert, *gs_off, *gs_idx;
+  double *Z, *V, *yl, *xc, *Wr, *ec, *ecv, *gpart;
+  unsigned long long* dbg;
+  long long nloc, npr, ps, cs;
+  int nblk;
+  __device__ __forceinline__ void pin() {
+    arg_pin(binv); arg_pin(w2rx); arg_pin(w2sx); arg_pin(w2ry); arg_pin(w2sy); arg_pin(Tc); arg_pin(Tc32); arg_pin(J12); arg_pin(D12); arg_pin(hat);
+    arg_pin(ecslot); arg_pin(evl); arg_pin(evert); arg_pin(Z); arg_pin(V); arg_pin(yl); arg_pin(xc);
+    arg_pin(Wr); arg_pin(ec); arg_pin(ecv); arg_pin(gpart); arg_pin(nblk);
+    arg_pin(nloc); arg_pin(npr); arg_pin(ps); arg_pin(cs);
+  }
+};
+struct DivgsArgs : DivgsHead, DivgsRest {};
+
+// the bodies call this behind the issue of their flag load: nothing for Dev, the one batch of argument loads for a compact block
+__device__ __forceinline__ void arg_batch(const Dev&) {}
+template <class A> __device__ __forceinline__ void arg_batch(const A& d) { const_cast<A&>(d).pin(); }
+
 // iteration count of the current time step's velocity (which = 0) or pressure (1) solve into the per-step record
-__device__ inline void rec_step_iters(const Dev& d, int which, int count) {
+template <class A>
+__device__ inline void rec_step_iters(const A& d, int which, int count) {
   if (!d.step_iters) return;
   const int s = *d.stepctr - 1;
   if (s >= 0 && s < d.step_cap) atomicMax(&d.step_iters[2 * s + which], count);

@@ -208,7 +208,8 @@ struct PartialRows {
 // CSR fallback of the gather (valence > 4: hexahedral vertices, irregular 2-D vertices).  Same
 // left-to-right sum as a plain loop, but the index and value loads of up to eight entries are
 // issued together: three dependent round trips instead of two per entry.
-__device__ inline double gs_csr(const double* __restrict__ f, const Dev& d, long long l) {
+template <class A>
+__device__ inline double gs_csr(const double* __restrict__ f, const A& d, long long l) {
   const int o0 = d.gs_off[l], o1 = d.gs_off[l + 1];
   double s = 0.0;
   for (int k0 = o0; k0 < o1; k0 += 8) {
@@ -249,7 +250,8 @@ __device__ inline GsVals gs_load(const double* __restrict__ f, const int4 t, lon
   v.d = (t.w >= 0) ? f[t.w] : 0.0;
   return v;
 }
-__device__ inline double gs_sum(const GsVals& v, const double* __restrict__ f, const Dev& d, const int4 t, long long l) {
+template <class A>
+__device__ inline double gs_sum(const GsVals& v, const double* __restrict__ f, const A& d, const int4 t, long long l) {
   if (t.x < 0) return gs_csr(f, d, l);
   return ((v.a + v.b) + v.c) + v.d;
 }
@@ -266,7 +268,8 @@ __device__ inline GsVals2 gs_load2(const double2* __restrict__ f, const int4 t, 
   if (t.w >= 0) v.d = f[t.w];
   return v;
 }
-__device__ inline double gs_csr2(const double* __restrict__ f, const Dev& d, long long l, int c) {
+template <class A>
+__device__ inline double gs_csr2(const double* __restrict__ f, const A& d, long long l, int c) {
   const int o0 = d.gs_off[l], o1 = d.gs_off[l + 1];
   double s = 0.0;
   for (int k0 = o0; k0 < o1; k0 += 8) {
@@ -282,7 +285,8 @@ __device__ inline double gs_csr2(const double* __restrict__ f, const Dev& d, lon
   }
   return s;
 }
-__device__ inline double2 gs_sum2(const GsVals2& v, const double2* __restrict__ f, const Dev& d, const int4 t, long long l) {
+template <class A>
+__device__ inline double2 gs_sum2(const GsVals2& v, const double2* __restrict__ f, const A& d, const int4 t, long long l) {
   if (t.x < 0) return make_double2(gs_csr2((const double*)f, d, l, 0), gs_csr2((const double*)f, d, l, 1));
   return make_double2(((v.a.x + v.b.x) + v.c.x) + v.d.x, ((v.a.y + v.b.y) + v.c.y) + v.d.y);
 }
@@ -1012,8 +1016,8 @@ __global__ __launch_bounds__(Cfg<N>::NT) void k_convect_rhs(Dev d, StepCoef sc) 
 // CM (contexts of nsk_init_masks: symmetry boundaries): every velocity component has its own Dirichlet mask and Jacobi diagonal
 // -- Dev::mask is [2][nloc], Dev::dinv [3 orders][2][nloc] -- read with the first batch of loads; the arithmetic per component is
 // that of the shared-mask form.   [UPSTREAM bcmask: v1mask, v2mask]
-template <int N, bool PK = false, bool CM = false>
-__device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int it, const double* rhs, const unsigned bx_, const unsigned gx_) {
+template <int N, bool PK = false, bool CM = false, class A = Dev, class S = StepCoef>
+__device__ __forceinline__ void helm_body(const A& d, const S& sc, int it, const double* rhs, const unsigned bx_, const unsigned gx_) {
   // (shards with halo / interior overlap launch the boundary workgroups first, the rest with an offset; XCD-contiguous runs of
   //  element blocks: the neighbours' edge values are L2 hits where the grid is larger than the caches, config 3)
   const int bid = d.boff + (int)xcd_element(bx_, gx_);
@@ -1029,16 +1033,21 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
   const long long l = e * NN + nd, nl = d.cs;
   const int par = it & 1, ppar = par ^ 1;
   NSK_STAMP(0);
-  // the previous iteration's scalars and -- with them, so that the neighbour gathers below can go out together with the
-  // rest of phase A instead of one round trip later -- this node's gather-table entry (16 B per thread: what a launch that
-  // finds the solve finished pays on top of the flag)
+  // the previous iteration's scalars and -- with them, so that the neighbour gathers below are one round trip behind the
+  // head of phase A and not two -- this node's gather-table entry (16 B per thread: what a launch that finds the solve
+  // finished pays on top of the flag).  Loaded UNCONDITIONALLY from a clamped address and selected behind it: a load in a
+  // branch of its own, merged with a default, is waited for on the spot, ahead of every phase-A load; its first use is the
+  // gathers of phase B.
   double o[8] = {0, 0, 0, 0, 0, 0, 0, 0}, refn[2] = {0, 0};
-  int4 tab = make_int4(0, -1, -1, -1);
-  if (it > 1) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) o[q] = d.hscal[ppar * 8 + q];
+  for (int q = 0; q < 8; ++q) o[q] = d.hscal[ppar * 8 + q];          // (launches 0 and 1: valid memory, dropped below)
+  int4 tab = d.gs_tab[act ? l : 0];
+  if (!act) tab = make_int4(0, -1, -1, -1);
+  arg_batch(d);                       // (compact argument blocks: the rest of the arguments in one batch, in flight with the flags)
+  if (!(it > 1)) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) o[q] = 0.0;
   }
-  if (act) tab = d.gs_tab[l];
   if (it > 2 && o[2] != 0.0 && o[6] != 0.0) {   // finished earlier: cheapest exit
     if (bid == 0 && tid < 8) d.hscal[par * 8 + tid] = o[tid & 7];
     return;
@@ -1264,6 +1273,15 @@ __device__ __forceinline__ void helm_body(const Dev& d, const StepCoef& sc, int 
 template <int N, bool PK = false, bool CM = false>
 __global__ __launch_bounds__(Cfg<N>::NT) void k_helm(Dev d, StepCoef sc, int it, const double* rhs) {
   helm_body<N, PK, CM>(d, sc, it, rhs, blockIdx.x, gridDim.x);
+}
+// option "lean_args": the same body on the compact argument block -- the head as leading parameters (preloaded), the rest pinned
+// into one batch of argument loads that travels with the flags (nsk_dev.hpp); `grid` = gridDim.x without the hidden arguments
+template <int N, bool PK = false, bool CM = false>
+__global__ __launch_bounds__(Cfg<N>::NT) void k_helm_l(double* hscal, const int4* gs_tab, int nel, int boff, unsigned grid, int it, HelmRest r) {
+  HelmArgs d;
+  static_cast<HelmHead&>(d) = HelmHead{hscal, gs_tab, nel, boff};
+  static_cast<HelmRest&>(d) = r;
+  helm_body<N, PK, CM>(d, d.sc, it, d.rhs, blockIdx.x, grid);
 }
 
 
@@ -1794,7 +1812,8 @@ constexpr int UC_ROWS = 2;
 // Closes GMRES column jj from the dot-product sums sh[0..jj+1] (one lane; the same arithmetic in every workgroup => the same
 // decision everywhere): Givens rotations, residual, convergence.  sbc = {1 / h_{jj+1,jj}, converged}; `record`: this workgroup
 // writes the solve's state (GmresScal, statistics).
-__device__ __forceinline__ void uc_rotate(const Dev& d, GmresScal* G, int jj, double gj, double scale, int min_iter, int ord, bool record,
+template <class A>
+__device__ __forceinline__ void uc_rotate(const A& d, GmresScal* G, int jj, double gj, double scale, int min_iter, int ord, bool record,
                                           const double* sh, const double* scs, const double* ssn, double* scol, double* sbc) {
     double s2 = 0.0;
     for (int q = 0; q <= jj; ++q) s2 += sh[q] * sh[q];
@@ -1842,7 +1861,8 @@ __device__ __forceinline__ void uc_rotate(const Dev& d, GmresScal* G, int jj, do
 // The START of a solve inside A_0 (Dev::uc_start, set per launch): what k_gmres_update(j = -1) does -- |g'| from the partials
 // the (element-aligned) projection kernel left in row 0, the solve's state, the convergence flag -- by one lane of every
 // workgroup from sh[0] = |g'|^2; sbc = {1 / |g'|, done}.  The raw g' is in Dev::Wr, its corner restrictions in Dev::ecv.
-__device__ __forceinline__ void uc_start_solve(const Dev& d, GmresScal* G, double scale, int min_iter, bool record, const double* sh, double* sbc) {
+template <class A>
+__device__ __forceinline__ void uc_start_solve(const A& d, GmresScal* G, double scale, int min_iter, bool record, const double* sh, double* sbc) {
   const double hn = sqrt(sh[0]);
   const double gn0 = (d.nproj_max <= 0) ? hn : G->gnorm0;
   const double tol0 = d.tol_relative ? fmax(d.tol_pres * gn0 * scale, d.tol_pres_floor) : d.tol_pres;
@@ -2375,8 +2395,8 @@ __global__ __launch_bounds__(256) void k_proj_apply_e(Dev d) {
 // matrix rows (72 registers) go out when the partial-sum registers are free, behind them the other chunks of corner values, so
 // that the product finds its operands waiting (stamps of the chunked form: 4.5 us corner sums + 3.9 us product of 10.8).
 // The same operations in the same order as update_coarse_body: the same bits (the persistent tail runs that one).
-template <int MAXIT>
-__device__ __forceinline__ void uc_coarse_role(const Dev& d, int j, double scale, int min_iter, int ord, const unsigned bx_) {
+template <int MAXIT, class DA>
+__device__ __forceinline__ void uc_coarse_role(const DA& d, int j, double scale, int min_iter, int ord, const unsigned bx_) {
   extern __shared__ double srcv[];            // lda
   __shared__ double sh[MAXMR + 2], scs[MAXMR], ssn[MAXMR], scol[MAXMR + 2], sbc[4];
   const int tid = threadIdx.x;
@@ -2486,8 +2506,8 @@ __device__ __forceinline__ void uc_coarse_role(const Dev& d, int j, double scale
 
 template <int N>
 struct UcPatch { static constexpr int M = N - 2, PS = (((M + 4) * (M + 4) + 3) / 4) * 4; };   // patch stride at two overlap layers
-template <int N>
-__device__ __forceinline__ void uc_schwarz_role(const Dev& d, int j, double scale, int min_iter, int ord, const unsigned bx_, const unsigned gx_) {
+template <int N, class A>
+__device__ __forceinline__ void uc_schwarz_role(const A& d, int j, double scale, int min_iter, int ord, const unsigned bx_, const unsigned gx_) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NM = N * M;
   constexpr int MAXP = (M + 8) * (M + 8);
@@ -2635,6 +2655,19 @@ __global__ __launch_bounds__(256, 3) void k_schwarz_uc(Dev d, int j, double scal
   if (blockIdx.x < nsw) uc_schwarz_role<N>(d, j, scale, min_iter, ord, blockIdx.x, nsw);
     else uc_coarse_role<MAXIT>(d, j, scale, min_iter, ord, blockIdx.x - nsw);
 }
+template <int N, int MAXIT>
+__global__ __launch_bounds__(256, 3) void k_schwarz_uc_l(GmresScal* gsc, const int* p_idx, double* gpart, int uc_start, int nel, int boff, int nblk,
+                                                         unsigned nsw, int j, UcRest r) {
+  UcArgs d;
+  static_cast<UcHead&>(d) = UcHead{gsc, p_idx, gpart, uc_start, nel, boff, nblk};
+  static_cast<UcRest&>(d) = r;
+  NSK_STAMP(0);
+  const int dn = d.gsc->done;
+  arg_batch(d);                                // (the rest of the arguments in one batch, in flight with the flag)
+  if (!d.uc_start && dn) return;
+  if (blockIdx.x < nsw) uc_schwarz_role<N>(d, j, d.scale, d.min_iter, d.ord, blockIdx.x, nsw);
+    else uc_coarse_role<MAXIT>(d, j, d.scale, d.min_iter, d.ord, blockIdx.x - nsw);
+}
 
 // B_j: see above.  All NVL = 20 columns of Tc (fp32 copy: T32) and the first eight basis vectors live in registers.  Every load
 // of the first trip is UNCONDITIONAL (lanes without a node load a valid address and drop the value; basis vectors in groups of
@@ -2642,8 +2675,8 @@ __global__ __launch_bounds__(256, 3) void k_schwarz_uc(Dev d, int j, double scal
 // full wait per load (seen in the instruction stream of the first cut: twenty dependent trips for the fp32 copy).
 constexpr int UC_NVL = 20;
 // CM (contexts of nsk_init_masks): B^-1 mask per component, as divgs_body<N, true>; Tc is the image under the same operator
-template <int N, bool T32, bool SLIM = false, bool CM = false>
-__device__ __forceinline__ void divgs_t_body(const Dev& d, int j, const unsigned bx_, const unsigned gx_) {
+template <int N, bool T32, bool SLIM = false, bool CM = false, class A = Dev>
+__device__ __forceinline__ void divgs_t_body(const A& d, int j, const unsigned bx_, const unsigned gx_) {
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NM = N * M;
   constexpr int NVL = UC_NVL;
@@ -2656,7 +2689,9 @@ __device__ __forceinline__ void divgs_t_body(const Dev& d, int j, const unsigned
   const long long e = (long long)bid * EPB + el;
   const bool act = (el < EPB) && (e < d.nel);
   NSK_STAMP(0);
-  if (d.gsc->done) return;
+  const int dn = d.gsc->done;
+  arg_batch(d);                                // (compact argument blocks: the rest of the arguments in one batch, in flight with the flag)
+  if (dn) return;
   NSK_STAMP(1);
   const bool pact = act && nd < MM;
   // safe addresses for the lanes without an element / a pressure node
@@ -2813,6 +2848,13 @@ __device__ __forceinline__ void divgs_t_body(const Dev& d, int j, const unsigned
 template <int N, bool T32, bool CM = false>
 __global__ __launch_bounds__(256, 2) void k_divgs_t(Dev d, int j) {
   divgs_t_body<N, T32, false, CM>(d, j, blockIdx.x, gridDim.x);
+}
+template <int N, bool T32, bool CM = false>
+__global__ __launch_bounds__(256, 2) void k_divgs_t_l(GmresScal* gsc, const int4* gs_tab, int nel, int boff, unsigned grid, int j, DivgsRest r) {
+  DivgsArgs d;
+  static_cast<DivgsHead&>(d) = DivgsHead{gsc, gs_tab, nel, boff};
+  static_cast<DivgsRest&>(d) = r;
+  divgs_t_body<N, T32, false, CM>(d, j, blockIdx.x, grid);
 }
 
 // after GMRES: dp = h2 * sum_i y_i Z_i (+ projected part) ; p = p* + dp ; yl = D^T dp
