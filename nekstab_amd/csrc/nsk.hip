@@ -249,8 +249,8 @@ struct nsk_ctx {
   long long absorb_maps = 0;             // maps run with the deferred update of the projection space (option "proj_absorb")
   long long helmpack_steps = 0;          // time steps whose velocity solve ran on the packed scratch arrays (option "helm_pack")
   long long leanargs_steps = 0;          // time steps whose iteration kernels took the compact argument blocks (option "lean_args")
-  int lean_args = -1;                   // k_helm, k_schwarz_uc and k_divgs_t on compact argument blocks (k_helm_l, k_schwarz_uc_l, k_divgs_t_l; nsk_dev.hpp) instead of Dev by value: -1 = where allowed (leanargs_on), 0 = never, 1 = the same as -1 (every other context ignores it); option "lean_args"
-  int helm_pack = -1;                   // 16-byte accesses in the quadrilateral velocity solve (k_helm<N, true>, k_helm_tail<N, true>, k_pres_rhs<N, .., true>): -1 = where allowed and where it pays (helmpack_on: lx1 <= 10), 0 = never, 1 = wherever allowed; option "helm_pack"
+  int lean_args = -1;                   // k_helm, k_schwarz_uc and k_divgs_t on compact argument blocks (k_helm_l, k_schwarz_uc_l, k_divgs_t_l; nsk_dev.hpp) instead of Dev by value: -1 = where allowed (StepForm::leanargs), 0 = never, 1 = the same as -1 (every other context ignores it); option "lean_args"
+  int helm_pack = -1;                   // 16-byte accesses in the quadrilateral velocity solve (k_helm<N, true>, k_helm_tail<N, true>, k_pres_rhs<N, .., true>): -1 = where allowed and where it pays (StepForm::helmpack: lx1 <= 10), 0 = never, 1 = wherever allowed; option "helm_pack"
   long long convfuse_steps = 0;          // time steps run with convection and the velocity right-hand side in one launch (option "conv_fuse")
   long long sb_maps = 0, sb_steps = 0, sb_launch_h = 0, sb_launch_p = 0;     // maps / time steps run on per-step budgets and their budgeted launches (diagnostics)
   bool last_map_per_step = false;        // the map just run took the per-step budgets
@@ -261,8 +261,8 @@ struct nsk_ctx {
   int tc32 = 0;                         // k_divgs_t: the fp32 copy of the coarse image (0 = never (default: it moves a map by 2e-8 for 0.6 us per iteration), 1 = always, -1 = where the solve's relative tolerance is >= 1e-5; option "tc32", NSK_TC32)
   int skip_close = 1;                   // no closing launch behind a pressure tail that covers the merged range (option "skip_close", NSK_SKIP_CLOSE; measured +0.3 %)
   int sb_pct = 90;                      // per-step budgets behind the safety-net tail: percentile of the window's counts (100 = the largest, rounds 5 to mid-6; option "sb_pct", NSK_SB_PCT; 90 measured +0.6 %, with skip_close +1.3 %: profiles/r06_ab_fuse2.txt)
-  int proj_absorb = -1;                 // the update of the pressure projection space of step s applied by its first readers in step s + 1 (k_pres_rhs, k_proj_apply_e) instead of a k_proj_update launch per step: -1 = where the solve starts inside A_0 (absorb_on), 0 = never, 1 = the same as -1 (contexts without that start ignore it); option "proj_absorb"
-  int conv_fuse = -1;                   // convection and the velocity right-hand side in one launch (k_convect_rhs) instead of k_convect + k_rhs: -1 = where allowed (convfuse_on), 0 = never, 1 = the same as -1 (every other context ignores it); option "conv_fuse"
+  int proj_absorb = -1;                 // the update of the pressure projection space of step s applied by its first readers in step s + 1 (k_pres_rhs, k_proj_apply_e) instead of a k_proj_update launch per step: -1 = where the solve starts inside A_0 (StepForm::absorb), 0 = never, 1 = the same as -1 (contexts without that start ignore it); option "proj_absorb"
+  int conv_fuse = -1;                   // convection and the velocity right-hand side in one launch (k_convect_rhs) instead of k_convect + k_rhs: -1 = where allowed (StepForm::convfuse), 0 = never, 1 = the same as -1 (every other context ignores it); option "conv_fuse"
   bool up_host = false;                 // steps with the deferred update are queued and no flush behind them yet (flush_proj)
   int fuse2_start = 1;                  // ... and the solve's start inside its first launch (k_proj_apply_e; no k_gmres_update(-1) launch); option "fuse2_start", NSK_FUSE2_START
   int fuse2 = 1;                        // round 6: the merged iteration in TWO launches (k_schwarz_uc, k_divgs_t; option "fuse2", NSK_FUSE2); 0 = the three launches of rounds 3-5
@@ -1218,29 +1218,126 @@ static void launch_update_coarse(nsk_ctx* c, const Dev& d, int j, double scale, 
   hipLaunchKernelGGL(pick_update_coarse(d.coarse_lda / 256), dim3(cgrid), dim3(256), sh, c->stream, d, j, scale, min_iter, ord);
 }
 
-// The iteration kernels on compact argument blocks (option "lean_args"): quadrilaterals on one rank, clones and host-checked
-// (eager) steps included.  Shards, hexahedra and the persistent velocity solve (k_helm_fused) never reach these launches or keep
-// Dev, whatever the option says; the persistent tails keep Dev and share the bodies.
-static bool leanargs_on(const nsk_ctx* c) {
-  return c->lean_args != 0 && c->ndim == 2 && !c->parent && c->d.nranks <= 1 && !c->fused;
+// ---- The FORM of a time step: which kernels it launches.  step_form() is the only code that turns the option fields and the
+// context's facts into these answers; every launch site takes them from a StepForm (run_map computes one per map and hands it
+// down; a caller outside the maps asks step_form itself).  Three facts are not the context's and are combined with the form where
+// they are known: a stream under capture (hc = F.hostcheck && !stream_capturing), in_map (absorb = in_map && F.absorb), and of the
+// start inside A_0 the parts that belong to one solve (!hc, np > 0, !in_test: pres_solve_launch).
+struct StepForm {
+  // Host-checked convergence on a full-mesh context (option "hostcheck"): eager steps, the host reads the device's flags.  Never on
+  // shards (group_hostcheck), with the persistent velocity solve or in the operator tests.
+  bool hostcheck = false;
+  // Merged bookkeeping (k_update_coarse): quadrilateral single-rank contexts with the dense in-LDS coarse solve (option "merged_update")
+  bool merged = false;
+  // round 6, the merged iteration in two launches: A_j (Schwarz workgroups + coarse workgroups) and B_j (option "fuse2"; needs: the
+  // coarse image Tc with nsk::k2::UC_NVL columns, coarse_lda a multiple of 768, two overlap layers of the Schwarz patches)
+  bool fuse2 = false;
+  // ... and the solve's start inside A_0 (option "fuse2_start"), as far as the context decides it
+  bool f2start = false;
+  // Deferred update of the pressure projection space (option "proj_absorb"): exactly the contexts whose every pressure solve starts
+  // inside A_0 (f2start; pres_solve_launch refuses a step that disagrees) and whose velocity solve is launched per iteration.
+  // Everything else -- hexahedra, shards, host-checked meshes, fuse2 = 0, nproj = 0, the operator tests -- keeps the k_proj_update
+  // launch per step, whatever the option says.
+  bool absorb = false;
+  // Convection and the velocity right-hand side in one launch (option "conv_fuse"): quadrilaterals on one rank whose velocity solve
+  // is launched per iteration, no forcing added between the two halves.  Everything else -- hexahedra, shards, forced and SFD maps,
+  // the persistent form, the operator tests -- keeps k_convect + k_rhs, whatever the option says.  Host-checked (eager) steps take it too.
+  bool convfuse = false;
+  // The velocity solve on packed scratch arrays (option "helm_pack"): quadrilaterals on one rank whose solve is launched per
+  // iteration or ends in the persistent tail.  Shards (the halo exchange and the totals index rows), hexahedra and the persistent
+  // solve (k_helm_fused has its own body) keep the component-major layout.  The arrays are scratch within one solve, so the two
+  // layouts share the allocations and nothing is converted when the option changes.
+  // lx1 = 12 takes it only when the option is 1: k_helm<12, true> needs 142 registers where k_helm<12> needs 124, one wavefront per
+  // SIMD fewer, and that kernel is close to its bandwidth bound (config 3: 18.9 -> 20.2 us per launch, -3 % matvecs/s).
+  bool helmpack = false;
+  // The iteration kernels on compact argument blocks (option "lean_args"): quadrilaterals on one rank, clones and host-checked
+  // (eager) steps included.  Shards, hexahedra and the persistent velocity solve (k_helm_fused) never reach these launches or keep
+  // Dev, whatever the option says; the persistent tails keep Dev and share the bodies.
+  bool leanargs = false;
+  // Persistent tails behind the per-step budgets (option "tail"): graph-replayed quadrilateral single-rank contexts with the merged
+  // bookkeeping whose two tail kernels are resident (nsk_ctx::tail_ok, asked once)
+  bool tails = false;
+  bool gs_lag = false;                  // hexahedra, lx1 <= 10: the lagged second Gram-Schmidt correction (option "gs_lag"; -1 = single-rank contexts)
+  bool flat_proj = false;               // hexahedra, lx1 <= 10 with Dev::dpw: dp, p and PD in one streaming pass (option "flat_proj"; -1 = single-rank contexts)
+  int nit = 0;                          // coarse_lda / 256: the table size of k_schwarz_uc / k_update_coarse / the pressure tails (with_nit)
+};
+// The kernels of a context's two persistent tails, from the selectors: launch_helm_tail / launch_pres_tail launch them and
+// tails_resident asks about them, so the two cannot disagree.  (k_pres_tail2 is the two-launch form's tail, 256 threads whatever
+// lx1; the two pressure tails have one signature.)
+template <int N>
+static auto helm_tail_kernel(const nsk_ctx* c, const StepForm& F) { return pick_helm_tail<N>(F.helmpack, c->cm); }
+template <int N>
+static auto pres_tail_kernel(const nsk_ctx* c, const StepForm& F) { return F.fuse2 ? pick_pres_tail2<N>(F.nit, c->cm) : pick_pres_tail<N>(F.nit, c->cm); }
+template <int N>
+static int pres_tail_threads(const StepForm& F) { return F.fuse2 ? 256 : nsk::k2::Cfg<N>::NT; }
+// persistent tails: both kernels resident with one workgroup per CU of margin (the occupancy query can be one high)
+template <int N>
+static int tails_resident(nsk_ctx* c, const StepForm& F, int ncu) {
+  constexpr int NT = nsk::k2::Cfg<N>::NT;
+  const size_t sh = (size_t)c->d.coarse_lda * sizeof(double);
+  if (!F.fuse2) {
+    // k_pres_tail runs update_coarse_body, written for 256-thread workgroups, on its first cgrid workgroups (ADVICE r5)
+    const unsigned cgrid = (c->d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS);
+    if (NT != 256 || cgrid > (unsigned)c->nblk) return 0;
+  }
+  int ph = 0, pp = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, helm_tail_kernel<N>(c, F), NT, 0) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, pres_tail_kernel<N>(c, F), pres_tail_threads<N>(F), sh) != hipSuccess) return 0;
+  const int need = (c->nblk + ncu - 1) / ncu;
+  if (c->debug) fprintf(stderr, "persistent tails: %d workgroups per CU needed, occupancy %d (velocity) / %d (pressure)\n", need, ph, pp);
+  // (the occupancy query is one workgroup per CU high only where it is bound by scalar registers, 7-8 per CU: MI355X_MICROARCH.md,
+  //  residency; grids of up to 5 per CU take it as it is, as fused_possible does)
+  return need <= std::min(std::min(ph, pp), 5);
 }
-// round 6, the merged iteration in two launches: A_j (Schwarz workgroups + coarse workgroups) and B_j
-// (needs: the coarse image Tc with nsk::k2::UC_NVL columns, coarse_lda a multiple of 768, two overlap layers of the Schwarz patches)
-static bool fuse2_on(const nsk_ctx* c) {
-  if (!(c->fuse2 && c->d.Tc && c->d.Wr && c->d.ecv && c->d.rch && c->ndim == 2)) return false;
-  if (c->d.nvl != nsk::k2::UC_NVL || c->d.coarse_lda % 768 != 0 || c->d.coarse_lda > 3072) return false;
+static StepForm step_form(nsk_ctx* c) {
+  const Dev& d = c->d;
+  StepForm F;
+  const bool quad1 = c->ndim == 2 && !c->parent && d.nranks <= 1 && !c->fused;      // quadrilaterals on one rank, velocity solve launched per iteration
+  const bool hex = c->ndim == 3 && c->N <= 10, rank1 = d.nranks <= 1 && !c->parent;
+  F.nit = d.coarse_lda / 256;
+  // hostcheck = -1: quadrilateral meshes of thousands of workgroups (config 3: 7984 at lx1 = 12, kernels of ~65 us): a flag read per
+  // solve costs less than the launches a budget spends on converged solves, and budgets that cannot overflow mean no redone maps
+  // (measured: 0.262 -> 0.334 Arnoldi steps per second, scripts/cfg3_hostcheck_ab.sh); hexahedral meshes from 8192 elements on
+  if (!c->parent && !c->fused && !c->in_test) F.hostcheck = c->hostcheck >= 0 ? c->hostcheck != 0 : (c->ndim == 2 ? c->nblk > 4096 : c->nel >= 8192);
+  F.merged = c->merged_update && c->ndim == 2 && d.coarse_lda <= 3072 && !d.use_tot && d.nranks <= 1 && d.rch && d.ecv;
   const int M = c->N - 2;
-  return c->d.p_stride == (((M + 4) * (M + 4) + 3) / 4) * 4;
+  F.fuse2 = c->fuse2 && d.Tc && d.Wr && d.ecv && d.rch && c->ndim == 2 && d.nvl == nsk::k2::UC_NVL && d.coarse_lda % 768 == 0 && d.coarse_lda <= 3072 &&
+            d.p_stride == (((M + 4) * (M + 4) + 3) / 4) * 4;
+  F.f2start = F.merged && F.fuse2 && c->fuse2_start && d.nproj_max > 0 && d.nproj_max <= MAXPROJ && std::min(c->merged_iters, c->gmres_cycle) > 0;
+  F.absorb = c->proj_absorb != 0 && !c->fused && !c->in_test && !c->parent && !F.hostcheck && F.f2start && c->max_pres > 0;
+  F.convfuse = c->conv_fuse != 0 && quad1 && !c->force && !c->sfd.on && !c->in_test;
+  F.helmpack = c->helm_pack != 0 && quad1 && !(c->helm_pack < 0 && c->N > 10);
+  F.leanargs = c->lean_args != 0 && quad1;
+  F.gs_lag = hex && (c->gs_lag >= 0 ? c->gs_lag != 0 : rank1);
+  F.flat_proj = hex && d.dpw && (c->flat_proj >= 0 ? c->flat_proj != 0 : rank1);
+  // (F.merged: Dev::rch exists only with the dense coarse solve, so nothing is asked of coarse_lda that the tails did not ask before)
+  if (c->tail != 0 && !c->fused && !c->parent && !c->clone_of && F.merged && !F.hostcheck && c->use_graph) {
+    if (c->tail_ok < 0) {
+      int ncu = 0, dev = 0;
+      c->tail_ok = 0;
+      if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) {
+        switch (c->N) {
+          case 6: c->tail_ok = tails_resident<6>(c, F, ncu); break;
+          case 8: c->tail_ok = tails_resident<8>(c, F, ncu); break;
+          case 10: c->tail_ok = tails_resident<10>(c, F, ncu); break;
+          case 12: c->tail_ok = tails_resident<12>(c, F, ncu); break;
+          default: break;
+        }
+      }
+    }
+    F.tails = c->tail_ok > 0;
+  }
+  return F;
 }
 template <int N>
-static void launch_schwarz_uc(nsk_ctx* c, const Dev& d, int j, double scale, int min_iter, int ord) {
+static void launch_schwarz_uc(nsk_ctx* c, const StepForm& F, const Dev& d, int j, double scale, int min_iter, int ord) {
   if (c->ndim != 2) return;
   const unsigned cgrid = (d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS), nsw = (unsigned)c->nblk;
   const size_t sh = d.coarse_lda * sizeof(double);
-  const int nit = d.coarse_lda / 256;
-  // (fuse2_on: nit is exactly 3, 6, 9 or 12, the table size itself; any other value has never launched anything)
+  const int nit = F.nit;      // (of the context: every Dev handed in is a copy of c->d)
+  // (F.fuse2: nit is exactly 3, 6, 9 or 12, the table size itself; any other value has never launched anything)
   if (nit < 3 || nit > 12 || nit % 3 != 0) return;
-  if (leanargs_on(c)) {
+  if (F.leanargs) {
     hipLaunchKernelGGL(pick_schwarz_uc_lean<N>(nit), dim3(nsw + cgrid), dim3(256), sh, c->stream, d.gsc, d.p_idx, d.gpart, d.uc_start, d.nel, d.boff, d.nblk,
                        nsw, j, uc_rest(d, scale, min_iter, ord));
     return;
@@ -1253,7 +1350,7 @@ static void launch_proj_apply_e(nsk_ctx* c, const Dev& d) {
   hipLaunchKernelGGL(nsk::k2::k_proj_apply_e<N>, dim3(c->nblk), dim3(256), 0, c->stream, d);
 }
 // the quadrilateral forms of the velocity right-hand side and the pressure right-hand side (Dev::absorb, Dev::bstep_late, Dev::helm_pk
-// say what the step asked for): absorb = the deferred projection update (absorb_on), k_rhs then with its bookkeeping workgroup
+// say what the step asked for): absorb = the deferred projection update (StepForm::absorb), k_rhs then with its bookkeeping workgroup
 template <int N>
 static void launch_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool absorb) {
   if (c->ndim != 2) return;
@@ -1265,9 +1362,9 @@ static void launch_pres_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool a
   hipLaunchKernelGGL(pick_pres_rhs<N>(absorb, d.helm_pk), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, helm_par, check_helm);
 }
 template <int N>
-static void launch_divgs_t(nsk_ctx* c, const Dev& d, int j) {
+static void launch_divgs_t(nsk_ctx* c, const StepForm& F, const Dev& d, int j) {
   if (c->ndim != 2) return;
-  if (leanargs_on(c)) {
+  if (F.leanargs) {
     hipLaunchKernelGGL(pick_divgs_t_lean<N>(d.tc32, c->cm), dim3(c->nblk), dim3(256), 0, c->stream, d.gsc, d.gs_tab, d.nel, d.boff, (unsigned)c->nblk, j, divgs_rest(d));
     return;
   }
@@ -1296,47 +1393,21 @@ static int flags_done(nsk_ctx* c, int which, int it, bool* done) {
   }
   return 0;
 }
-static bool hostcheck_on(const nsk_ctx* c) {
-  if (c->parent || c->fused || c->in_test) return false;
-  if (c->hostcheck >= 0) return c->hostcheck != 0;
-  // quadrilateral meshes of thousands of workgroups (config 3: 7984 at lx1 = 12, kernels of ~65 us): a flag read per solve costs
-  // less than the launches a budget spends on converged solves, and budgets that cannot overflow mean no redone maps
-  // (measured: 0.262 -> 0.334 Arnoldi steps per second, scripts/cfg3_hostcheck_ab.sh)
-  if (c->ndim == 2) return c->nblk > 4096;
-  return c->nel >= 8192;
-}
 
-// Deferred update of the pressure projection space (option "proj_absorb"): exactly the contexts whose every pressure solve starts
-// inside A_0 (f2start of pres_solve_launch, which refuses a step that disagrees) and whose velocity solve is launched per
-// iteration.  Everything else -- hexahedra, shards, host-checked meshes, fuse2 = 0, nproj = 0, the operator tests -- keeps the
-// k_proj_update launch per step, whatever the option says.
-static bool absorb_on(const nsk_ctx* c) {
-  const Dev& d = c->d;
-  if (c->proj_absorb == 0 || c->fused || c->in_test || c->parent || hostcheck_on(c)) return false;
-  if (!(c->merged_update && c->ndim == 2 && d.coarse_lda <= 3072 && !d.use_tot && d.nranks <= 1 && d.rch && d.ecv)) return false;
-  if (!(fuse2_on(c) && c->fuse2_start && d.nproj_max > 0 && d.nproj_max <= MAXPROJ)) return false;
-  return c->max_pres > 0 && std::min(c->merged_iters, c->gmres_cycle) > 0;
-}
-// Convection and the velocity right-hand side in one launch (option "conv_fuse"): quadrilaterals on one rank whose velocity solve
-// is launched per iteration, no forcing added between the two halves.  Everything else -- hexahedra, shards, forced and SFD maps, the
-// persistent form, the operator tests -- keeps k_convect + k_rhs, whatever the option says.  Host-checked (eager) steps take it too.
-static bool convfuse_on(const nsk_ctx* c) {
-  if (c->conv_fuse == 0 || c->ndim != 2 || c->parent || c->d.nranks > 1 || c->fused || c->force || c->sfd.on || c->in_test) return false;
-  return true;
-}
-// The velocity solve on packed scratch arrays (option "helm_pack"): quadrilaterals on one rank whose solve is launched per
-// iteration or ends in the persistent tail.  Shards (the halo exchange and the totals index rows), hexahedra and the persistent
-// solve (k_helm_fused has its own body) keep the component-major layout.  The arrays are scratch within one solve, so the two
-// layouts share the allocations and nothing is converted when the option changes.
-// lx1 = 12 takes it only when the option is 1: k_helm<12, true> needs 142 registers where k_helm<12> needs 124, one wavefront per
-// SIMD fewer, and that kernel is close to its bandwidth bound (config 3: 18.9 -> 20.2 us per launch, -3 % matvecs/s).
-static bool helmpack_on(const nsk_ctx* c) {
-  if (c->helm_pack == 0 || c->ndim != 2 || c->parent || c->d.nranks > 1 || c->fused) return false;
-  if (c->helm_pack < 0 && c->N > 10) return false;
-  return true;
+// The convection kernel of a step (step(), group_step()): hexahedra at lx1 = 8 and 10 with the contractions on the matrix cores
+// (option "mfma_convect"; adjoint = 2, the full equations of Newton-Krylov, at lx1 = 10 only), else k_convect of the context's kernel set
+template <int N>
+static void launch_convect(nsk_ctx* c, const Dev& d, int adjoint) {
+  const dim3 grid(c->nel);
+  const double* u = d.u;
+  if (c->key == 108 && adjoint != 2 && c->mfma_convect) hipLaunchKernelGGL(nsk::k3::k_convect_mfma8, grid, dim3(512), 0, c->stream, d, u, d.bf, adjoint);
+  else if (c->key == 110 && adjoint != 2 && c->mfma_convect) hipLaunchKernelGGL(nsk::k3::k_convect_mfma<10>, grid, dim3(512), 0, c->stream, d, u, d.bf, adjoint);
+  else if (c->key == 110 && c->mfma_convect) hipLaunchKernelGGL(nsk::k3::k_convect_mfma_nl<10>, grid, dim3(1024), 0, c->stream, d, u, d.bf);
+  else if (c->ndim == 2) hipLaunchKernelGGL(nsk::k2::k_convect<N>, grid, dim3(nsk::k2::Cfg<N>::NTD), 0, c->stream, d, u, d.bf, adjoint);
+  else if constexpr (N <= 10) hipLaunchKernelGGL(nsk::k3::k_convect<N>, grid, dim3(nsk::k3::Cfg<N>::NTD), 0, c->stream, d, u, d.bf, adjoint);
 }
 template <int N>
-static void launch_convect_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool absorb) {      // (quadrilaterals only: convfuse_on)
+static void launch_convect_rhs(nsk_ctx* c, const Dev& d, const StepCoef& sc, bool absorb) {      // (quadrilaterals only: StepForm::convfuse)
   if (c->ndim != 2) return;
   hipLaunchKernelGGL(pick_convect_rhs<N>(absorb), dim3(c->nblk + (absorb ? 1 : 0)), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc);
 }
@@ -1351,14 +1422,6 @@ static int flush_proj(nsk_ctx* c) {
   return 0;
 }
 
-// hexahedral GMRES column j in the lagged form: streaming Gram-Schmidt pass (first-pass subtraction, second-pass dots, the
-// pending correction of v_j, corner restriction of w'), totals, Hessenberg column.  JB = compile-time bound of j, RB = rows
-// of 64 nodes in flight per wavefront.
-static bool gs_lag_on(const nsk_ctx* c) {
-  if (c->ndim != 3 || c->N > 10) return false;
-  if (c->gs_lag >= 0) return c->gs_lag != 0;
-  return c->d.nranks <= 1 && !c->parent;
-}
 // Resident workgroups of a hexahedral kernel: as many as the device holds at once (per_cu on every CU), a multiple of 8 so that
 // a workgroup's stride stays inside its XCD's run of elements.
 static int resident_grid(int per_cu) {
@@ -1426,8 +1489,11 @@ static void launch_divgs3(nsk_ctx* c, const Dev& d, int count, const double* yl,
     hipLaunchKernelGGL(pick_divgs3<N>(c3 != 0, c->cm), dim3(count), dim3(nsk::k3::Cfg<N>::NT), 0, c->stream, d, yl, wout, j, check_done);
   }
 }
+// hexahedral GMRES column j in the lagged form (StepForm::gs_lag): streaming Gram-Schmidt pass (first-pass subtraction, second-pass
+// dots, the pending correction of v_j, corner restriction of w'), totals, Hessenberg column.  JB = compile-time bound of j, RB = rows
+// of 64 nodes in flight per wavefront.
 template <int N>
-static void launch_gs_dots3(nsk_ctx* c, const Dev& d, int j) {         // first-pass dots as their own streaming pass (gs_lag = 2)
+static void launch_gs_dots3(nsk_ctx* c, const Dev& d, int j) {        // first-pass dots as their own streaming pass (gs_lag = 2)
   if constexpr (N <= 10) {
     constexpr int ROWS = (nsk::k3::Cfg<N>::MM + 63) / 64;
     constexpr int R4 = ROWS < 4 ? ROWS : 4, R2 = ROWS < 2 ? ROWS : 2;
@@ -1471,7 +1537,7 @@ static int helm_pf_grid(nsk_ctx* c) {
 }
 // one CG iteration of the velocity solve: k_helm, or (hexahedra with Dev::helm_fdm) the two launches of the block-preconditioned form
 template <int N>
-static void launch_helm_iter(nsk_ctx* c, const Dev& d, const StepCoef& sc, int it, const double* rhs) {
+static void launch_helm_iter(nsk_ctx* c, const StepForm& F, const Dev& d, const StepCoef& sc, int it, const double* rhs) {
   if constexpr (N <= 10) {
     if (c->ndim == 3 && d.helm_fdm) {
       hipLaunchKernelGGL(nsk::k3::k_helm_fa<N>, dim3(c->nblk), dim3(nsk::k3::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
@@ -1493,7 +1559,7 @@ static void launch_helm_iter(nsk_ctx* c, const Dev& d, const StepCoef& sc, int i
     }
     if constexpr (N <= 10) hipLaunchKernelGGL(pick_helm3<N>(c->cm), dim3(c->nblk), dim3(nsk::k3::Cfg<N>::NT), 0, c->stream, d, sc, it, rhs);
   } else {                          // quadrilaterals: the packed layout (Dev::helm_pk), one mask per component (nsk_init_masks)
-    if (leanargs_on(c)) {
+    if (F.leanargs) {
       hipLaunchKernelGGL(pick_helm_lean<N>(d.helm_pk, c->cm), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d.hscal, d.gs_tab, d.nel, d.boff, (unsigned)c->nblk, it,
                          helm_rest(d, sc, rhs));
       return;
@@ -1507,11 +1573,6 @@ static void launch_vel_update_proj3(nsk_ctx* c, const Dev& d, const StepCoef& sc
   if constexpr (N <= 10) hipLaunchKernelGGL(pick_vel_update_proj3<N>(c->cm), dim3(c->nblk), dim3(nsk::k3::Cfg<N>::NT), 0, c->stream, d, sc);
 }
 
-static bool flat_proj_on(const nsk_ctx* c) {
-  if (c->ndim != 3 || c->N > 10 || !c->d.dpw) return false;
-  if (c->flat_proj >= 0) return c->flat_proj != 0;
-  return c->d.nranks <= 1 && !c->parent;
-}
 template <int N>
 static void launch_pres_comb3(nsk_ctx* c, const Dev& d, const StepCoef& sc) {        // dp, p and PD in one streaming pass, then yl = D^T dp
   if constexpr (N <= 10) {
@@ -1528,8 +1589,8 @@ static void launch_proj_dots3(nsk_ctx* c, const Dev& d) {
   }
 }
 
-template <int N> static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double scale, int min_iter, int ord, bool start = false);
-static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_mul = 1.0, bool allow_cap = false, bool hc = false, bool tail = false, bool absorb = false) {
+template <int N> static void launch_pres_tail(nsk_ctx* c, const StepForm& F, const Dev& d, int j0, int j1, double scale, int min_iter, int ord, bool start = false);
+static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, int np, double tol_mul = 1.0, bool allow_cap = false, bool hc = false, bool tail = false, bool absorb = false) {
   Dev d = c->d;                                            // by value: the early steps of a map run with a tighter tolerance
   d.absorb = absorb ? 1 : 0;
   d.tol_pres = early_tol(d, tol_mul);
@@ -1538,7 +1599,7 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
     d.pres_cap = std::max(c->pres_cap, c->min_pres); np = std::min(np, d.pres_cap);
   }
   const double scale = 1.0 / (h2 * std::sqrt(d.vol));
-  const bool lag = gs_lag_on(c);
+  const bool lag = F.gs_lag;
   d.gs_lag = lag ? 1 : 0;
   DISPATCH_N(c->key, {
     constexpr int NT = Cfg<N>::NT;
@@ -1547,11 +1608,9 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
     if (!d.has_outflow && !c->in_test) { hipLaunchKernelGGL(k_ortho, dim3(c->nblk), dim3(256), 0, c->stream, d); tot_rows(c, d.gpart, 1, d.gtot); }
     // round 6: with the two-launch iteration the solve starts INSIDE A_0 (element-aligned projection kernel -> raw g' in Wr
     // + its corner restrictions; no k_gmres_update(-1) launch) where the projection kernel is the last producer of g'
-    const bool merged0 = c->merged_update && c->ndim == 2 && d.coarse_lda <= 3072 && !d.use_tot && d.nranks <= 1 && d.rch && d.ecv && !hc;
     // (the choice must not depend on the launch budgets or on the tail mode: the two projection kernels sum their partials in
     //  different groups, so a step that switched form with its budget would change bits between otherwise identical runs)
-    const bool f2start = merged0 && fuse2_on(c) && c->fuse2_start && d.nproj_max > 0 && d.nproj_max <= MAXPROJ && !c->in_test && np > 0 &&
-                         std::min(c->merged_iters, c->gmres_cycle) > 0;
+    const bool f2start = F.f2start && !hc && !c->in_test && np > 0;
     if (absorb && !f2start) return fail(NSK_EINVAL, "internal: deferred projection update in a step whose pressure solve does not start inside A_0");
     if (f2start) launch_proj_apply_e<N>(c, d);
     else if (d.nproj_max > 0 && !c->in_test) { hipLaunchKernelGGL(k_proj_apply, dim3(c->nblk), dim3(256), 0, c->stream, d); tot_rows(c, d.gpart, 1, d.gtot); }
@@ -1560,7 +1619,7 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
     // Only the first `merged_iters` (24) iterations of a solve: x_c(v_j) by linearity is a recurrence, its rounding error grows by
     // ~|h_jj / h_{j+1,j}| per iteration (harmless in a preconditioner for a dozen iterations, a stalled solve after forty:
     // measured on the 1e-8 solves of test_newton_gpu); later iterations take the classic four kernels.
-    const bool merged = c->merged_update && c->ndim == 2 && d.coarse_lda <= 3072 && !d.use_tot && d.nranks <= 1 && d.rch && d.ecv && !hc;
+    const bool merged = F.merged && !hc;
     // with a persistent tail `np` is the HEAD (merged iterations launched one by one); the tail covers the rest of the merged
     // range in one launch, and iterations beyond it (classic form) keep the class budget
     const bool tl = tail && merged && d.pres_cap == 0;
@@ -1573,14 +1632,14 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
       if (rc2) return rc2;
       if (done) { c->hc_pres[ord] = 0; np = 0; }
     }
-    const bool f2 = merged && fuse2_on(c);
+    const bool f2 = merged && F.fuse2;
     // the fp32 copy of the coarse image where the tolerance of THIS solve is loose (relative, >= 1e-5): option "tc32" = -1 (default) / 0 / 1
     d.tc32 = (c->tc32 < 0) ? ((d.tol_relative && d.tol_pres >= 1e-5 && d.Tc32) ? 1 : 0) : ((c->tc32 && d.Tc32) ? 1 : 0);
     for (int j = 0; j < (tl ? nhead : nm); ++j) {
       if (f2) {                                            // two launches per iteration (round 6)
         Dev d0 = d; d0.uc_start = (f2start && j == 0) ? 1 : 0;
-        launch_schwarz_uc<N>(c, d0, j, scale, c->min_pres, ord);
-        launch_divgs_t<N>(c, d, j);
+        launch_schwarz_uc<N>(c, F, d0, j, scale, c->min_pres, ord);
+        launch_divgs_t<N>(c, F, d, j);
         continue;
       }
       launch_update_coarse(c, d, j, scale, c->min_pres, ord);
@@ -1588,7 +1647,7 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
       if (c->ndim == 2) launch_divgs2<N>(c, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2);
       else hipLaunchKernelGGL(k_divgs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2);
     }
-    if (tl && nhead < nm) launch_pres_tail<N>(c, d, nhead, nm, scale, c->min_pres, ord, f2start && nhead == 0);
+    if (tl && nhead < nm) launch_pres_tail<N>(c, F, d, nhead, nm, scale, c->min_pres, ord, f2start && nhead == 0);
     // a velocity tail ran in this step but no pressure tail will: the velocity tail's barrier words (set 0) are re-zeroed by
     // the pressure tail only, so zero them here (a dirty set lets the next velocity tail's first barriers fall through)
     if (tail && !(tl && nhead < nm) && c->sync) (void)hipMemsetAsync(c->sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream);
@@ -1600,7 +1659,7 @@ static int pres_solve_launch(nsk_ctx* c, double h2, int ord, int np, double tol_
         // two-launch form, budget below the merged range: the last column is closed by A_nm -- the SAME code (uc_rotate) that closes
         // every other column and that the persistent tail runs, so that a solve of exactly nm iterations ends with the same bits
         // whatever budget or tail mode ended it (k_gmres_update's own copy of the rotation differs from it by rounding)
-        launch_schwarz_uc<N>(c, d, nm, scale, c->min_pres, ord);
+        launch_schwarz_uc<N>(c, F, d, nm, scale, c->min_pres, ord);
       } else {
         Dev dcl = d;
         if (f2) dcl.wraw = d.Wr;                           // the raw w of B_{nm-1}; classic iterations follow: they need v_nm normalised and its corner restrictions
@@ -1685,75 +1744,26 @@ static int fused_possible(nsk_ctx* c) {
   return need <= std::min(per, 5);      // 5: what ~110 SGPRs admit (floor(800 / 128) = 6) minus one
 }
 
-// The kernels of a context's two persistent tails, from the selectors: launch_helm_tail / launch_pres_tail launch them and
-// tails_resident asks about them, so the two cannot disagree.  (k_pres_tail2 is the two-launch form's tail, 256 threads whatever
-// lx1; the two pressure tails have one signature.)
 template <int N>
-static auto helm_tail_kernel(const nsk_ctx* c) { return pick_helm_tail<N>(helmpack_on(c), c->cm); }
-template <int N>
-static auto pres_tail_kernel(const nsk_ctx* c) {
-  const int nit = c->d.coarse_lda / 256;
-  return fuse2_on(c) ? pick_pres_tail2<N>(nit, c->cm) : pick_pres_tail<N>(nit, c->cm);
-}
-template <int N>
-static int pres_tail_threads(const nsk_ctx* c) { return fuse2_on(c) ? 256 : nsk::k2::Cfg<N>::NT; }
-// persistent tails: both kernels resident with one workgroup per CU of margin (the occupancy query can be one high)
-template <int N>
-static int tails_resident(nsk_ctx* c, int ncu) {
-  constexpr int NT = nsk::k2::Cfg<N>::NT;
-  const size_t sh = (size_t)c->d.coarse_lda * sizeof(double);
-  if (!fuse2_on(c)) {
-    // k_pres_tail runs update_coarse_body, written for 256-thread workgroups, on its first cgrid workgroups (ADVICE r5)
-    const unsigned cgrid = (c->d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS);
-    if (NT != 256 || cgrid > (unsigned)c->nblk) return 0;
-  }
-  int ph = 0, pp = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&ph, helm_tail_kernel<N>(c), NT, 0) != hipSuccess) return 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&pp, pres_tail_kernel<N>(c), pres_tail_threads<N>(c), sh) != hipSuccess) return 0;
-  const int need = (c->nblk + ncu - 1) / ncu;
-  if (c->debug) fprintf(stderr, "persistent tails: %d workgroups per CU needed, occupancy %d (velocity) / %d (pressure)\n", need, ph, pp);
-  // (the occupancy query is one workgroup per CU high only where it is bound by scalar registers, 7-8 per CU: MI355X_MICROARCH.md,
-  //  residency; grids of up to 5 per CU take it as it is, as fused_possible does)
-  return need <= std::min(std::min(ph, pp), 5);
-}
-static bool tails_on(nsk_ctx* c) {
-  if (c->tail == 0 || c->fused || c->ndim != 2 || c->parent || c->clone_of || c->d.use_tot || c->d.nranks > 1 || !c->d.ecv || !c->d.rch || !c->merged_update) return false;
-  if (hostcheck_on(c) || !c->use_graph) return false;
-  if (c->tail_ok < 0) {
-    int ncu = 0, dev = 0;
-    c->tail_ok = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) {
-      switch (c->N) {
-        case 6: c->tail_ok = tails_resident<6>(c, ncu); break;
-        case 8: c->tail_ok = tails_resident<8>(c, ncu); break;
-        case 10: c->tail_ok = tails_resident<10>(c, ncu); break;
-        case 12: c->tail_ok = tails_resident<12>(c, ncu); break;
-        default: break;
-      }
-    }
-  }
-  return c->tail_ok > 0;
-}
-template <int N>
-static void launch_helm_tail(nsk_ctx* c, const Dev& d, const StepCoef& sc, int it0, int it_end) {
+static void launch_helm_tail(nsk_ctx* c, const StepForm& F, const Dev& d, const StepCoef& sc, int it0, int it_end) {
   if (c->ndim != 2) return;
-  // (step() set d.helm_pk from helmpack_on, the question helm_tail_kernel asks)
-  hipLaunchKernelGGL(helm_tail_kernel<N>(c), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
+  // (step() set d.helm_pk from F.helmpack, the member helm_tail_kernel reads)
+  hipLaunchKernelGGL(helm_tail_kernel<N>(c, F), dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, d, sc, it0, it_end, (const double*)d.rloc, c->sync, c->sync + SYNC_WORDS);
 }
 template <int N>
-static void launch_pres_tail(nsk_ctx* c, const Dev& d, int j0, int j1, double scale, int min_iter, int ord, bool start) {
+static void launch_pres_tail(nsk_ctx* c, const StepForm& F, const Dev& d, int j0, int j1, double scale, int min_iter, int ord, bool start) {
   if (c->ndim != 2) return;
   const unsigned cgrid = (d.nvert + 4 * UC_ROWS - 1) / (4 * UC_ROWS);
   const size_t sh = d.coarse_lda * sizeof(double);
   unsigned* sy = c->sync + SYNC_WORDS;          // (set 1; zeroes set 0 for the next velocity tail)
   // column j0-1 is closed by a launch: a solve of exactly j0 iterations ends there (the tails: skip_a)
-  if (fuse2_on(c)) {
+  if (F.fuse2) {
     Dev d0 = d; d0.uc_start = (start && j0 == 0) ? 1 : 0;      // (a head of zero launches: the solve starts in this one)
-    launch_schwarz_uc<N>(c, d0, j0, scale, min_iter, ord);   // A_{j0}
+    launch_schwarz_uc<N>(c, F, d0, j0, scale, min_iter, ord);   // A_{j0}
   } else {
     launch_update_coarse(c, d, j0, scale, min_iter, ord);
   }
-  hipLaunchKernelGGL(pres_tail_kernel<N>(c), dim3(c->nblk), dim3(pres_tail_threads<N>(c)), sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
+  hipLaunchKernelGGL(pres_tail_kernel<N>(c, F), dim3(c->nblk), dim3(pres_tail_threads<N>(F)), sh, c->stream, d, j0, j1, scale, min_iter, ord, cgrid, 1, sy, c->sync);
 }
 
 // Call j of SFD (nsk_sfd.hpp) on the state after time step j of the running map: j = 0 .. nsteps - 1 behind the convection
@@ -1844,22 +1854,22 @@ static int bcv_begin_attempt(nsk_ctx* c) {
   return c->bcv.attempt++ > 0 ? bcv_restore(c) : 0;
 }
 
-static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_over = -1, bool tail = false, bool in_map = false) {
+static int step(nsk_ctx* c, const StepForm& F, int istep, int adjoint, int nh_over = -1, int np_over = -1, bool tail = false, bool in_map = false) {
   Dev& d = c->d;
   const StepCoef sc = make_coef(c, istep, adjoint);
-  const bool hc = hostcheck_on(c) && !stream_capturing(c->stream);
+  const bool hc = F.hostcheck && !stream_capturing(c->stream);
   // the steps of a map (run_map flushes behind the last one) with the deferred update of the projection space: k_rhs gets
   // the bookkeeping workgroup, k_pres_rhs / k_proj_apply_e apply the last step's update, no k_proj_update launch
-  const bool absorb = in_map && absorb_on(c);
+  const bool absorb = in_map && F.absorb;
   Dev da = d; da.absorb = absorb ? 1 : 0;
-  // one launch for convection + right-hand side (convfuse_on); it reads *bstep in every workgroup, so this step's k_pres_rhs
+  // one launch for convection + right-hand side (F.convfuse); it reads *bstep in every workgroup, so this step's k_pres_rhs
   // advances it (once per step in every launch mode: budgets, tails, eager, captured)
-  const bool cfuse = convfuse_on(c);
-  // the velocity solve on the packed scratch arrays (helmpack_on): k_helm, k_helm_tail and this step's k_pres_rhs agree on it
-  const bool hpk = helmpack_on(c);
+  const bool cfuse = F.convfuse;
+  // the velocity solve on the packed scratch arrays (F.helmpack): k_helm, k_helm_tail and this step's k_pres_rhs agree on it
+  const bool hpk = F.helmpack;
   d.helm_pk = da.helm_pk = hpk ? 1 : 0;
   if (hpk && !in_map) c->helmpack_steps++;
-  if (leanargs_on(c) && !in_map) c->leanargs_steps++;
+  if (F.leanargs && !in_map) c->leanargs_steps++;
   if (cfuse) da.bstep_late = ((d.bf_stride || d.forb) && adjoint != 2) ? 1 : 0;
   if (cfuse && !in_map) c->convfuse_steps++;            // (the steps of a map are counted by run_map: a captured step is replayed)
   int nh = hc ? c->max_helm : (nh_over > 0 ? nh_over : c->cur_helm[sc.cls]);
@@ -1868,15 +1878,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
     if (d.forb && adjoint != 2)       // Fourier orbit: the base flow of this step into the steady slot (hexahedra: cUr is the 12-constant array)
       hipLaunchKernelGGL(k_baseflow_fourier<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (double*)d.cUr, (double*)d.cUs,
                          (double*)d.GUx, (double*)d.GUy, (double*)d.GVx, (double*)d.GVy);
-    if (cfuse) { }                  // (below: k_convect_rhs)
-    else if (c->key == 108 && adjoint != 2 && c->mfma_convect)
-      hipLaunchKernelGGL(nsk::k3::k_convect_mfma8, dim3(c->nel), dim3(512), 0, c->stream, d, (const double*)d.u, d.bf, adjoint);
-    else if (c->key == 110 && adjoint != 2 && c->mfma_convect)
-      hipLaunchKernelGGL(nsk::k3::k_convect_mfma<10>, dim3(c->nel), dim3(512), 0, c->stream, d, (const double*)d.u, d.bf, adjoint);
-    else if (c->key == 110 && adjoint == 2 && c->mfma_convect)      // the full equations (Newton-Krylov)
-      hipLaunchKernelGGL(nsk::k3::k_convect_mfma_nl<10>, dim3(c->nel), dim3(1024), 0, c->stream, d, (const double*)d.u, d.bf);
-    else
-      hipLaunchKernelGGL(k_convect<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, d, (const double*)d.u, d.bf, adjoint);
+    if (!cfuse) launch_convect<N>(c, d, adjoint);      // (else below: k_convect_rhs)
     if (c->force)                     // forced map: + B f where the sponge entered, before the EXT extrapolation (k_rhs)
       hipLaunchKernelGGL(nsk::sens::k_add_force, dim3((unsigned)((d.nloc + 255) / 256)), dim3(256), 0, c->stream, d.bf, d.cs, d.bm1, c->force, d.nloc, c->ndim);
     if (c->sfd.on) sfd_call(c, istep - 1);      // SFD map: the filter, the residual and + B (-chi)(vxo - qbar) in the same place
@@ -1890,7 +1892,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
       else hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc);
       if (tail) nh = std::max(1, std::min(nh, c->max_helm - 1));      // HEAD launches; the persistent tail runs launches nh .. max_helm-1
       for (int it = 0; it < nh; ++it) {
-        launch_helm_iter<N>(c, d, sc, it, (const double*)d.rloc);
+        launch_helm_iter<N>(c, F, d, sc, it, (const double*)d.rloc);
         tot_rows(c, d.hpart + (size_t)(it & 1) * c->hrows * c->nblk, c->hrows, d.htot + (it & 1) * c->hstride);
         if (hc && it >= 1 && it >= c->hc_helm[sc.cls] && ((it - c->hc_helm[sc.cls]) % 2 == 0)) {
           bool done = false;
@@ -1899,7 +1901,7 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
           if (done) { c->hc_helm[sc.cls] = std::max(1, it - 1); nh = it + 1; break; }
         }
       }
-      if (tail) { launch_helm_tail<N>(c, d, sc, nh, c->max_helm); nh = c->max_helm; }
+      if (tail) { launch_helm_tail<N>(c, F, d, sc, nh, c->max_helm); nh = c->max_helm; }
       // (quadrilaterals: `da` is `d` with this step's absorb and bstep_late, the two k_pres_rhs reads besides helm_pk)
       if (c->ndim == 2) launch_pres_rhs<N>(c, da, sc, absorb, (nh - 1) & 1, nh - 1);
       else hipLaunchKernelGGL(k_pres_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc, (nh - 1) & 1, nh - 1);
@@ -1907,9 +1909,9 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
   });
   // The first steps of a map project out whatever divergence the input vector has (a noise seed is far from
   // solenoidal): an error there survives to the end of the map, so those solves are converged further.
-  int rc = pres_solve_launch(c, sc.h2, sc.cls, hc ? c->max_pres : (np_over > 0 ? np_over : c->cur_pres[sc.cls]), istep <= 3 ? c->early_pres_mul : 1.0, adjoint != 2, hc, tail, absorb);
+  int rc = pres_solve_launch(c, F, sc.h2, sc.cls, hc ? c->max_pres : (np_over > 0 ? np_over : c->cur_pres[sc.cls]), istep <= 3 ? c->early_pres_mul : 1.0, adjoint != 2, hc, tail, absorb);
   if (rc) return rc;
-  const bool flat = flat_proj_on(c);
+  const bool flat = F.flat_proj;
   Dev df = da; df.flat_proj = flat ? 1 : 0;
   DISPATCH_N(c->key, {
     if (flat) launch_pres_comb3<N>(c, df, sc);
@@ -1934,14 +1936,14 @@ static int step(nsk_ctx* c, int istep, int adjoint, int nh_over = -1, int np_ove
 
 static const int CLS_ISTEP[NCLS] = {1, 2, 3, 4, 7, 17};    // first step of every class
 
-static int ensure_graph(nsk_ctx* c, int cls, int adjoint) {
+static int ensure_graph(nsk_ctx* c, const StepForm& F, int cls, int adjoint) {
   nsk_ctx::StepGraph& g = c->graphs[adjoint][cls];
   if (g.exec && g.nh == c->cur_helm[cls] && g.np == c->cur_pres[cls]) return 0;
   const auto t_cap0 = std::chrono::steady_clock::now();
   if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
   hipGraph_t graph = nullptr;
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = step(c, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
+  int rc = step(c, F, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
   if (rc) return rc;
   if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1953,7 +1955,7 @@ static int ensure_graph(nsk_ctx* c, int cls, int adjoint) {
   return 0;
 }
 
-static int ensure_graph_multi(nsk_ctx* c, int adjoint) {
+static int ensure_graph_multi(nsk_ctx* c, const StepForm& F, int adjoint) {
   nsk_ctx::StepGraph& g = c->graphs[adjoint][NCLS];
   const int cls = NCLS - 1;
   if (g.exec && g.nh == c->cur_helm[cls] && g.np == c->cur_pres[cls]) return 0;
@@ -1962,7 +1964,7 @@ static int ensure_graph_multi(nsk_ctx* c, int adjoint) {
   hipGraph_t graph = nullptr;
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
-  for (int r = 0; r < c->graph_steps && !rc; ++r) rc = step(c, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
+  for (int r = 0; r < c->graph_steps && !rc; ++r) rc = step(c, F, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
   if (rc) return rc;
   if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -1975,8 +1977,8 @@ static int ensure_graph_multi(nsk_ctx* c, int adjoint) {
 }
 
 // the captured step of class `cls` with the launch budgets (nh, np): per-step budgets (nsk_ctx::gcache)
-static int graph_for(nsk_ctx* c, int adjoint, int cls, int nh, int np, hipGraphExec_t* out) {
-  const bool tail = tails_on(c);
+static int graph_for(nsk_ctx* c, const StepForm& F, int adjoint, int cls, int nh, int np, hipGraphExec_t* out) {
+  const bool tail = F.tails;
   const std::array<int, 4> key{adjoint, cls + (tail ? 16 : 0), nh, np};
   auto it = c->gcache.find(key);
   if (it != c->gcache.end()) { *out = it->second; return 0; }
@@ -1985,7 +1987,7 @@ static int graph_for(nsk_ctx* c, int adjoint, int cls, int nh, int np, hipGraphE
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = step(c, CLS_ISTEP[cls], adjoint, nh, np, tail, true);
+  int rc = step(c, F, CLS_ISTEP[cls], adjoint, nh, np, tail, true);
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
   if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
   if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -2041,7 +2043,8 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   if (d.forb && adjoint != 2) { int rc = forb_trig_ensure(c); if (rc) return rc; }
   // one- and two-step maps (newton.py: time derivative of the orbit) run eagerly: capturing six step-class graphs for them
   // costs more than the steps, and their iteration counts say nothing about the budgets of the real maps
-  const bool use_graph = c->use_graph && c->nsteps > 2 && !hostcheck_on(c);
+  const StepForm F = step_form(c);                          // one form for every step of this map, captured or eager, and for its counters
+  const bool use_graph = c->use_graph && c->nsteps > 2 && !F.hostcheck;
   const bool per_step = use_graph && step_budgets_ready(c, adjoint);
   c->last_map_per_step = per_step; c->last_map_kind = adjoint;
   std::vector<hipGraphExec_t> plan;
@@ -2056,16 +2059,16 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
     plan.resize(c->nsteps);
     for (int istep = 1; istep <= c->nsteps; ++istep) {
       const nsk_ctx::StepBudgets& b = c->sb[adjoint];
-      int rc = graph_for(c, adjoint, step_class(istep), b.bh[istep - 1], b.bp[istep - 1], &plan[istep - 1]);
+      int rc = graph_for(c, F, adjoint, step_class(istep), b.bh[istep - 1], b.bp[istep - 1], &plan[istep - 1]);
       if (rc) return rc;
       c->sb_launch_h += b.bh[istep - 1]; c->sb_launch_p += b.bp[istep - 1];
     }
     c->sb_maps++; c->sb_steps += c->nsteps;
-    if (tails_on(c)) c->tail_maps++;
+    if (F.tails) c->tail_maps++;
   } else if (use_graph)
-    for (int k = 0; k < NCLS; ++k) { int rc = ensure_graph(c, k, adjoint); if (rc) return rc; }
+    for (int k = 0; k < NCLS; ++k) { int rc = ensure_graph(c, F, k, adjoint); if (rc) return rc; }
   const int gsteps = (use_graph && !per_step && c->graph_steps > 1 && c->nsteps >= CLS_ISTEP[NCLS - 1] + 2 * c->graph_steps) ? c->graph_steps : 1;
-  if (gsteps > 1) { int rc = ensure_graph_multi(c, adjoint); if (rc) return rc; }
+  if (gsteps > 1) { int rc = ensure_graph_multi(c, F, adjoint); if (rc) return rc; }
   { int rc = state_load(c, q); if (rc) return rc; }
   if (d.bf_stride || d.forb) {
     if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
@@ -2077,10 +2080,10 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
     if (!rc && c->bcv.step0 == 0) rc = bcv_call(G1, nullptr, false);
     if (rc) return rc;
   }
-  if (absorb_on(c)) { c->up_host = true; c->absorb_maps++; }
-  if (convfuse_on(c)) c->convfuse_steps += c->nsteps;
-  if (helmpack_on(c)) c->helmpack_steps += c->nsteps;
-  if (leanargs_on(c)) c->leanargs_steps += c->nsteps;
+  if (F.absorb) { c->up_host = true; c->absorb_maps++; }
+  if (F.convfuse) c->convfuse_steps += c->nsteps;
+  if (F.helmpack) c->helmpack_steps += c->nsteps;
+  if (F.leanargs) c->leanargs_steps += c->nsteps;
   for (int istep = 1; istep <= c->nsteps; ++istep) {
     if (per_step) {
       HIPCHK(hipGraphLaunch(plan[istep - 1], c->stream));
@@ -2092,7 +2095,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
       }
       HIPCHK(hipGraphLaunch(c->graphs[adjoint][step_class(istep)].exec, c->stream));
     } else {
-      int rc = step(c, istep, adjoint, -1, -1, false, true);
+      int rc = step(c, F, istep, adjoint, -1, -1, false, true);
       if (rc) return rc;
       if (c->debug) {
         GmresScal G; double hs[32];
@@ -2169,12 +2172,12 @@ static void step_budgets_update(nsk_ctx* c) {
   b.bh.assign(ns, 0); b.bp.assign(ns, 0);
   // (tail = 2: the budgets below + a persistent tail behind them as a SAFETY NET: a solve that outruns its budget continues
   //  in the tail instead of costing a redone map)
-  const bool net = tails_on(c);
+  const bool net = step_form(c).tails;
   static const int env_h = std::getenv("NSK_SB_HEAD_H") ? std::atoi(std::getenv("NSK_SB_HEAD_H")) : -1;
   static const int env_p = std::getenv("NSK_SB_HEAD_P") ? std::atoi(std::getenv("NSK_SB_HEAD_P")) : -1;
   // (options "tail_off_h" / "tail_off_p" > 0 add to the head-room of the plain budgets too: tests use it for a reference run that cannot overflow)
   const int head_h = (env_h >= 0 ? env_h : (net ? 1 : 3)) + std::max(0, c->tail_off_h), head_p = (env_p >= 0 ? env_p : (net ? 0 : 2)) + std::max(0, c->tail_off_p);
-  if (tails_on(c) && c->tail == 1) {
+  if (net && c->tail == 1) {
     // HEADS for the persistent tails: the MEDIAN count of this step over the window (offline on 56 maps of config 2: the cheapest
     // predictor, 0.44 launches that find nothing to do and 0.56 tail iterations per pressure solve; profiles/r05_step_budgets.txt).
     // Velocity: a solve of I iterations is found finished by launch I (0-based), i.e. I + 1 launches.
@@ -2307,7 +2310,7 @@ static int map_finish(nsk_ctx* c) {
     (void)reset_solver_state(c);        // ... and the next map of this context starts clean
     return fail(NSK_ENAN, "non-finite state inside the map: " + std::to_string((long long)h.nonfinite) + " time steps with a NaN / Inf pressure right-hand side (input vector not finite?)");
   }
-  const bool hcm = hostcheck_on(c);     // host-checked eager steps iterate to the caps whatever the budgets say
+  const bool hcm = step_form(c).hostcheck;     // host-checked eager steps iterate to the caps whatever the budgets say
   if (h.unconverged == 0) {
     if (c->nsteps > 2 && !hcm) { budgets_update(c, h); step_budgets_update(c); }
     c->sb_force_class = false;
@@ -3333,7 +3336,7 @@ static int orbit_integrate(std::vector<nsk_ctx*>& G, bool sharded, const double*
       for (int k = 0; k < narr; ++k) to[k] = c->orbit[k] + (size_t)(istep - 1) * per_step(c);
       if ((rc = launch_baseflow(c, u, to))) return rc;
     }
-    if ((rc = sharded ? group_step(G, istep, 2) : step(G[0], istep, 2))) return rc;
+    if ((rc = sharded ? group_step(G, istep, 2) : step(G[0], step_form(G[0]), istep, 2))) return rc;
   }
   Stats h;
   HIPCHK(hipMemcpyAsync(&h, G[0]->d.stats, sizeof(Stats), hipMemcpyDeviceToHost, G[0]->stream));
@@ -4336,12 +4339,13 @@ int nsk_debug_stamps(nsk_ctx* c, unsigned long long* out, int nblk_max) {
   if (!c || !out) return fail(NSK_EINVAL, "bad argument");
   if (c->cm) return fail(NSK_EINVAL, "nsk_debug_stamps: launches the shared-mask kernel forms only (context of nsk_init_masks)");
   Dev& d = c->d;
+  const StepForm F = step_form(c);                      // the instantiations the context's steps run (options "helm_pack", "lean_args")
   const size_t nrow = (size_t)c->nblk + (size_t)(d.nvert + 7) / 8 + 8;           // (k_schwarz_uc: Schwarz + coarse workgroups)
   if (!d.dbg) { int rc = dalloc(c, &d.dbg, (size_t)16 * nrow); if (rc) return rc; }
   HIPCHK(hipMemset(d.dbg, 0, (size_t)16 * nrow * sizeof(unsigned long long)));
   const char* sk = std::getenv("NSK_STAMP_KERNEL");
   if (sk && (std::string(sk) == "schwarz_uc" || std::string(sk) == "divgs_t")) {
-    if (!fuse2_on(c)) return fail(NSK_EINVAL, "two-launch GMRES iteration not available in this context");
+    if (!F.fuse2) return fail(NSK_EINVAL, "two-launch GMRES iteration not available in this context");
     Dev dd = d; dd.tol_pres = 0.0; dd.tol_relative = 0; dd.pres_cap = 0;
     dd.tc32 = (c->tc32 != 0 && d.Tc32) ? 1 : 0;
     const StepCoef sc = make_coef(c, 17, 0);
@@ -4350,8 +4354,8 @@ int nsk_debug_stamps(nsk_ctx* c, unsigned long long* out, int nblk_max) {
     HIPCHK(hipMemsetAsync((char*)d.gsc + offsetof(GmresScal, done), 0, sizeof(int), c->stream));
     DISPATCH_N(c->key, {
       for (int r = 0; r < 5; ++r) {
-        if (std::string(sk) == "schwarz_uc") { launch_divgs_t<N>(c, dd, jd - 1); launch_schwarz_uc<N>(c, dd, jd, scale, 2, 5); }
-        else { launch_schwarz_uc<N>(c, dd, jd, scale, 2, 5); launch_divgs_t<N>(c, dd, jd); }
+        if (std::string(sk) == "schwarz_uc") { launch_divgs_t<N>(c, F, dd, jd - 1); launch_schwarz_uc<N>(c, F, dd, jd, scale, 2, 5); }
+        else { launch_schwarz_uc<N>(c, F, dd, jd, scale, 2, 5); launch_divgs_t<N>(c, F, dd, jd); }
       }
     });
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -4364,8 +4368,8 @@ int nsk_debug_stamps(nsk_ctx* c, unsigned long long* out, int nblk_max) {
     if (nblk_max < 0) {
       Dev dd = d; dd.tol_helm = 0.0; dd.tol_relative = 0;
       const StepCoef sc = make_coef(c, 3, 0);
-      dd.helm_pk = helmpack_on(c) ? 1 : 0;                   // the instantiation the context's steps run (option "helm_pack")
-      for (int r = 0; r < 6; ++r) launch_helm_iter<N>(c, dd, sc, r, (const double*)d.rloc);
+      dd.helm_pk = F.helmpack ? 1 : 0;
+      for (int r = 0; r < 6; ++r) launch_helm_iter<N>(c, F, dd, sc, r, (const double*)d.rloc);
       nblk_max = -nblk_max;
     } else if (std::getenv("NSK_STAMP_KERNEL") && std::string(std::getenv("NSK_STAMP_KERNEL")) == "divgs_w") {
       for (int r = 0; r < 5; ++r) launch_divgs3<N>(c, d, c->nblk, (const double*)d.yl, c->wp2, -1, 0, 3);
@@ -4510,10 +4514,11 @@ int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
   Dev d = c->d;
+  const StepForm F = step_form(c);                              // the instantiations the context's steps run (options "helm_pack", "lean_args")
   float ms = 0.f;
   if (n == "helm" || n == "helm_wg") {
     d.tol_helm = 0.0; d.tol_relative = 0;                       // never converge: every launch does full work
-    d.helm_pk = helmpack_on(c) ? 1 : 0;                         // the instantiation the context's steps run (option "helm_pack")
+    d.helm_pk = F.helmpack ? 1 : 0;
     const StepCoef sc = make_coef(c, 3, 0);
     const int cyc = 8;
     const int keep_pf = c->helm_pf;
@@ -4521,12 +4526,12 @@ int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
     HIPCHK(hipStreamSynchronize(c->stream));
     DISPATCH_N(c->key, {
       for (int r = 0; r < cyc; ++r) {                             // warm
-        launch_helm_iter<N>(c, d, sc, r % cyc, (const double*)d.rloc);
+        launch_helm_iter<N>(c, F, d, sc, r % cyc, (const double*)d.rloc);
         tot_rows(c, d.hpart + (size_t)(r & 1) * c->hrows * c->nblk, c->hrows, d.htot + (r & 1) * c->hstride);
       }
       HIPCHK(hipEventRecord(e0, c->stream));
       for (int r = 0; r < reps; ++r) {
-        launch_helm_iter<N>(c, d, sc, r % cyc, (const double*)d.rloc);
+        launch_helm_iter<N>(c, F, d, sc, r % cyc, (const double*)d.rloc);
         tot_rows(c, d.hpart + (size_t)(r & 1) * c->hrows * c->nblk, c->hrows, d.htot + (r & 1) * c->hstride);   // use_tot contexts only (a few us, included)
       }
       HIPCHK(hipEventRecord(e1, c->stream));
@@ -4653,11 +4658,11 @@ int nsk_bench_kernel(nsk_ctx* c, const char* name, int reps, double* avg_us) {
         if (r <= 0 || n.rfind("update_coarse", 0) == 0 || n.rfind("schwarz_uc", 0) == 0 || n == "gmres_update") HIPCHK(clear_done());   // (a 4-byte memset node per launch, same for all)
         if (n == "coarse") hipLaunchKernelGGL(k_coarse, dim3((d.nvert + 4 * CROWS_W - 1) / (4 * CROWS_W)), dim3(256), d.coarse_lda * sizeof(double), c->stream, d);
         else if (n.rfind("update_coarse", 0) == 0) launch_update_coarse(c, d, std::atoi(n.c_str() + 13), scale, 2, 5);
-        else if (n.rfind("schwarz_uc", 0) == 0) launch_schwarz_uc<N>(c, d, std::atoi(n.c_str() + 10), scale, 2, 5);
-        else if (n == "divgs_t") launch_divgs_t<N>(c, d, jj);
+        else if (n.rfind("schwarz_uc", 0) == 0) launch_schwarz_uc<N>(c, F, d, std::atoi(n.c_str() + 10), scale, 2, 5);
+        else if (n == "divgs_t") launch_divgs_t<N>(c, F, d, jj);
         else if (n == "pres_chain_fused") {
           HIPCHK(clear_done());
-          for (int j = 0; j < 8; ++j) { launch_schwarz_uc<N>(c, d, j, scale, 2, 5); launch_divgs_t<N>(c, d, j); }
+          for (int j = 0; j < 8; ++j) { launch_schwarz_uc<N>(c, F, d, j, scale, 2, 5); launch_divgs_t<N>(c, F, d, j); }
         }
         else if (n == "divgs2") hipLaunchKernelGGL(k_divgs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)d.yl, d.V + (size_t)(jj + 1) * d.ps, jj, 2);
         else if (n == "schwarz") hipLaunchKernelGGL(k_schwarz<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)(d.V + (size_t)jj * d.ps), d.Z + (size_t)jj * d.npr, 1, 1);
@@ -4788,9 +4793,10 @@ int nsk_test_op3(nsk_ctx* c, int which, const double* in, double* out, int a, in
     HIPCHK(hipMemcpy(d.bloc, d.rloc, nv * sizeof(double), hipMemcpyDeviceToDevice));
     HIPCHK(hipMemset(d.stats, 0, sizeof(Stats)));
     const StepCoef sc = make_coef(c, a, 0);
+    const StepForm F = step_form(c);
     DISPATCH_N(c->key, {
       for (int it = 0; it < c->max_helm; ++it) {
-        launch_helm_iter<N>(c, d, sc, it, (const double*)d.rloc);
+        launch_helm_iter<N>(c, F, d, sc, it, (const double*)d.rloc);
         tot_rows(c, d.hpart + (size_t)(it & 1) * c->hrows * c->nblk, c->hrows, d.htot + (it & 1) * c->hstride);
       }
     });
@@ -4865,7 +4871,7 @@ int nsk_test_pres_solve(nsk_ctx* c, const double* g, double* out, int* iters) {
   HIPCHK(hipMemcpy(d.gpart, part.data(), c->nblk * sizeof(double), hipMemcpyHostToDevice));
   StepCoef sc = make_coef(c, 3, 0);
   const int savep = d.nproj_max; d.nproj_max = 0; c->in_test = 1;
-  int rc = pres_solve_launch(c, 1.0, 3, c->max_pres);
+  int rc = pres_solve_launch(c, step_form(c), 1.0, 3, c->max_pres);
   c->in_test = 0;
   if (rc) return rc;
   sc.h2 = 1.0;

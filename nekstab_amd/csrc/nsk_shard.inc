@@ -602,14 +602,7 @@ static int group_step(std::vector<nsk_ctx*>& G, int istep, int adjoint) {
       if (c->d.forb && adjoint != 2)  // Fourier orbit: the base flow of this step into the rank's steady slot (hexahedra: cUr is the 12-constant array)
         hipLaunchKernelGGL(k_baseflow_fourier<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, c->d, (double*)c->d.cUr, (double*)c->d.cUs,
                            (double*)c->d.GUx, (double*)c->d.GUy, (double*)c->d.GVx, (double*)c->d.GVy);
-      if (c->key == 108 && adjoint != 2 && c->mfma_convect)
-        hipLaunchKernelGGL(nsk::k3::k_convect_mfma8, dim3(c->nel), dim3(512), 0, c->stream, c->d, (const double*)c->d.u, c->d.bf, adjoint);
-      else if (c->key == 110 && adjoint != 2 && c->mfma_convect)
-        hipLaunchKernelGGL(nsk::k3::k_convect_mfma<10>, dim3(c->nel), dim3(512), 0, c->stream, c->d, (const double*)c->d.u, c->d.bf, adjoint);
-      else if (c->key == 110 && adjoint == 2 && c->mfma_convect)
-        hipLaunchKernelGGL(nsk::k3::k_convect_mfma_nl<10>, dim3(c->nel), dim3(1024), 0, c->stream, c->d, (const double*)c->d.u, c->d.bf);
-      else
-        hipLaunchKernelGGL(k_convect<N>, dim3(c->nel), dim3(Cfg<N>::NTD), 0, c->stream, c->d, (const double*)c->d.u, c->d.bf, adjoint);
+      launch_convect<N>(c, c->d, adjoint);
       if (c->force)                     // forced map (nsk_group_forced_map; eager steps only): + B f of the rank's own elements, as step()
         hipLaunchKernelGGL(nsk::sens::k_add_force, dim3((unsigned)((c->d.nloc + 255) / 256)), dim3(256), 0, c->stream, c->d.bf, c->d.cs, c->d.bm1, c->force, c->d.nloc, c->ndim);
       if (c->sfd.on) sfd_call(c, istep - 1);      // SFD map (nsk_group_sfd_map; eager steps only): the rank's own elements, as step()
