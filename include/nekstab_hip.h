@@ -148,7 +148,7 @@ int nsk_set_tolerances(nsk_ctx* ctx, double tol_helm, double tol_pres, int relat
  * "fuse2" (1, default; round 6: the merged pressure GMRES iteration in TWO launches -- k_schwarz_uc: Schwarz workgroups and
  *   coarse-solve workgroups side by side, k_divgs_t: the coarse part through its precomputed image under E; 0 = the three
  *   launches of rounds 3-5), "fuse2_start" (1: the solve starts inside the first of them, no k_gmres_update(-1) launch),
- *   "tc32" (0, default; 1: fp32 copy of the coarse image, moves a map by 2e-8),
+ *   "tc32" (0, default; 1: fp32 copy of the coarse image, moves a map by 2e-8; -1: where the relative tolerance is >= 1e-5),
  * "zero_metrics" (hexahedra; 1, default: arrays of the mapping and of the base-flow constants that are zero on every node -- the
  *   cross terms Nek5000 skips on its undeformed elements, hmholtz.f axhelm / ifdfrm -- are not loaded; 0: every array is loaded,
  *   same bits.  The set-up sets derivatives of the mapping that are rounding noise on every node to zero; NSK_ZERO_METRICS=0 in

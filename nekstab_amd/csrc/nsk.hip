@@ -25,6 +25,7 @@
 
 #include "../../include/nekstab_hip.h"
 #include "nsk_basis.hpp"
+#include "nsk_setup_host.hpp"
 #include "nsk_kernels.hpp"
 #include "nsk_persist.hpp"
 #include "nsk3_kernels.hpp"
@@ -338,7 +339,8 @@ struct nsk_ctx {
   Stats hstats{};
   hipStream_t stream = nullptr;
   std::vector<void*> allocs;
-  std::map<void*, size_t> alloc_bytes;  // size of every device allocation of this context (reset_solver_state)
+  struct MutRec { size_t slot, bytes; };  // a pointer member of this context (its offset inside nsk_ctx; Dev's members through nsk_ctx::d) and the size of its array
+  std::vector<MutRec> mut;              // the mutable solver state THIS context allocated (dalloc_mut; reset_solver_state, nsk_clone)
   // per-time-step iteration record of the last map (Dev::step_iters, copied behind every map): [2 * nsteps] ints
   static constexpr int STEP_CAP = 8192;
   int* h_step_iters = nullptr;          // pinned
@@ -412,15 +414,70 @@ static void invalidate_graphs(nsk_ctx* c) {
   for (auto& b : c->sb) { b.n = 0; b.bh.clear(); b.bp.clear(); }
 }
 
+static int dalloc_bytes(nsk_ctx* c, void** p, size_t bytes) {
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, bytes);
+  if (e != hipSuccess) return fail(NSK_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+  (void)hipMemset(q, 0, bytes);
+  c->allocs.push_back(q);
+  *p = q;
+  return 0;
+}
 template <class T>
 static int dalloc(nsk_ctx* c, T** p, size_t n) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-  if (e != hipSuccess) return fail(NSK_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-  (void)hipMemset(q, 0, std::max<size_t>(n, 1) * sizeof(T));
-  c->allocs.push_back(q);
-  c->alloc_bytes[q] = std::max<size_t>(n, 1) * sizeof(T);
-  *p = (T*)q;
+  return dalloc_bytes(c, (void**)p, std::max<size_t>(n, 1) * sizeof(T));
+}
+// ... of the MUTABLE solver state: what a map may leave behind for the next one (time-stepper lags, CG / GMRES work arrays, the
+// pressure projection space, partial sums, counters).  Allocates like dalloc and enters the array in the context's record
+// (nsk_ctx::mut): reset_solver_state zeroes exactly the record, nsk_clone gives a lane one array of its own per entry.  An array a
+// shard merely inherits from its parent (`d = P->d`) is in the PARENT's record: the parent resets it.
+static int dalloc_mut_bytes(nsk_ctx* c, void** p, size_t bytes) {
+  int rc = dalloc_bytes(c, p, bytes);
+  if (!rc) c->mut.push_back({(size_t)((char*)p - (char*)c), bytes});
+  return rc;
+}
+template <class T>
+static int dalloc_mut(nsk_ctx* c, T** p, size_t n) {
+  return dalloc_mut_bytes(c, (void**)p, std::max<size_t>(n, 1) * sizeof(T));
+}
+// The core of the mutable state, the same in every kind of context (build, build3, shard_fill; a lane gets it from its parent's
+// record): time-stepper fields, CG and GMRES work arrays, per-workgroup partial sums, counters, and the pressure projection space
+// when there is one.  cs / ps: strides of a velocity component / a GMRES basis vector (ghost slots included); ncorn: corners of an
+// element.  hpart and hscal are indexed by nsk_ctx::hrows / hstride, never by their size: the larger (hexahedral) one for all.
+static int alloc_core_state(nsk_ctx* c, int ndim, long long cs, long long ps, long long npr, int nel, int nblk, int ncorn, int nproj_max) {
+  Dev& d = c->d;
+  const size_t v = (size_t)ndim * cs;
+  int rc;
+  if ((rc = dalloc_mut(c, &d.u, v)) || (rc = dalloc_mut(c, &d.p, npr)) || (rc = dalloc_mut(c, &d.plag, npr)) || (rc = dalloc_mut(c, &d.pext, npr)) ||
+      (rc = dalloc_mut(c, &d.ulag, 2 * v)) || (rc = dalloc_mut(c, &d.exlag, 2 * v)) || (rc = dalloc_mut(c, &d.bf, v)) ||
+      (rc = dalloc_mut(c, &d.rloc, v)) || (rc = dalloc_mut(c, &d.bloc, v)) || (rc = dalloc_mut(c, &d.dulag, 3 * v)) ||
+      (rc = dalloc_mut(c, &d.hx, v)) || (rc = dalloc_mut(c, &d.hr, v)) || (rc = dalloc_mut(c, &d.hp, v)) || (rc = dalloc_mut(c, &d.hs, v)) ||
+      (rc = dalloc_mut(c, &d.hwl, 2 * v)) || (rc = dalloc_mut(c, &d.hpart, (size_t)24 * nblk)) || (rc = dalloc_mut(c, &d.hscal, 64)) ||
+      (rc = dalloc_mut(c, &d.V, (size_t)(MAXMR + 1) * ps)) || (rc = dalloc_mut(c, &d.Z, (size_t)MAXMR * npr)) || (rc = dalloc_mut(c, &d.yl, v)) ||
+      (rc = dalloc_mut(c, &d.ec, (size_t)nel * ncorn)) || (rc = dalloc_mut(c, &d.gpart, (size_t)(MAXMR + 2) * nblk)) ||
+      (rc = dalloc_mut(c, &d.gpart2, (size_t)(MAXMR + 2) * nblk)) || (rc = dalloc_mut(c, &d.gsc, 1)) || (rc = dalloc_mut(c, &d.stats, 1)) ||
+      (rc = dalloc_mut(c, &d.xacc, npr))) return rc;
+  if (nproj_max > 0)
+    if ((rc = dalloc_mut(c, &d.PX, (size_t)nproj_max * npr)) || (rc = dalloc_mut(c, &d.PEX, (size_t)nproj_max * npr)) ||
+        (rc = dalloc_mut(c, &d.PD, npr)) || (rc = dalloc_mut(c, &d.PED, npr)) || (rc = dalloc_mut(c, &d.ppart, (size_t)(MAXPROJ + 2) * nblk))) return rc;
+  return 0;
+}
+// the summed rows of the partials (Dev::use_tot; shards: the all-reduced totals), indexed by MAXMR / MAXPROJ, never by their size
+static int alloc_totals(nsk_ctx* c) {
+  Dev& d = c->d;
+  int rc;
+  if ((rc = dalloc_mut(c, &d.htot, 32)) || (rc = dalloc_mut(c, &d.gtot, MAXMR + 8)) || (rc = dalloc_mut(c, &d.gtot2, MAXMR + 8)) || (rc = dalloc_mut(c, &d.ptot, MAXPROJ + 2))) return rc;
+  return 0;
+}
+// what no map hands to the next and every context has of its own: work vectors, one state vector, Krylov scratch, pinned buffers
+static int alloc_scratch(nsk_ctx* c, int ndim, long long cs, long long npr) {
+  int rc;
+  c->kblk = 256;
+  if ((rc = dalloc(c, &c->wv1, (size_t)ndim * cs)) || (rc = dalloc(c, &c->wv2, (size_t)ndim * cs)) || (rc = dalloc(c, &c->wp1, npr)) || (rc = dalloc(c, &c->wp2, npr)) ||
+      (rc = dalloc(c, &c->scratch, (size_t)c->nstate)) ||
+      (rc = dalloc(c, &c->kpart, (size_t)c->kblk * 1024)) || (rc = dalloc(c, &c->kout, 1024)) || (rc = dalloc(c, &c->kptr, 1024))) return rc;
+  if (hipHostMalloc((void**)&c->hpin, 4096 * sizeof(double)) != hipSuccess || hipHostMalloc((void**)&c->hstat_pin, sizeof(Stats)) != hipSuccess)
+    return fail(NSK_ENOMEM, "hipHostMalloc");
   return 0;
 }
 template <class T>
@@ -606,21 +663,74 @@ __global__ void k_gj_update(double* __restrict__ A, int n, int k, const double* 
 // ---------------------------------------------------------------------------
 static int fused_possible(nsk_ctx* c);
 
-// (gid, local index) pairs into ascending (gid, index) order.  The pairs arrive in ascending index, so a counting sort on the
-// gid is stable and O(n): 1 s instead of the 6 s std::sort takes on the 1e8 nodes of config 5.  Sparse numberings (a rank's
-// sub-mesh keeps the global ids) fall back to the comparison sort when the id range is more than 8x the node count.
-static void sort_gid_pairs(std::vector<std::pair<long long, int>>& srt) {
-  const size_t n = srt.size();
-  long long mx = -1;
-  bool neg = false;
-  for (const auto& p : srt) { mx = std::max(mx, p.first); neg = neg || p.first < 0; }
-  if (neg || mx + 1 > 8 * (long long)n + 1024) { std::sort(srt.begin(), srt.end()); return; }
-  std::vector<unsigned> start((size_t)mx + 2, 0u);
-  for (const auto& p : srt) start[(size_t)p.first + 1]++;
-  for (size_t g = 0; g + 1 < start.size(); ++g) start[g + 1] += start[g];
-  std::vector<std::pair<long long, int>> out(n);
-  for (const auto& p : srt) out[start[(size_t)p.first]++] = p;
-  srt.swap(out);
+// The common opening of build and build3, behind their checks of the case: sizes (EPB elements per workgroup), the scalars of Dev,
+// tolerances, the projection-space settings, the context's stream.
+static int build_open(nsk_ctx* c, const nsk_case& cs, int ndim, int EPB) {
+  const int N = cs.lx1, M = N - 2, ND = cs.lxd > 0 ? cs.lxd : 3 * N / 2;
+  auto pw = [&](int a) { return ndim == 3 ? a * a * a : a * a; };
+  c->ndim = ndim; c->N = N; c->NN = pw(N); c->M = M; c->MM = pw(M); c->ND = ND; c->NDD = pw(ND);
+  c->EPB = EPB; c->nel = cs.nel; c->nblk = (cs.nel + EPB - 1) / EPB;
+  c->nloc = (long long)cs.nel * c->NN; c->npr = (long long)cs.nel * c->MM; c->nstate = ndim * c->nloc + c->npr;
+  c->re = cs.re; c->endtime = cs.endtime;
+  if (cs.max_helm_iter > 0) c->max_helm = cs.max_helm_iter;
+  if (cs.max_pres_iter > 0) c->max_pres = std::min(cs.max_pres_iter, 4 * MAXMR);     // beyond MAXMR: restarted GMRES cycles
+  HIPCHK(hipStreamCreate(&c->stream));
+  Dev& d = c->d;
+  d.ndim = ndim; d.nel = cs.nel; d.nblk = c->nblk; d.nloc = c->nloc; d.npr = c->npr; d.nu = 1.0 / cs.re;
+  d.cs = c->nloc; d.ps = c->npr; d.npr_glob = c->npr;          // one rank: no ghost slots
+  d.nranks = 1; d.rank = 0;
+  c->h_gid.assign(cs.gid, cs.gid + c->nloc);
+  d.tol_helm = cs.tol_helm > 0 ? cs.tol_helm : 1e-9;
+  d.tol_pres = cs.tol_pres > 0 ? cs.tol_pres : 1e-7;
+  d.tol_relative = cs.tol_relative; d.max_mr = std::min(c->max_pres, MAXMR); d.has_outflow = cs.has_outflow;
+  // projection space also with the pressure null space (adjoint runs, closed domains): with the restart policy of k_proj_update it
+  // cuts config 4's pressure iterations from 26 to 15 per step (rounds 1-2 switched it off there: their merge policy made such solves slower)
+  d.nproj_max = (cs.has_outflow || !std::getenv("NSK_NO_PROJ_SINGULAR")) ? std::min(cs.nproj, MAXPROJ) : 0;
+  d.proj_restart = 1;
+  if (const char* g = std::getenv("NSK_PROJ_RESTART")) d.proj_restart = std::atoi(g);
+  return 0;
+}
+
+// The environment overrides of the options, read at the end of build (QUAD) and build3 (HEX): a name is invisible to the mesh
+// kind that does not list it.  (NSK_FUSED asks fused_possible, the component-mask refusals ask the context: in the builders.)
+static void env_overrides(nsk_ctx* c) {
+  enum { QUAD = 1, HEX = 2 };
+  static const struct { const char* name; int nsk_ctx::*opt; int lo, hi, kinds; } tab[] = {      // lo > hi: no clamp
+      {"NSK_USE_GRAPH", &nsk_ctx::use_graph, 1, 0, QUAD | HEX},
+      {"NSK_GRAPH_STEPS", &nsk_ctx::graph_steps, 1, 64, QUAD | HEX},
+      {"NSK_HOSTCHECK", &nsk_ctx::hostcheck, 1, 0, QUAD | HEX},
+      {"NSK_DEBUG", &nsk_ctx::debug, 1, 0, QUAD | HEX},
+      {"NSK_MERGED_UPDATE", &nsk_ctx::merged_update, 1, 0, QUAD},
+      {"NSK_FUSE2", &nsk_ctx::fuse2, 1, 0, QUAD},
+      {"NSK_TC32", &nsk_ctx::tc32, 1, 0, QUAD},
+      {"NSK_FUSE2_START", &nsk_ctx::fuse2_start, 1, 0, QUAD},
+      {"NSK_SB_PCT", &nsk_ctx::sb_pct, 1, 0, QUAD},
+      {"NSK_SKIP_CLOSE", &nsk_ctx::skip_close, 1, 0, QUAD},
+      {"NSK_MERGED_ITERS", &nsk_ctx::merged_iters, 0, MAXMR, QUAD},
+      {"NSK_STEP_BUDGETS", &nsk_ctx::step_budgets, 1, 0, QUAD},
+      {"NSK_TAIL", &nsk_ctx::tail, 1, 0, QUAD},
+      {"NSK_TAIL_OFF_H", &nsk_ctx::tail_off_h, 1, 0, QUAD},
+      {"NSK_TAIL_OFF_P", &nsk_ctx::tail_off_p, 1, 0, QUAD},
+      {"NSK_GS_LAG", &nsk_ctx::gs_lag, 1, 0, HEX},
+      {"NSK_FLAT_PROJ", &nsk_ctx::flat_proj, 1, 0, HEX},
+      {"NSK_EAPPLY_PIPE", &nsk_ctx::eapply_pipe, 1, 0, HEX},
+      {"NSK_DIVGS_C3", &nsk_ctx::divgs_c3, 1, 0, HEX},
+      {"NSK_HELM_PF", &nsk_ctx::helm_pf, 1, 0, HEX},
+  };
+  for (const auto& t : tab) {
+    const char* g = (t.kinds & (c->ndim == 3 ? HEX : QUAD)) ? std::getenv(t.name) : nullptr;
+    if (g) c->*t.opt = t.lo > t.hi ? std::atoi(g) : std::max(t.lo, std::min(std::atoi(g), t.hi));
+  }
+}
+
+// the four-integer gather table of a CSR (Dev::gs_tab)
+static std::vector<int4> gs_table(const std::vector<int>& gs_off, const std::vector<int>& gs_idx) {
+  std::vector<int4> tab(gs_off.size() - 1);
+  for (size_t l = 0; l < tab.size(); ++l) {
+    const auto v = nsk_setup::gs_row(&gs_idx[gs_off[l]], (size_t)(gs_off[l + 1] - gs_off[l]));
+    tab[l] = make_int4(v[0], v[1], v[2], v[3]);
+  }
+  return tab;
 }
 
 // dense coarse solve: A_c (nvert x nvert, host) -> its inverse on the device (Gauss-Jordan), fp64 (Dev::Aci) and fp32 with
@@ -654,43 +764,18 @@ static int coarse_dense_inverse(nsk_ctx* c, std::vector<double>& Ac, bool has_ou
 static int build(nsk_ctx* c, const nsk_case& cs) {
   const int N = cs.lx1, NN = N * N, M = N - 2, MM = M * M, ND = cs.lxd > 0 ? cs.lxd : 3 * N / 2, NDD = ND * ND;
   if (cs.ndim != 2) return fail(NSK_EINVAL, "build(): ndim must be 2");
-  const bool timing = std::getenv("NSK_SETUP_TIMING") != nullptr;       // seconds per set-up section on stderr
-  auto t_last = std::chrono::steady_clock::now();
-  auto tick = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "set-up %-44s %7.3f s\n", what, std::chrono::duration<double>(now - t_last).count());
-    t_last = now;
-  };
+  nsk_setup::SectionTimer tick;
   c->ndim = 2; c->key = cs.lx1; c->d.ndim = 2;
   if (!(N == 6 || N == 8 || N == 10 || N == 12)) return fail(NSK_EINVAL, "lx1 must be 6, 8, 10 or 12");
   if (ND != 3 * N / 2) return fail(NSK_EINVAL, "lxd must be 3*lx1/2");
   const int nel = cs.nel;
-  c->N = N; c->NN = NN; c->M = M; c->MM = MM; c->ND = ND; c->NDD = NDD;
-  c->EPB = (256 / NN) > 0 ? 256 / NN : 1;
+  int rc;
+  if ((rc = build_open(c, cs, 2, (256 / NN) > 0 ? 256 / NN : 1))) return rc;
   c->NT = ((c->EPB * NN + 63) / 64) * 64;
   c->NTD = ((NDD + 63) / 64) * 64;
-  c->nel = nel; c->nblk = (nel + c->EPB - 1) / c->EPB;
-  c->nloc = (long long)nel * NN; c->npr = (long long)nel * MM; c->nstate = 2 * c->nloc + c->npr;
-  c->re = cs.re; c->endtime = cs.endtime;
   c->layers = std::max(1, std::min(cs.schwarz_layers > 0 ? cs.schwarz_layers : 1, std::min(4, M)));
-  if (cs.max_helm_iter > 0) c->max_helm = cs.max_helm_iter;
-  if (cs.max_pres_iter > 0) c->max_pres = std::min(cs.max_pres_iter, 4 * MAXMR);     // beyond MAXMR: restarted GMRES cycles
   const long long nloc = c->nloc, npr = c->npr;
-  HIPCHK(hipStreamCreate(&c->stream));
   Dev& d = c->d;
-  d.nel = nel; d.nblk = c->nblk; d.nloc = nloc; d.npr = npr; d.nu = 1.0 / cs.re;
-  d.cs = nloc; d.ps = npr; d.npr_glob = npr;          // one rank: no ghost slots
-  d.nranks = 1; d.rank = 0;
-  c->h_gid.assign(cs.gid, cs.gid + nloc);
-  d.tol_helm = cs.tol_helm > 0 ? cs.tol_helm : 1e-9;
-  d.tol_pres = cs.tol_pres > 0 ? cs.tol_pres : 1e-7;
-  d.tol_relative = cs.tol_relative; d.max_mr = std::min(c->max_pres, MAXMR); d.has_outflow = cs.has_outflow;
-  // projection space also with the pressure null space (adjoint runs, closed domains): with the restart policy of k_proj_update it
-  // cuts config 4's pressure iterations from 26 to 15 per step (rounds 1-2 switched it off there: their merge policy made such solves slower)
-  d.nproj_max = (cs.has_outflow || !std::getenv("NSK_NO_PROJ_SINGULAR")) ? std::min(cs.nproj, MAXPROJ) : 0;
-  d.proj_restart = 1;
-  if (const char* g = std::getenv("NSK_PROJ_RESTART")) d.proj_restart = std::atoi(g);
 
   // ---- bases
   std::vector<double> z1, w1, z2, w2, zd, wd;
@@ -704,7 +789,6 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
       hat[0 * MM + b * M + a] = sm * rm; hat[1 * MM + b * M + a] = sm * rp;
       hat[2 * MM + b * M + a] = sp * rm; hat[3 * MM + b * M + a] = sp * rp;
     }
-  int rc;
   if ((rc = dupload(c, &d.D, D)) || (rc = dupload(c, &d.J12, J12)) || (rc = dupload(c, &d.D12, D12)) ||
       (rc = dupload(c, &d.Jd, Jd)) || (rc = dupload(c, &d.Dd, Dd)) || (rc = dupload(c, &d.hat, hat))) return rc;
 
@@ -777,42 +861,10 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
 
   tick("bases + geometry");
   // ---- gather-scatter CSR from the global numbering
-  std::vector<int> gs_off(nloc + 1), gs_idx(nloc);
-  std::vector<std::pair<long long, int>> srt(nloc);
-  for (long long l = 0; l < nloc; ++l) srt[l] = {cs.gid[l], (int)l};
-  sort_gid_pairs(srt);
-  std::vector<int> grp_start(nloc), grp_cnt(nloc);
-  {
-    std::vector<int> cnt(nloc, 0);
-    long long a = 0;
-    while (a < nloc) {
-      long long b = a;
-      while (b < nloc && srt[b].first == srt[a].first) ++b;
-      for (long long k = a; k < b; ++k) { grp_start[srt[k].second] = (int)a; grp_cnt[srt[k].second] = (int)(b - a); }
-      a = b;
-    }
-    gs_off[0] = 0;
-    for (long long l = 0; l < nloc; ++l) gs_off[l + 1] = gs_off[l] + grp_cnt[l];
-    gs_idx.resize(gs_off[nloc]);
-    for (long long l = 0; l < nloc; ++l)
-      for (int k = 0; k < grp_cnt[l]; ++k) gs_idx[gs_off[l] + k] = srt[grp_start[l] + k].second;
-  }
-  {
-    std::vector<int4> tab(nloc);
-    for (long long l = 0; l < nloc; ++l) {
-      const int n = gs_off[l + 1] - gs_off[l];
-      int v[4] = {-1, -1, -1, -1};
-      if (n <= 4) for (int k = 0; k < n; ++k) v[k] = gs_idx[gs_off[l] + k];
-      else v[0] = -2;
-      tab[l] = make_int4(v[0], v[1], v[2], v[3]);
-    }
-    if ((rc = dupload(c, &d.gs_tab, tab))) return rc;
-  }
-  auto dssum_h = [&](const std::vector<double>& f) {
-    std::vector<double> o(nloc);
-    for (long long l = 0; l < nloc; ++l) { double s = 0; for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) s += f[gs_idx[k]]; o[l] = s; }
-    return o;
-  };
+  std::vector<int> gs_off, gs_idx;
+  nsk_setup::gs_csr(cs.gid, nloc, gs_off, gs_idx);
+  if ((rc = dupload(c, &d.gs_tab, gs_table(gs_off, gs_idx)))) return rc;
+  auto dssum_h = [&](const std::vector<double>& f) { return nsk_setup::dssum_h(gs_off, gs_idx, f); };
   // (component masks, nsk_init_masks: [2][nloc] each, component mc from the caller's cmask[mc]; cs.mask is not read)
   const int nmc = c->cm ? 2 : 1;
   if (c->cm && c->local) return fail(NSK_EINVAL, "component masks: not with a rank-local set-up");
@@ -843,9 +895,7 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
   c->cfl_target = cs.cfl;
   {
     c->h_cflg.resize((size_t)4 * nloc);
-    std::vector<double> dri(N);
-    dri[0] = 1.0 / (z1[1] - z1[0]); dri[N - 1] = 1.0 / (z1[N - 1] - z1[N - 2]);
-    for (int i = 1; i < N - 1; ++i) dri[i] = 1.0 / (0.5 * (z1[i + 1] - z1[i - 1]));
+    const std::vector<double> dri = nsk_setup::dri_table(z1);
     double ctarg = 0;
     for (int e = 0; e < nel; ++e)
       for (int j = 0; j < N; ++j)
@@ -900,24 +950,7 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
 
   tick("dt rule, Jacobi diagonals, uploads");
   // ---- state + solver work arrays
-  if ((rc = dalloc(c, &d.u, 2 * d.cs)) || (rc = dalloc(c, &d.p, npr)) || (rc = dalloc(c, &d.plag, npr)) ||
-      (rc = dalloc(c, &d.pext, npr)) || (rc = dalloc(c, &d.ulag, 4 * d.cs)) || (rc = dalloc(c, &d.exlag, 4 * d.cs)) ||
-      (rc = dalloc(c, &d.bf, 2 * d.cs)) || (rc = dalloc(c, &d.rloc, 2 * d.cs)) || (rc = dalloc(c, &d.bloc, 2 * d.cs)) || (rc = dalloc(c, &d.dulag, 6 * d.cs)) || (rc = dalloc(c, &d.hx, 2 * d.cs)) ||
-      (rc = dalloc(c, &d.hr, 2 * d.cs)) || (rc = dalloc(c, &d.hp, 2 * d.cs)) || (rc = dalloc(c, &d.hs, 2 * d.cs)) ||
-      (rc = dalloc(c, &d.hwl, 4 * d.cs)) || (rc = dalloc(c, &d.hpart, (size_t)16 * c->nblk)) || (rc = dalloc(c, &d.hscal, 32)) ||
-      (rc = dalloc(c, &d.V, (size_t)(MAXMR + 1) * d.ps)) || (rc = dalloc(c, &d.Z, (size_t)MAXMR * npr)) ||
-      (rc = dalloc(c, &d.yl, 2 * d.cs)) || (rc = dalloc(c, &d.ec, (size_t)nel * 4)) ||
-      (rc = dalloc(c, &d.gpart, (size_t)(MAXMR + 2) * c->nblk)) || (rc = dalloc(c, &d.gpart2, (size_t)(MAXMR + 2) * c->nblk)) || (rc = dalloc(c, &d.gsc, 1)) ||
-      (rc = dalloc(c, &d.stats, 1)) || (rc = dalloc(c, &c->wv1, 2 * d.cs)) || (rc = dalloc(c, &c->wv2, 2 * d.cs)) ||
-      (rc = dalloc(c, &c->wp1, npr)) || (rc = dalloc(c, &c->wp2, npr)) || (rc = dalloc(c, &c->scratch, (size_t)c->nstate))) return rc;
-  if (d.nproj_max > 0)
-    if ((rc = dalloc(c, &d.PX, (size_t)d.nproj_max * npr)) || (rc = dalloc(c, &d.PEX, (size_t)d.nproj_max * npr)) ||
-        (rc = dalloc(c, &d.PD, npr)) || (rc = dalloc(c, &d.PED, npr)) || (rc = dalloc(c, &d.ppart, (size_t)(MAXPROJ + 2) * c->nblk))) return rc;
-  if ((rc = dalloc(c, &d.xacc, npr))) return rc;
-  c->kblk = 256;
-  if ((rc = dalloc(c, &c->kpart, (size_t)c->kblk * 1024)) || (rc = dalloc(c, &c->kout, 1024)) || (rc = dalloc(c, &c->kptr, 1024))) return rc;
-  HIPCHK(hipHostMalloc((void**)&c->hpin, 4096 * sizeof(double)));
-  HIPCHK(hipHostMalloc((void**)&c->hstat_pin, sizeof(Stats)));
+  if ((rc = alloc_core_state(c, 2, d.cs, d.ps, npr, nel, c->nblk, 4, d.nproj_max)) || (rc = alloc_scratch(c, 2, d.cs, npr))) return rc;
 
   tick("work arrays");
   // ---- element adjacency (shared GLL nodes)
@@ -983,7 +1016,6 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
     HIPCHK(hipMemcpy(Eblk.data(), dE, Eblk.size() * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipFree(dE));
     c->allocs.erase(std::find(c->allocs.begin(), c->allocs.end(), (void*)dE));
-    c->alloc_bytes.erase((void*)dE);
   }
   auto Eentry = [&](int a, int r, int b, int k) -> double {   // E[(a,r),(b,k)]
     const std::vector<int>& v = nb[b];
@@ -1023,8 +1055,8 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
     int lda = ((nvert + 255) / 256) * 256;
     if (((nvert + 767) / 768) * 768 <= 3072) lda = ((nvert + 767) / 768) * 768;
     d.coarse_lda = lda; c->coarse_lda = lda;
-    if (lda > 3072 && (rc = dalloc(c, &c->rc_big, lda))) return rc;
-    if (lda <= 3072 && (rc = dalloc(c, &d.rch, (size_t)MAXMR * lda))) return rc;     // restriction history (k_update_coarse)
+    if (lda > 3072 && (rc = dalloc_mut(c, &c->rc_big, lda))) return rc;
+    if (lda <= 3072 && (rc = dalloc_mut(c, &d.rch, (size_t)MAXMR * lda))) return rc;     // restriction history (k_update_coarse)
     if (c->local) {
       // rank-local set-up: the rows of the vertices this rank owns (owner = the rank of the lowest element at the vertex; all
       // elements at it, their neighbours and the mass of their nodes are inside the two rings, so these rows are complete);
@@ -1052,7 +1084,7 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
       std::vector<int> ecslot((size_t)nel * 4, 0);
       for (int v = 0; v < nvert; ++v)
         for (int k = 0; k < v_off[v + 1] - v_off[v]; ++k) ecslot[v_ent[v_off[v] + k]] = v * 8 + k;
-      if ((rc = dupload(c, &d.ecslot, ecslot)) || (rc = dalloc(c, &d.ecv, (size_t)8 * d.coarse_lda))) return rc;
+      if ((rc = dupload(c, &d.ecslot, ecslot)) || (rc = dalloc_mut(c, &d.ecv, (size_t)8 * d.coarse_lda))) return rc;
     }
   }
   // ---- round 6 (k_schwarz_uc / k_divgs_t): the image of the coarse prolongation under E, block sparse, from the probed E blocks:
@@ -1097,13 +1129,13 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
       for (int a = 0; a < nel; ++a) for (size_t k = 0; k < vl[a].size(); ++k) evl[(size_t)a * nvl + k] = vl[a][k];
       d.nvl = nvl;
       std::vector<float> Tc32(Tc.begin(), Tc.end());
-      if ((rc = dupload(c, &d.evl, evl)) || (rc = dupload(c, &d.Tc, Tc)) || (rc = dupload(c, &d.Tc32, Tc32)) || (rc = dalloc(c, &d.Wr, (size_t)d.ps))) return rc;
+      if ((rc = dupload(c, &d.evl, evl)) || (rc = dupload(c, &d.Tc, Tc)) || (rc = dupload(c, &d.Tc32, Tc32)) || (rc = dalloc_mut(c, &d.Wr, (size_t)d.ps))) return rc;
     }
   }
   tick("coarse image under E (Tc)");
   c->h_evert = evert;
   if ((rc = dupload(c, &d.v_off, v_off)) || (rc = dupload(c, &d.v_ent, v_ent)) || (rc = dupload(c, &d.evert, evert)) ||
-      (rc = dalloc(c, &d.xc, nvert))) return rc;
+      (rc = dalloc_mut(c, &d.xc, nvert))) return rc;
 
   tick("coarse operator + its inverse");
   // ---- restricted additive Schwarz patches: own Gauss nodes + `layers` rows of every neighbour
@@ -1167,30 +1199,16 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
   // (k_tot2) instead of in every consumer workgroup, which is O(nblk^2)
   if (c->nblk > 1024 || std::getenv("NSK_USE_TOT")) {
     d.use_tot = 1;
-    if ((rc = dalloc(c, &d.htot, 32)) || (rc = dalloc(c, &d.gtot, MAXMR + 8)) || (rc = dalloc(c, &d.gtot2, MAXMR + 8)) || (rc = dalloc(c, &d.ptot, MAXPROJ + 2))) return rc;
+    if ((rc = alloc_totals(c))) return rc;
   }
   for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
   c->bh_n = 0;
-  if ((rc = dalloc(c, &c->sync, 2 * SYNC_WORDS))) return rc;      // two sets: the tails alternate (nsk_persist.hpp)
+  if ((rc = dalloc_mut(c, &c->sync, 2 * SYNC_WORDS))) return rc;      // two sets: the tails alternate (nsk_persist.hpp)
   // persistent velocity solve: available where the grid is resident, OFF by default -- measured on config 2 it is not faster
   // than the launch-per-iteration form (13.6 vs 13.5 us per CG iteration: DESIGN.md section 5); option "fused" / NSK_FUSED=1
   c->fused = 0;
   if (const char* g = std::getenv("NSK_FUSED")) c->fused = std::atoi(g) && fused_possible(c);
-  if (const char* g = std::getenv("NSK_USE_GRAPH")) c->use_graph = std::atoi(g);
-  if (const char* g = std::getenv("NSK_MERGED_UPDATE")) c->merged_update = std::atoi(g);
-  if (const char* g = std::getenv("NSK_FUSE2")) c->fuse2 = std::atoi(g);
-  if (const char* g = std::getenv("NSK_TC32")) c->tc32 = std::atoi(g);
-  if (const char* g = std::getenv("NSK_FUSE2_START")) c->fuse2_start = std::atoi(g);
-  if (const char* g = std::getenv("NSK_SB_PCT")) c->sb_pct = std::atoi(g);
-  if (const char* g = std::getenv("NSK_SKIP_CLOSE")) c->skip_close = std::atoi(g);
-  if (const char* g = std::getenv("NSK_HOSTCHECK")) c->hostcheck = std::atoi(g);
-  if (const char* g = std::getenv("NSK_GRAPH_STEPS")) c->graph_steps = std::max(1, std::min(std::atoi(g), 64));
-  if (const char* g = std::getenv("NSK_MERGED_ITERS")) c->merged_iters = std::max(0, std::min(std::atoi(g), MAXMR));
-  if (const char* g = std::getenv("NSK_DEBUG")) c->debug = std::atoi(g);
-  if (const char* g = std::getenv("NSK_STEP_BUDGETS")) c->step_budgets = std::atoi(g);
-  if (const char* g = std::getenv("NSK_TAIL")) c->tail = std::atoi(g);
-  if (const char* g = std::getenv("NSK_TAIL_OFF_H")) c->tail_off_h = std::atoi(g);
-  if (const char* g = std::getenv("NSK_TAIL_OFF_P")) c->tail_off_p = std::atoi(g);
+  env_overrides(c);
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1633,7 +1651,7 @@ static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, 
       if (done) { c->hc_pres[ord] = 0; np = 0; }
     }
     const bool f2 = merged && F.fuse2;
-    // the fp32 copy of the coarse image where the tolerance of THIS solve is loose (relative, >= 1e-5): option "tc32" = -1 (default) / 0 / 1
+    // the fp32 copy of the coarse image where the tolerance of THIS solve is loose (relative, >= 1e-5): option "tc32" = -1; 0 (default): never, 1: always
     d.tc32 = (c->tc32 < 0) ? ((d.tol_relative && d.tol_pres >= 1e-5 && d.Tc32) ? 1 : 0) : ((c->tc32 && d.Tc32) ? 1 : 0);
     for (int j = 0; j < (tl ? nhead : nm); ++j) {
       if (f2) {                                            // two launches per iteration (round 6)
@@ -2230,16 +2248,8 @@ static void step_budgets_update(nsk_ctx* c) {
 // survive every later map (step 1 multiplies the lags by ZERO coefficients: 0 x Inf = NaN; the projection space is kept from
 // map to map by design).  This is what made BENCH_r04 fail: scripts/repro_r04_nan.py.
 static int reset_solver_state(nsk_ctx* c) {
-  Dev& d = c->d;
-  void* mut[] = {d.u, d.p, d.plag, d.pext, d.ulag, d.exlag, d.bf, d.rloc, d.bloc, d.dulag, d.hx, d.hr, d.hp, d.hs, d.hwl, d.hpart, d.hscal,
-                 d.V, d.Z, d.yl, d.ec, d.ecv, d.Wr, d.xc, d.gpart, d.xacc, d.dpw, d.hz, d.hy, d.rch, d.gsc, d.PX, d.PEX, d.PD, d.PED, d.ppart, d.stats,
-                 d.gpart2, d.gtot2, d.ptot, d.htot, d.gtot, c->rc_big, c->cw_d0, c->cw_d1, c->cw_r, c->circ_rh, c->circ_xh, c->rc_part, c->sync};
-  for (void* p : mut) {
-    if (!p) continue;
-    auto it = c->alloc_bytes.find(p);
-    if (it == c->alloc_bytes.end()) continue;            // (an array this context shares with its parent: the parent resets it)
-    HIPCHK(hipMemsetAsync(p, 0, it->second, c->stream));
-  }
+  // (the record holds what this context allocated: an array it shares with its parent is the parent's to reset)
+  for (const auto& m : c->mut) HIPCHK(hipMemsetAsync(*(void**)((char*)c + m.slot), 0, m.bytes, c->stream));
   c->state_dirty = false;
   c->up_host = false;                                      // (GmresScal::up_pending went with the rest)
   return 0;
@@ -2388,9 +2398,11 @@ int nsk_shard_release_parent(nsk_ctx* P) {
   for (void* p : P->allocs) {
     bool k = false;
     for (const void* q : keep) k = k || (q && q == p);
-    if (k) left.push_back(p); else { (void)hipFree(p); P->alloc_bytes.erase(p); }
+    if (k) left.push_back(p); else (void)hipFree(p);
   }
   P->allocs.swap(left);
+  auto freed = [&](const nsk_ctx::MutRec& m) { return std::find(P->allocs.begin(), P->allocs.end(), *(void**)((char*)P + m.slot)) == P->allocs.end(); };
+  P->mut.erase(std::remove_if(P->mut.begin(), P->mut.end(), freed), P->mut.end());      // (the record follows the arrays)
   for (auto& a : P->graphs) for (auto& g : a) if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; g.nh = -1; }
   P->released = true;
   return 0;
@@ -2911,7 +2923,6 @@ int nsk_vec_free(nsk_ctx* c, int n, nsk_vec* v) {
     if (it == c->allocs.end()) return fail(NSK_EINVAL, "unknown vector handle");
     (void)hipFree(v[k]);
     c->allocs.erase(it);
-    c->alloc_bytes.erase((void*)v[k]);
     v[k] = nullptr;
   }
   return 0;
@@ -4429,31 +4440,11 @@ int nsk_clone(nsk_ctx* P, nsk_ctx** out) {
   d.stepctr = nullptr; d.step_iters = nullptr;            // (the lane's own per-step record is made at its first map)
   const long long npr = c->npr;
   int rc;
-  // the mutable set of build(): time-stepper state, CG / GMRES work arrays, projection space, partial sums, counters
-  if ((rc = dalloc(c, &d.u, 2 * d.cs)) || (rc = dalloc(c, &d.p, npr)) || (rc = dalloc(c, &d.plag, npr)) ||
-      (rc = dalloc(c, &d.pext, npr)) || (rc = dalloc(c, &d.ulag, 4 * d.cs)) || (rc = dalloc(c, &d.exlag, 4 * d.cs)) ||
-      (rc = dalloc(c, &d.bf, 2 * d.cs)) || (rc = dalloc(c, &d.rloc, 2 * d.cs)) || (rc = dalloc(c, &d.bloc, 2 * d.cs)) || (rc = dalloc(c, &d.dulag, 6 * d.cs)) || (rc = dalloc(c, &d.hx, 2 * d.cs)) ||
-      (rc = dalloc(c, &d.hr, 2 * d.cs)) || (rc = dalloc(c, &d.hp, 2 * d.cs)) || (rc = dalloc(c, &d.hs, 2 * d.cs)) ||
-      (rc = dalloc(c, &d.hwl, 4 * d.cs)) || (rc = dalloc(c, &d.hpart, (size_t)16 * c->nblk)) || (rc = dalloc(c, &d.hscal, 32)) ||
-      (rc = dalloc(c, &d.V, (size_t)(MAXMR + 1) * d.ps)) || (rc = dalloc(c, &d.Z, (size_t)MAXMR * npr)) ||
-      (rc = dalloc(c, &d.yl, 2 * d.cs)) || (rc = dalloc(c, &d.ec, (size_t)c->nel * 4)) ||
-      (rc = dalloc(c, &d.gpart, (size_t)(MAXMR + 2) * c->nblk)) || (rc = dalloc(c, &d.gpart2, (size_t)(MAXMR + 2) * c->nblk)) || (rc = dalloc(c, &d.gsc, 1)) ||
-      (rc = dalloc(c, &d.stats, 1)) || (rc = dalloc(c, &c->wv1, 2 * d.cs)) || (rc = dalloc(c, &c->wv2, 2 * d.cs)) ||
-      (rc = dalloc(c, &c->wp1, npr)) || (rc = dalloc(c, &c->wp2, npr)) || (rc = dalloc(c, &c->scratch, (size_t)c->nstate)) ||
-      (rc = dalloc(c, &d.xacc, npr)) || (rc = dalloc(c, &d.xc, c->nvert))) return bail(rc);
-  if (d.nproj_max > 0)
-    if ((rc = dalloc(c, &d.PX, (size_t)d.nproj_max * npr)) || (rc = dalloc(c, &d.PEX, (size_t)d.nproj_max * npr)) ||
-        (rc = dalloc(c, &d.PD, npr)) || (rc = dalloc(c, &d.PED, npr)) || (rc = dalloc(c, &d.ppart, (size_t)(MAXPROJ + 2) * c->nblk))) return bail(rc);
-  if (P->rc_big && (rc = dalloc(c, &c->rc_big, c->coarse_lda))) return bail(rc);
-  if (P->d.rch && (rc = dalloc(c, &d.rch, (size_t)MAXMR * c->coarse_lda))) return bail(rc);
-  if (P->d.ecv && (rc = dalloc(c, &d.ecv, (size_t)8 * c->coarse_lda))) return bail(rc);
-  if (P->d.Wr && (rc = dalloc(c, &d.Wr, (size_t)d.ps))) return bail(rc);            // (Tc / evl are immutable: shared with the parent)
-  if (d.use_tot && ((rc = dalloc(c, &d.htot, 32)) || (rc = dalloc(c, &d.gtot, MAXMR + 8)) || (rc = dalloc(c, &d.gtot2, MAXMR + 8)) || (rc = dalloc(c, &d.ptot, MAXPROJ + 2)))) return bail(rc);
-  if ((rc = dalloc(c, &c->sync, 2 * SYNC_WORDS))) return bail(rc);
-  c->kblk = 256;
-  if ((rc = dalloc(c, &c->kpart, (size_t)c->kblk * 1024)) || (rc = dalloc(c, &c->kout, 1024)) || (rc = dalloc(c, &c->kptr, 1024))) return bail(rc);
-  if (hipHostMalloc((void**)&c->hpin, 4096 * sizeof(double)) != hipSuccess || hipHostMalloc((void**)&c->hstat_pin, sizeof(Stats)) != hipSuccess)
-    return bail(fail(NSK_ENOMEM, "hipHostMalloc"));
+  // the mutable state: one array of the lane's own for every entry of the parent's record, same slot, same size (the parent is a
+  // context of build(): every entry is an array build() allocated); then what no map hands to the next
+  for (const auto& m : P->mut)
+    if ((rc = dalloc_mut_bytes(c, (void**)((char*)c + m.slot), m.bytes))) return bail(rc);
+  if ((rc = alloc_scratch(c, 2, d.cs, npr))) return bail(rc);
   c->bm1s_host = P->bm1s_host;
   if ((rc = ensure_step_record(c))) return bail(rc);
   HIPCHK(hipStreamSynchronize(c->stream));

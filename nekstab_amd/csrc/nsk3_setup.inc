@@ -343,8 +343,8 @@ static int coarse_build3(nsk_ctx* c, std::vector<std::vector<std::pair<int, doub
       }
       { nsk_vec a = dB, b2 = drow, c2 = dcol; nsk_vec_free(c, 1, &a); nsk_vec_free(c, 1, &b2); nsk_vec_free(c, 1, &c2); }
       c->circ_nz = nz; c->circ_nv2 = nv2; c->circ_nmat = nmat; c->circ_lda = lda2; c->circ_Binv = dBinv;
-      if ((rc = dupload(c, &c->circ_F, F)) || (rc = dupload(c, &c->circ_cols, cols)) || (rc = dalloc(c, &c->circ_rh, (size_t)nz * nv2)) ||
-          (rc = dalloc(c, &c->circ_xh, (size_t)nz * nv2))) return rc;
+      if ((rc = dupload(c, &c->circ_F, F)) || (rc = dupload(c, &c->circ_cols, cols)) || (rc = dalloc_mut(c, &c->circ_rh, (size_t)nz * nv2)) ||
+          (rc = dalloc_mut(c, &c->circ_xh, (size_t)nz * nv2))) return rc;
       c->coarse_iter = 1;                                   // same call sites as the polynomial (coarse_iterative dispatches)
       c->coarse_bytes = 4.0 * nmat * nv2 * lda2 + 8.0 * (2.0 * nz * nz + 4.0 * nz * nv2);      // stored inverses (fp32) + the two z-transforms
       d.Aci = nullptr; d.Acif = nullptr;
@@ -440,8 +440,8 @@ static int coarse_build3(nsk_ctx* c, std::vector<std::vector<std::pair<int, doub
       }
     c->cA_width = width;
     if ((rc = dupload(c, &c->cA_rp, rp)) || (rc = dupload(c, &c->cA_ci, eci)) || (rc = dupload(c, &c->cA_va, eva)) ||
-        (rc = dupload(c, &c->cA_dinv, dinvc)) || (rc = dalloc(c, &c->cw_d0, lda)) || (rc = dalloc(c, &c->cw_d1, lda)) ||
-        (rc = dalloc(c, &c->cw_r, lda))) return rc;
+        (rc = dupload(c, &c->cA_dinv, dinvc)) || (rc = dalloc_mut(c, &c->cw_d0, lda)) || (rc = dalloc_mut(c, &c->cw_d1, lda)) ||
+        (rc = dalloc_mut(c, &c->cw_r, lda))) return rc;
     c->coarse_iter = 1;
     c->coarse_bytes = (double)deg * ((double)width * nvert * 12.0 + 5.0 * 8.0 * nvert);       // per degree: padded rows (value + column) + five vectors
     d.Aci = nullptr; d.Acif = nullptr;
@@ -464,63 +464,23 @@ static void parallel_elems(int nel, F&& fn) {
   for (auto& th : pool) th.join();
 }
 
-// [nel][8][8] gather lists of the element corners (Dev::gs_corner): the CSR list of corner node (k, j, i) in {0, N-1}^3 of every
-// element, -1 padded; a list longer than 8 is marked -2 (the kernels then walk the CSR arrays)
-static std::vector<int> corner_table(int N, int nel, const std::vector<int>& gs_off, const std::vector<int>& gs_idx) {
-  std::vector<int> t((size_t)nel * 64, -1);
-  const int NN = N * N * N;
-  for (int e = 0; e < nel; ++e)
-    for (int cc = 0; cc < 8; ++cc) {
-      const int k = (cc & 4) ? N - 1 : 0, j = (cc & 2) ? N - 1 : 0, i = (cc & 1) ? N - 1 : 0;
-      const long long l = (long long)e * NN + (k * N + j) * N + i;
-      const int n = gs_off[l + 1] - gs_off[l];
-      int* row = &t[((size_t)e * 8 + cc) * 8];
-      if (n > 8) { row[0] = -2; continue; }
-      for (int q = 0; q < n; ++q) row[q] = gs_idx[gs_off[l] + q];
-    }
-  return t;
-}
-
 static int build3(nsk_ctx* c, const nsk_case& cs) {
   const int N = cs.lx1, NN = N * N * N, M = N - 2, MM = M * M * M, ND = cs.lxd > 0 ? cs.lxd : 3 * N / 2, NDD = ND * ND * ND;
   if (!(N == 6 || N == 8 || N == 10)) return fail(NSK_EINVAL, "3-D: lx1 must be 6, 8 or 10 in this build");
   if (ND != 3 * N / 2) return fail(NSK_EINVAL, "lxd must be 3*lx1/2");
   if (!cs.z || !cs.wb) return fail(NSK_EINVAL, "3-D case needs z and wb");
   const int nel = cs.nel;
-  const bool timing = std::getenv("NSK_SETUP_TIMING") != nullptr;       // seconds per set-up section on stderr
-  auto t_last = std::chrono::steady_clock::now();
-  auto tick = [&](const char* what) {
-    if (!timing) return;
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "set-up %-44s %7.3f s\n", what, std::chrono::duration<double>(now - t_last).count());
-    t_last = now;
-  };
-  c->ndim = 3; c->key = 100 + N; c->hrows = 12; c->hstride = 16;
+  nsk_setup::SectionTimer tick;
+  c->key = 100 + N; c->hrows = 12; c->hstride = 16;
   if (const char* g = std::getenv("NSK_ZERO_METRICS")) c->zero_metrics = std::atoi(g);
-  c->N = N; c->NN = NN; c->M = M; c->MM = MM; c->ND = ND; c->NDD = NDD;
-  c->EPB = 1; c->NT = ((NN + 63) / 64) * 64; c->NTD = c->NT;
-  c->nel = nel; c->nblk = nel;
-  c->nloc = (long long)nel * NN; c->npr = (long long)nel * MM; c->nstate = 3 * c->nloc + c->npr;
-  c->re = cs.re; c->endtime = cs.endtime;
+  int rc;
+  if ((rc = build_open(c, cs, 3, 1))) return rc;
+  c->NT = ((NN + 63) / 64) * 64; c->NTD = c->NT;
   c->layers = 0;
-  if (cs.max_helm_iter > 0) c->max_helm = cs.max_helm_iter;
-  if (cs.max_pres_iter > 0) c->max_pres = std::min(cs.max_pres_iter, 4 * MAXMR);     // beyond MAXMR: restarted GMRES cycles
   const long long nloc = c->nloc, npr = c->npr;
   const size_t nfine = (size_t)nel * NDD;
-  HIPCHK(hipStreamCreate(&c->stream));
   Dev& d = c->d;
-  d.ndim = 3; d.nfine = (long long)nfine; d.use_tot = 1;
-  d.nel = nel; d.nblk = c->nblk; d.nloc = nloc; d.npr = npr; d.nu = 1.0 / cs.re;
-  d.cs = nloc; d.ps = npr; d.npr_glob = npr; d.nranks = 1; d.rank = 0;
-  c->h_gid.assign(cs.gid, cs.gid + nloc);
-  d.tol_helm = cs.tol_helm > 0 ? cs.tol_helm : 1e-9;
-  d.tol_pres = cs.tol_pres > 0 ? cs.tol_pres : 1e-7;
-  d.tol_relative = cs.tol_relative; d.max_mr = std::min(c->max_pres, MAXMR); d.has_outflow = cs.has_outflow;
-  // projection space also with the pressure null space (adjoint runs, closed domains): with the restart policy of k_proj_update it
-  // cuts config 4's pressure iterations from 26 to 15 per step (rounds 1-2 switched it off there: their merge policy made such solves slower)
-  d.nproj_max = (cs.has_outflow || !std::getenv("NSK_NO_PROJ_SINGULAR")) ? std::min(cs.nproj, MAXPROJ) : 0;
-  d.proj_restart = 1;
-  if (const char* g = std::getenv("NSK_PROJ_RESTART")) d.proj_restart = std::atoi(g);
+  d.nfine = (long long)nfine; d.use_tot = 1;
 
   std::vector<double> z1, w1, z2, w2, zd, wd;
   zwgll(N, z1, w1); zwgl(M, z2, w2); zwgl(ND, zd, wd);
@@ -537,7 +497,6 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
           const double ht = (v & 4) ? 0.5 * (1 + z2[cc]) : 0.5 * (1 - z2[cc]);
           hat[(size_t)v * MM + (cc * M + b) * M + a] = hr * hs * ht;
         }
-  int rc;
   if ((rc = dupload(c, &d.D, D)) || (rc = dupload(c, &d.J12, J12)) || (rc = dupload(c, &d.D12, D12)) ||
       (rc = dupload(c, &d.Jd, Jd)) || (rc = dupload(c, &d.Dd, Dd)) || (rc = dupload(c, &d.hat, hat))) return rc;
 
@@ -664,40 +623,10 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
 
   tick("bases + geometry");
   // ---- gather-scatter CSR from the global numbering
-  std::vector<int> gs_off(nloc + 1), gs_idx;
-  {
-    std::vector<std::pair<long long, int>> srt(nloc);
-    for (long long l = 0; l < nloc; ++l) srt[l] = {cs.gid[l], (int)l};
-    sort_gid_pairs(srt);
-    std::vector<int> grp_start(nloc), grp_cnt(nloc);
-    long long a = 0;
-    while (a < nloc) {
-      long long b = a;
-      while (b < nloc && srt[b].first == srt[a].first) ++b;
-      for (long long k = a; k < b; ++k) { grp_start[srt[k].second] = (int)a; grp_cnt[srt[k].second] = (int)(b - a); }
-      a = b;
-    }
-    gs_off[0] = 0;
-    for (long long l = 0; l < nloc; ++l) gs_off[l + 1] = gs_off[l] + grp_cnt[l];
-    gs_idx.resize(gs_off[nloc]);
-    for (long long l = 0; l < nloc; ++l)
-      for (int k = 0; k < grp_cnt[l]; ++k) gs_idx[gs_off[l] + k] = srt[grp_start[l] + k].second;
-    std::vector<int4> tab(nloc);
-    for (long long l = 0; l < nloc; ++l) {
-      const int n = gs_off[l + 1] - gs_off[l];
-      int v[4] = {-1, -1, -1, -1};
-      if (n <= 4) for (int k = 0; k < n; ++k) v[k] = gs_idx[gs_off[l] + k];
-      else v[0] = -2;
-      tab[l] = make_int4(v[0], v[1], v[2], v[3]);
-    }
-    if ((rc = dupload(c, &d.gs_tab, tab))) return rc;
-    if ((rc = dupload(c, &d.gs_corner, corner_table(N, nel, gs_off, gs_idx)))) return rc;
-  }
-  auto dssum_h = [&](const std::vector<double>& f) {
-    std::vector<double> o(nloc);
-    for (long long l = 0; l < nloc; ++l) { double s = 0; for (int k = gs_off[l]; k < gs_off[l + 1]; ++k) s += f[gs_idx[k]]; o[l] = s; }
-    return o;
-  };
+  std::vector<int> gs_off, gs_idx;
+  nsk_setup::gs_csr(cs.gid, nloc, gs_off, gs_idx);
+  if ((rc = dupload(c, &d.gs_tab, gs_table(gs_off, gs_idx))) || (rc = dupload(c, &d.gs_corner, nsk_setup::corner_table(N, nel, gs_off, gs_idx)))) return rc;
+  auto dssum_h = [&](const std::vector<double>& f) { return nsk_setup::dssum_h(gs_off, gs_idx, f); };
   // (component masks, nsk_init_masks: mask and binv [3][nloc], component mc from the caller's cmask[mc], cs.mask is not read; behind
   //  them what the <.., CM = true> kernel forms load -- nsk3_kernels.hpp, cm_bits: the three masks of a node as the bits of a 32-bit
   //  word behind mask, the unmasked 1 / B as a fourth row of binv)
@@ -741,9 +670,7 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
   c->cfl_target = cs.cfl;
   {
     c->h_cflg.resize((size_t)9 * nloc);
-    std::vector<double> dri(N);
-    dri[0] = 1.0 / (z1[1] - z1[0]); dri[N - 1] = 1.0 / (z1[N - 1] - z1[N - 2]);
-    for (int i = 1; i < N - 1; ++i) dri[i] = 1.0 / (0.5 * (z1[i + 1] - z1[i - 1]));
+    const std::vector<double> dri = nsk_setup::dri_table(z1);
     const double* U[3] = {cs.ub, cs.vb, cs.wb};
     double ctarg = 0;
     for (int e = 0; e < nel; ++e)
@@ -815,26 +742,8 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
   double* bfc = nullptr;
   if ((rc = dalloc(c, &bfc, (size_t)12 * nfine))) return rc;
   d.bfc = bfc; d.cUr = bfc;                                         // nsk_set_baseflow writes through cUr
-  if ((rc = dalloc(c, &d.u, 3 * d.cs)) || (rc = dalloc(c, &d.p, npr)) || (rc = dalloc(c, &d.plag, npr)) ||
-      (rc = dalloc(c, &d.pext, npr)) || (rc = dalloc(c, &d.ulag, 6 * d.cs)) || (rc = dalloc(c, &d.exlag, 6 * d.cs)) ||
-      (rc = dalloc(c, &d.bf, 3 * d.cs)) || (rc = dalloc(c, &d.rloc, 3 * d.cs)) || (rc = dalloc(c, &d.bloc, 3 * d.cs)) ||
-      (rc = dalloc(c, &d.dulag, 9 * d.cs)) || (rc = dalloc(c, &d.hx, 3 * d.cs)) || (rc = dalloc(c, &d.hr, 3 * d.cs)) ||
-      (rc = dalloc(c, &d.hp, 3 * d.cs)) || (rc = dalloc(c, &d.hs, 3 * d.cs)) || (rc = dalloc(c, &d.hwl, 6 * d.cs)) ||
-      (rc = dalloc(c, &d.hpart, (size_t)24 * c->nblk)) || (rc = dalloc(c, &d.hscal, 64)) ||
-      (rc = dalloc(c, &d.V, (size_t)(MAXMR + 1) * d.ps)) || (rc = dalloc(c, &d.Z, (size_t)MAXMR * npr)) ||
-      (rc = dalloc(c, &d.yl, 3 * d.cs)) || (rc = dalloc(c, &d.ec, (size_t)nel * 8)) ||
-      (rc = dalloc(c, &d.gpart, (size_t)(MAXMR + 2) * c->nblk)) || (rc = dalloc(c, &d.gpart2, (size_t)(MAXMR + 2) * c->nblk)) || (rc = dalloc(c, &d.htot, 32)) || (rc = dalloc(c, &d.gtot, MAXMR + 2)) ||
-      (rc = dalloc(c, &d.gtot2, MAXMR + 2)) || (rc = dalloc(c, &d.ptot, MAXPROJ + 2)) || (rc = dalloc(c, &d.gsc, 1)) ||
-      (rc = dalloc(c, &d.stats, 1)) || (rc = dalloc(c, &c->wv1, 3 * d.cs)) || (rc = dalloc(c, &c->wv2, 3 * d.cs)) ||
-      (rc = dalloc(c, &c->wp1, npr)) || (rc = dalloc(c, &c->wp2, npr)) || (rc = dalloc(c, &c->scratch, (size_t)c->nstate))) return rc;
-  if ((rc = dalloc(c, &d.xacc, npr)) || (rc = dalloc(c, &d.dpw, npr))) return rc;
-  if (d.nproj_max > 0)
-    if ((rc = dalloc(c, &d.PX, (size_t)d.nproj_max * npr)) || (rc = dalloc(c, &d.PEX, (size_t)d.nproj_max * npr)) ||
-        (rc = dalloc(c, &d.PD, npr)) || (rc = dalloc(c, &d.PED, npr)) || (rc = dalloc(c, &d.ppart, (size_t)(MAXPROJ + 2) * c->nblk))) return rc;
-  c->kblk = 256;
-  if ((rc = dalloc(c, &c->kpart, (size_t)c->kblk * 1024)) || (rc = dalloc(c, &c->kout, 1024)) || (rc = dalloc(c, &c->kptr, 1024))) return rc;
-  HIPCHK(hipHostMalloc((void**)&c->hpin, 4096 * sizeof(double)));
-  HIPCHK(hipHostMalloc((void**)&c->hstat_pin, sizeof(Stats)));
+  if ((rc = alloc_core_state(c, 3, d.cs, d.ps, npr, nel, c->nblk, 8, d.nproj_max)) || (rc = alloc_totals(c)) || (rc = dalloc_mut(c, &d.dpw, npr)) ||
+      (rc = alloc_scratch(c, 3, d.cs, npr))) return rc;
 
   tick("work arrays");
   // ---- base-flow constants on the dealiasing mesh (device)
@@ -1025,7 +934,7 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
         }
         if (std::getenv("NSK_DEBUG")) fprintf(stderr, "velocity solves: %d of %d elements take a fast-diagonalisation block (aspect ratio >= %.1f)\n", nblock, nel, amin);
         if ((rc = dupload(c, &d.hfT, hfT))) return rc;
-        if ((rc = dupload(c, &d.hfS, hfS)) || (rc = dupload(c, &d.hfL, hfL)) || (rc = dalloc(c, &d.hz, 3 * d.cs)) || (rc = dalloc(c, &d.hy, 3 * d.cs))) return rc;
+        if ((rc = dupload(c, &d.hfS, hfS)) || (rc = dupload(c, &d.hfL, hfL)) || (rc = dalloc_mut(c, &d.hz, 3 * d.cs)) || (rc = dalloc_mut(c, &d.hy, 3 * d.cs))) return rc;
         d.helm_fdm = 1;
       }
     }
@@ -1083,7 +992,7 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
   const int lda = ((nvert + 255) / 256) * 256;
   d.coarse_lda = lda; c->coarse_lda = lda;
   if ((rc = dupload(c, &d.v_off, v_off)) || (rc = dupload(c, &d.v_ent, v_ent)) || (rc = dupload(c, &d.evert, evert)) ||
-      (rc = dalloc(c, &d.xc, nvert)) || (rc = dalloc(c, &c->rc_big, lda))) return rc;
+      (rc = dalloc_mut(c, &d.xc, nvert)) || (rc = dalloc_mut(c, &c->rc_big, lda))) return rc;
   d.vtab = nullptr; d.p_inv = nullptr; d.p_stride = 0;
   {
     // vertex graph: neighbours share an element
@@ -1149,21 +1058,13 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
   tick("coarse operator probed + coarse solve built");
   for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
   d.proj_reset = 1;       // hexahedra: a map that starts from the previous map's projection space needs 15-20 % more Helmholtz iterations (DESIGN section 8)
-  if (const char* g = std::getenv("NSK_USE_GRAPH")) c->use_graph = std::atoi(g);
-  if (const char* g = std::getenv("NSK_GS_LAG")) c->gs_lag = std::atoi(g);
-  if (const char* g = std::getenv("NSK_FLAT_PROJ")) c->flat_proj = std::atoi(g);
-  if (const char* g = std::getenv("NSK_EAPPLY_PIPE")) c->eapply_pipe = std::atoi(g);
-  if (const char* g = std::getenv("NSK_DIVGS_C3")) c->divgs_c3 = std::atoi(g);
-  if (const char* g = std::getenv("NSK_HELM_PF")) c->helm_pf = std::atoi(g);
+  env_overrides(c);
   if (c->cm) {
     // component masks (nsk_init_masks): k_divgs_w has no such form.  Asked for through the environment: refused.
     const char* dw = std::getenv("NSK_DIVGS_WAVE");
     if (c->eapply_pipe == 3 || (dw && std::atoi(dw) != 0))
       return fail(NSK_EINVAL, "NSK_EAPPLY_PIPE=3 / NSK_DIVGS_WAVE: the wavefront divergence kernel (k_divgs_w) has no component-mask form (context of nsk_init_masks)");
   }
-  if (const char* g = std::getenv("NSK_GRAPH_STEPS")) c->graph_steps = std::max(1, std::min(std::atoi(g), 64));
-  if (const char* g = std::getenv("NSK_HOSTCHECK")) c->hostcheck = std::atoi(g);
-  if (const char* g = std::getenv("NSK_DEBUG")) c->debug = std::atoi(g);
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }

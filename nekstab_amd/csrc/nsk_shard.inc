@@ -161,31 +161,18 @@ static int shard_fill(nsk_ctx* c, nsk_ctx* P, const int* part, int rank, int nra
   }
   c->nvh = (int)vh_off.size() - 1;
   // gather tables: local copies (ascending) then the ghost slots of every sharing peer
-  std::vector<long long> order(nloc);
   std::vector<int4> tab(nloc);
   std::vector<int> gs_off(nloc + 1, 0), gs_idx;
   {
-    std::map<long long, std::vector<int>> copies;
-    std::vector<std::pair<long long, int>> srt(nloc);
-    for (long long l = 0; l < nloc; ++l) srt[l] = {lgid[l], (int)l};
-    std::sort(srt.begin(), srt.end());
-    std::vector<int> first(nloc), cnt(nloc);
-    for (long long a = 0; a < nloc;) {
-      long long b = a;
-      while (b < nloc && srt[b].first == srt[a].first) ++b;
-      for (long long k = a; k < b; ++k) { first[srt[k].second] = (int)a; cnt[srt[k].second] = (int)(b - a); }
-      a = b;
-    }
+    std::vector<int> loc_off, loc_idx, ent;
+    nsk_setup::gs_csr(lgid.data(), nloc, loc_off, loc_idx);
     for (long long l = 0; l < nloc; ++l) {
-      std::vector<int> ent;
-      for (int k = 0; k < cnt[l]; ++k) ent.push_back(srt[first[l] + k].second);
+      ent.assign(loc_idx.begin() + loc_off[l], loc_idx.begin() + loc_off[l + 1]);
       const long long g = lgid[l];
       if (rmask[g] & ~(1u << rank))
         for (int p = 0; p < nranks; ++p)
           if (p != rank && (rmask[g] & (1u << p))) ent.push_back((int)nloc + slot[{p, g}]);
-      int v[4] = {-1, -1, -1, -1};
-      if (ent.size() <= 4) for (size_t k = 0; k < ent.size(); ++k) v[k] = ent[k];
-      else v[0] = -2;
+      const auto v = nsk_setup::gs_row(ent.data(), ent.size());
       tab[l] = make_int4(v[0], v[1], v[2], v[3]);
       gs_idx.insert(gs_idx.end(), ent.begin(), ent.end());
       gs_off[l + 1] = (int)gs_idx.size();
@@ -303,29 +290,19 @@ static int shard_fill(nsk_ctx* c, nsk_ctx* P, const int* part, int rank, int nra
     if ((rc = dupload(c, &d.v_off, v_off)) || (rc = dupload(c, &d.v_ent, v_ent))) return rc;
   }
   d.gs_corner = nullptr; d.dpw = nullptr;                  // (shards run the element-kernel forms of the once-per-step sums)
-  if (c->ndim == 3 && (rc = dupload(c, &d.gs_corner, corner_table(c->N, nel, gs_off, gs_idx)))) return rc;
+  if (c->ndim == 3 && (rc = dupload(c, &d.gs_corner, nsk_setup::corner_table(c->N, nel, gs_off, gs_idx)))) return rc;
   if ((rc = dupload(c, &d.gs_tab, tab)) || (rc = dupload(c, &d.gs_off, gs_off)) || (rc = dupload(c, &d.gs_idx, gs_idx)) ||
       (rc = dupload(c, &d.p_idx, p_idx)) || (rc = dupload(c, &c->vh_off, vh_off)) || (rc = dupload(c, &c->vh_idx, vh_idx)) ||
       (rc = dupload(c, &c->ph_sidx, ph_sidx))) return rc;
   // ---- rank-local state and work arrays
   const long long cs = d.cs;
-  if ((rc = dalloc(c, &d.u, nd * cs)) || (rc = dalloc(c, &d.p, npr)) || (rc = dalloc(c, &d.plag, npr)) || (rc = dalloc(c, &d.pext, npr)) ||
-      (rc = dalloc(c, &d.ulag, 2 * nd * cs)) || (rc = dalloc(c, &d.exlag, 2 * nd * cs)) || (rc = dalloc(c, &d.bf, nd * cs)) ||
-      (rc = dalloc(c, &d.rloc, nd * cs)) || (rc = dalloc(c, &d.bloc, nd * cs)) || (rc = dalloc(c, &d.dulag, 3 * nd * cs)) ||
-      (rc = dalloc(c, &d.hx, nd * cs)) || (rc = dalloc(c, &d.hr, nd * cs)) || (rc = dalloc(c, &d.hp, nd * cs)) || (rc = dalloc(c, &d.hs, nd * cs)) ||
-      (rc = dalloc(c, &d.hwl, 2 * nd * cs)) || (rc = dalloc(c, &d.hpart, (size_t)24 * c->nblk)) || (rc = dalloc(c, &d.hscal, 64)) ||
-      (rc = dalloc(c, &d.V, (size_t)(MAXMR + 1) * d.ps)) || (rc = dalloc(c, &d.Z, (size_t)MAXMR * npr)) || (rc = dalloc(c, &d.yl, nd * cs)) ||
-      (rc = dalloc(c, &d.ec, (size_t)nel * NCORN)) || (rc = dalloc(c, &d.xc, P->nvert)) || (rc = dalloc(c, &d.gpart, (size_t)(MAXMR + 2) * c->nblk)) ||
-      (rc = dalloc(c, &d.gpart2, (size_t)(MAXMR + 2) * c->nblk)) ||
-      (rc = dalloc(c, &d.gsc, 1)) || (rc = dalloc(c, &d.xacc, npr)) || (rc = dalloc(c, &d.stats, 1)) || (rc = dalloc(c, &d.htot, 32)) || (rc = dalloc(c, &d.gtot, MAXMR + 8)) ||
-      (rc = dalloc(c, &d.gtot2, MAXMR + 8)) || (rc = dalloc(c, &d.ptot, MAXPROJ + 2)) ||
+  // (of the parent's mutable arrays a shard keeps, through `d = P->d` and the copies above: rch, Wr / hz, hy, cw_*, circ_*; they stay
+  //  in the parent's record)
+  if ((rc = alloc_core_state(c, nd, cs, d.ps, npr, nel, c->nblk, NCORN, d.nproj_max)) || (rc = alloc_totals(c)) ||
+      (rc = dalloc_mut(c, &d.xc, P->nvert)) || (rc = dalloc_mut(c, &c->rc_part, c->coarse_lda)) ||
       (rc = dalloc(c, &c->vsend, (size_t)4 * std::max(c->nvh, 1))) || (rc = dalloc(c, &c->vrecv, (size_t)4 * std::max(c->nvh, 1))) ||
       (rc = dalloc(c, &c->psend, std::max(c->nps, 1))) || (rc = dalloc(c, &c->precv, std::max(c->npg, 1))) ||
-      (rc = dalloc(c, &c->rc_part, c->coarse_lda)) || (rc = dalloc(c, &c->scratch, (size_t)c->nstate)) ||
-      (rc = dalloc(c, &c->wv1, nd * cs)) || (rc = dalloc(c, &c->wv2, nd * cs)) || (rc = dalloc(c, &c->wp1, npr)) || (rc = dalloc(c, &c->wp2, npr))) return rc;
-  if (d.nproj_max > 0)
-    if ((rc = dalloc(c, &d.PX, (size_t)d.nproj_max * npr)) || (rc = dalloc(c, &d.PEX, (size_t)d.nproj_max * npr)) ||
-        (rc = dalloc(c, &d.PD, npr)) || (rc = dalloc(c, &d.PED, npr)) || (rc = dalloc(c, &d.ppart, (size_t)(MAXPROJ + 2) * c->nblk))) return rc;
+      (rc = alloc_scratch(c, nd, cs, npr))) return rc;
   {
     std::vector<int2> seg(std::max(c->nvh, 1), make_int2(0, 0));      // halo slot -> {first slot, slot count} of its peer (packed messages)
     for (size_t pi = 0; pi < c->peers.size(); ++pi)
@@ -333,10 +310,6 @@ static int shard_fill(nsk_ctx* c, nsk_ctx* P, const int* part, int rank, int nra
     if ((rc = dupload(c, &c->vh_seg, seg))) return rc;
   }
   c->mfma_convect = P->mfma_convect; c->helm_pf = P->helm_pf; c->helm_pf_grid = P->helm_pf_grid; c->debug = P->debug; c->gmres_cycle = P->gmres_cycle; c->gs2_from = P->gs2_from;
-  c->kblk = 256;
-  if ((rc = dalloc(c, &c->kpart, (size_t)c->kblk * 1024)) || (rc = dalloc(c, &c->kout, 1024)) || (rc = dalloc(c, &c->kptr, 1024))) return rc;
-  HIPCHK(hipHostMalloc((void**)&c->hpin, 4096 * sizeof(double)));
-  HIPCHK(hipHostMalloc((void**)&c->hstat_pin, sizeof(Stats)));
   HIPCHK(hipStreamSynchronize(P->stream));
   return 0;
 }
