@@ -39,6 +39,7 @@ module nekstab_hip
     integer(c_long_long) :: convfuse_steps
     integer(c_long_long) :: helmpack_steps
     integer(c_long_long) :: leanargs_steps
+    integer(c_long_long) :: idxfirst_steps
   end type
 
   interface

@@ -409,6 +409,9 @@ typedef struct {
   long long leanargs_steps;                 /* time steps since init whose iteration kernels (k_helm, k_schwarz_uc, k_divgs_t) took their arguments as compact
                                                blocks (option "lean_args"; a redone map counts again).  0 wherever the option does not apply: hexahedra,
                                                shards, the persistent velocity solve */
+  long long idxfirst_steps;                 /* time steps since init whose k_divgs_t_l (B_j of the pressure iteration) loaded its gather-table entry together
+                                               with the convergence flag (option "idx_first"; a redone map counts again).  0 wherever the compact blocks do
+                                               not run: hexahedra, shards, the persistent velocity solve, lean_args = 0 */
 } nsk_stats;
 int nsk_get_stats(nsk_ctx* ctx, nsk_stats* s);
 

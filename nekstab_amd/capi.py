@@ -48,7 +48,7 @@ class NskStats(C.Structure):
                 ("step_budget_maps", C.c_longlong), ("step_budget_helm_mean", C.c_double), ("step_budget_pres_mean", C.c_double),
                 ("tail_maps", C.c_longlong), ("zero_arrays", C.c_longlong), ("absorb_maps", C.c_longlong),
                 ("convfuse_steps", C.c_longlong), ("helmpack_steps", C.c_longlong),
-                ("leanargs_steps", C.c_longlong)]
+                ("leanargs_steps", C.c_longlong), ("idxfirst_steps", C.c_longlong)]
 
 
 # every symbol include/nekstab_hip.h declares: (restype, argtypes)

@@ -108,8 +108,15 @@ template <int N> static auto pick_pres_tail2(int nit, bool cm) {
 template <int N> static auto pick_helm_lean(bool pk, bool cm) {
   return with_bool(pk, [&](auto PK) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_helm_l<N, decltype(PK)::value, decltype(CM)::value>; }); });
 }
-template <int N> static auto pick_divgs_t_lean(bool t32, bool cm) {
-  return with_bool(t32, [&](auto T32) { return with_bool(cm, [](auto CM) { return &nsk::k2::k_divgs_t_l<N, decltype(T32)::value, decltype(CM)::value>; }); });
+// (ifirst: option "idx_first", B's gather-table entry in flight with the flag and its gathers first behind the flag test)
+// (lx1 = 8 on the fp32 coarse image, option "tc32": 128 registers today, 134 in the new order -- a wavefront per SIMD fewer; that one
+//  keeps today's order)
+template <int N> static auto pick_divgs_t_lean(bool t32, bool cm, bool ifirst) {
+  return with_bool(t32, [&](auto T32) { return with_bool(cm, [&](auto CM) {
+    constexpr bool t = decltype(T32)::value, m = decltype(CM)::value;
+    if constexpr (N == 8 && t) return &nsk::k2::k_divgs_t_l<N, t, m, false>;
+    else return with_bool(ifirst, [](auto IF) { return &nsk::k2::k_divgs_t_l<N, t, m, decltype(IF)::value>; });
+  }); });
 }
 template <int N> static auto pick_schwarz_uc_lean(int nit) { return with_nit(nit, [](auto NIT) { return &nsk::k2::k_schwarz_uc_l<N, decltype(NIT)::value>; }); }
 static nsk::HelmRest helm_rest(const nsk::Dev& d, const nsk::StepCoef& sc, const double* rhs) {
@@ -250,6 +257,8 @@ struct nsk_ctx {
   long long absorb_maps = 0;             // maps run with the deferred update of the projection space (option "proj_absorb")
   long long helmpack_steps = 0;          // time steps whose velocity solve ran on the packed scratch arrays (option "helm_pack")
   long long leanargs_steps = 0;          // time steps whose iteration kernels took the compact argument blocks (option "lean_args")
+  long long idxfirst_steps = 0;          // time steps whose k_divgs_t_l loaded its gather-table entry with the flag (option "idx_first")
+  int idx_first = -1;                   // k_divgs_t_l<.., true>: the gather-table entry leaves with the flag load, the yl gathers go first behind the flag test and the coarse values come off the first barrier's wait (divgs_t_body<.., IF>): -1 = where the compact blocks run and it pays (StepForm::idxfirst: lx1 <= 10), 0 = never, 1 = wherever the compact blocks run; option "idx_first"
   int lean_args = -1;                   // k_helm, k_schwarz_uc and k_divgs_t on compact argument blocks (k_helm_l, k_schwarz_uc_l, k_divgs_t_l; nsk_dev.hpp) instead of Dev by value: -1 = where allowed (StepForm::leanargs), 0 = never, 1 = the same as -1 (every other context ignores it); option "lean_args"
   int helm_pack = -1;                   // 16-byte accesses in the quadrilateral velocity solve (k_helm<N, true>, k_helm_tail<N, true>, k_pres_rhs<N, .., true>): -1 = where allowed and where it pays (StepForm::helmpack: lx1 <= 10), 0 = never, 1 = wherever allowed; option "helm_pack"
   long long convfuse_steps = 0;          // time steps run with convection and the velocity right-hand side in one launch (option "conv_fuse")
@@ -1272,6 +1281,11 @@ struct StepForm {
   // (eager) steps included.  Shards, hexahedra and the persistent velocity solve (k_helm_fused) never reach these launches or keep
   // Dev, whatever the option says; the persistent tails keep Dev and share the bodies.
   bool leanargs = false;
+  // B_j of the pressure iteration with its gather-table entry in flight with the flag (option "idx_first"): exactly where the compact
+  // blocks run -- the load needs the preloaded head.  The persistent tails share the body and keep today's order; A_j (k_schwarz_uc_l)
+  // keeps it too: the same change there measured nothing.  lx1 = 12 takes it only when the option is 1: config 3
+  // measured 0.357 -> 0.352 matvecs/s with it, as helm_pack there.
+  bool idxfirst = false;
   // Persistent tails behind the per-step budgets (option "tail"): graph-replayed quadrilateral single-rank contexts with the merged
   // bookkeeping whose two tail kernels are resident (nsk_ctx::tail_ok, asked once)
   bool tails = false;
@@ -1326,6 +1340,7 @@ static StepForm step_form(nsk_ctx* c) {
   F.convfuse = c->conv_fuse != 0 && quad1 && !c->force && !c->sfd.on && !c->in_test;
   F.helmpack = c->helm_pack != 0 && quad1 && !(c->helm_pack < 0 && c->N > 10);
   F.leanargs = c->lean_args != 0 && quad1;
+  F.idxfirst = c->idx_first != 0 && F.leanargs && !(c->idx_first < 0 && c->N > 10);
   F.gs_lag = hex && (c->gs_lag >= 0 ? c->gs_lag != 0 : rank1);
   F.flat_proj = hex && d.dpw && (c->flat_proj >= 0 ? c->flat_proj != 0 : rank1);
   // (F.merged: Dev::rch exists only with the dense coarse solve, so nothing is asked of coarse_lda that the tails did not ask before)
@@ -1383,7 +1398,7 @@ template <int N>
 static void launch_divgs_t(nsk_ctx* c, const StepForm& F, const Dev& d, int j) {
   if (c->ndim != 2) return;
   if (F.leanargs) {
-    hipLaunchKernelGGL(pick_divgs_t_lean<N>(d.tc32, c->cm), dim3(c->nblk), dim3(256), 0, c->stream, d.gsc, d.gs_tab, d.nel, d.boff, (unsigned)c->nblk, j, divgs_rest(d));
+    hipLaunchKernelGGL(pick_divgs_t_lean<N>(d.tc32, c->cm, F.idxfirst), dim3(c->nblk), dim3(256), 0, c->stream, d.gsc, d.gs_tab, d.nel, d.boff, (unsigned)c->nblk, j, divgs_rest(d));
     return;
   }
   hipLaunchKernelGGL(pick_divgs_t<N>(d.tc32, c->cm), dim3(c->nblk), dim3(256), 0, c->stream, d, j);
@@ -1888,6 +1903,7 @@ static int step(nsk_ctx* c, const StepForm& F, int istep, int adjoint, int nh_ov
   d.helm_pk = da.helm_pk = hpk ? 1 : 0;
   if (hpk && !in_map) c->helmpack_steps++;
   if (F.leanargs && !in_map) c->leanargs_steps++;
+  if (F.idxfirst && !in_map) c->idxfirst_steps++;
   if (cfuse) da.bstep_late = ((d.bf_stride || d.forb) && adjoint != 2) ? 1 : 0;
   if (cfuse && !in_map) c->convfuse_steps++;            // (the steps of a map are counted by run_map: a captured step is replayed)
   int nh = hc ? c->max_helm : (nh_over > 0 ? nh_over : c->cur_helm[sc.cls]);
@@ -2102,6 +2118,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   if (F.convfuse) c->convfuse_steps += c->nsteps;
   if (F.helmpack) c->helmpack_steps += c->nsteps;
   if (F.leanargs) c->leanargs_steps += c->nsteps;
+  if (F.idxfirst) c->idxfirst_steps += c->nsteps;
   for (int istep = 1; istep <= c->nsteps; ++istep) {
     if (per_step) {
       HIPCHK(hipGraphLaunch(plan[istep - 1], c->stream));
@@ -2836,6 +2853,11 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
     c->lean_args = (int)value;
     invalidate_graphs(c);
   }
+  else if (n == "idx_first") {
+    if (value != -1.0 && value != 0.0 && value != 1.0) return fail(NSK_EINVAL, "idx_first: -1, 0 or 1");
+    c->idx_first = (int)value;
+    invalidate_graphs(c);
+  }
   else if (n == "fuse2_start") { c->fuse2_start = (int)value; invalidate_graphs(c); }
   else if (n == "sb_pct") { c->sb_pct = (int)value; }
   else if (n == "skip_close") { c->skip_close = (int)value; invalidate_graphs(c); }
@@ -3006,6 +3028,7 @@ int nsk_get_stats(nsk_ctx* c, nsk_stats* s) {
   s->convfuse_steps = c->convfuse_steps;
   s->helmpack_steps = c->helmpack_steps;
   s->leanargs_steps = c->leanargs_steps;
+  s->idxfirst_steps = c->idxfirst_steps;
   s->zero_arrays = (long long)c->d.zmask | ((long long)c->d.bfmask << 12);
   s->step_budget_helm_mean = c->sb_maps ? (double)c->sb_launch_h / ((double)c->sb_steps) : 0.0;
   s->step_budget_pres_mean = c->sb_maps ? (double)c->sb_launch_p / ((double)c->sb_steps) : 0.0;

@@ -2675,8 +2675,21 @@ __global__ __launch_bounds__(256, 3) void k_schwarz_uc_l(GmresScal* gsc, const i
 // full wait per load (seen in the instruction stream of the first cut: twenty dependent trips for the fp32 copy).
 constexpr int UC_NVL = 20;
 // CM (contexts of nsk_init_masks): B^-1 mask per component, as divgs_body<N, true>; Tc is the image under the same operator
-template <int N, bool T32, bool SLIM = false, bool CM = false, class A = Dev>
+//
+// IF (option "idx_first", k_divgs_t_l only): today's order is flag -> first trip (gs_tab entry, evl, evert, Tc, basis, metrics)
+// -> second trip (yl through the table entry, xc through evl / evert) -> staging -> first barrier.  With IF the table entry
+// leaves WITH the flag, from the clamped address (16 B per lane: what a launch that finds the solve finished pays, as in
+// helm_body), and behind the flag test the loads go out in the order the first barrier needs them (loads return in issue order):
+//   (1) what the staging needs and every lane can address -- binv, J12, D12, hat -- and the indices evl, evert,
+//   (2) the yl gathers of both components,
+//   (3) everything else (Tc, basis, metrics, Z),
+// so that ONE counted wait, which leaves (3) in flight, stands in front of the staging of su.  The coarse values xc[evl], xc[evert]
+// go out behind that wait and are staged (sxc) behind the first contraction pass, in front of tile_barrier: sxc of an element
+// is written by the lanes nd < NVL of the element and read by its lanes nd < MM -- at lx1 = 8 the same wavefront (tile_barrier
+// is then the wave's own wait), otherwise tile_barrier is the workgroup's barrier.  No operation and no summation order moves.
+template <int N, bool T32, bool SLIM = false, bool CM = false, bool IF = false, class A = Dev>
 __device__ __forceinline__ void divgs_t_body(const A& d, int j, const unsigned bx_, const unsigned gx_) {
+  static_assert(!(IF && SLIM), "idx_first: the register form only");
   using C = Cfg<N>;
   constexpr int NN = C::NN, M = C::M, MM = C::MM, EPB = C::EPB, NM = N * M;
   constexpr int NVL = UC_NVL;
@@ -2690,6 +2703,8 @@ __device__ __forceinline__ void divgs_t_body(const A& d, int j, const unsigned b
   const bool act = (el < EPB) && (e < d.nel);
   NSK_STAMP(0);
   const int dn = d.gsc->done;
+  int4 tabf = make_int4(0, 0, 0, 0);
+  if constexpr (IF) tabf = d.gs_tab[(act ? e : 0) * NN + nd];      // (clamped address: lanes without an element drop what they gather)
   arg_batch(d);                                // (compact argument blocks: the rest of the arguments in one batch, in flight with the flag)
   if (dn) return;
   NSK_STAMP(1);
@@ -2700,13 +2715,30 @@ __device__ __forceinline__ void divgs_t_body(const A& d, int j, const unsigned b
   const int nds = nd < MM ? nd : 0;
   const long long q = es * MM + nds;
   // ---- first trip: everything addressable from the thread index
-  const int4 tab = d.gs_tab[l];
+  // (IF: first what the staging in front of the first barrier needs, then the gathers, then the rest; the asm statements keep
+  //  the compiler from moving a load from one group into another -- they wait for nothing)
+  int4 tab;
+  if constexpr (IF) tab = tabf; else tab = d.gs_tab[l];
   const double bi = d.binv[l];
   double bi1 = 0;
   if constexpr (CM) bi1 = d.binv[d.nloc + l];
-  const int ecs = d.ecslot[es * 4 + (nd & 3)];
+  int ecs = 0;
+  if constexpr (!IF) ecs = d.ecslot[es * 4 + (nd & 3)];
   const int iv = d.evl[es * NVL + (nd < NVL ? nd : 0)];
   const int4 ev = reinterpret_cast<const int4*>(d.evert)[es];
+  double j12a = 0, d12a = 0;
+  double hatv[(4 * MM + 255) / 256];
+  GsVals g0, g1;
+  if constexpr (IF) {
+    if (tid < NM) { j12a = d.J12[tid]; d12a = d.D12[tid]; }
+#pragma unroll
+    for (int r = 0; r < (4 * MM + 255) / 256; ++r) hatv[r] = d.hat[(tid + r * 256 < 4 * MM) ? tid + r * 256 : 0];
+    asm volatile("" ::: "memory");
+    g0 = gs_load(d.yl, tab, l);
+    g1 = gs_load(d.yl + d.cs, tab, l);
+    asm volatile("" ::: "memory");
+    ecs = d.ecslot[es * 4 + (nd & 3)];
+  }
   const double mw0 = d.w2rx[q], mw1 = d.w2sx[q], mw2 = d.w2ry[q], mw3 = d.w2sy[q];
   const double zq = d.Z[(size_t)j * d.npr + q];
   float ttf[T32 ? NVL : 1];
@@ -2735,23 +2767,31 @@ __device__ __forceinline__ void divgs_t_body(const A& d, int j, const unsigned b
       for (int k = 4; k < 8; ++k) vk[k] = d.V[(size_t)(k <= j ? k : j) * d.ps + q];
     }
   }
-  double j12a = 0, d12a = 0;
-  if (tid < NM) { j12a = d.J12[tid]; d12a = d.D12[tid]; }
-  double hatv[(4 * MM + 255) / 256];
+  if constexpr (!IF) {
+    if (tid < NM) { j12a = d.J12[tid]; d12a = d.D12[tid]; }
 #pragma unroll
-  for (int r = 0; r < (4 * MM + 255) / 256; ++r) hatv[r] = d.hat[(tid + r * 256 < 4 * MM) ? tid + r * 256 : 0];
+    for (int r = 0; r < (4 * MM + 255) / 256; ++r) hatv[r] = d.hat[(tid + r * 256 < 4 * MM) ? tid + r * 256 : 0];
+  }
   NSK_STAMP(2);
   // ---- second trip: the neighbours' values of yl, the coarse solution at this element's vertices
-  const GsVals g0 = gs_load(d.yl, tab, l), g1 = gs_load(d.yl + d.cs, tab, l);
-  const double xcv = d.xc[iv];
-  const double x0 = d.xc[ev.x], x1 = d.xc[ev.y], x2 = d.xc[ev.z], x3 = d.xc[ev.w];
+  double xcv = 0, x0 = 0, x1 = 0, x2 = 0, x3 = 0;
+  if constexpr (!IF) {
+    g0 = gs_load(d.yl, tab, l); g1 = gs_load(d.yl + d.cs, tab, l);
+    xcv = d.xc[iv];
+    x0 = d.xc[ev.x]; x1 = d.xc[ev.y]; x2 = d.xc[ev.z]; x3 = d.xc[ev.w];
+  }
   if (tid < NM) { sJ12[tid] = j12a; sD12[tid] = d12a; }
 #pragma unroll
   for (int r = 0; r < (4 * MM + 255) / 256; ++r) if (tid + r * 256 < 4 * MM) shat[tid + r * 256] = hatv[r];
   if (act) {
     su[(0 * EPB + el) * NN + nd] = bi * gs_sum(g0, d.yl, d, tab, l);
     su[(1 * EPB + el) * NN + nd] = (CM ? bi1 : bi) * gs_sum(g1, d.yl + d.cs, d, tab, l);
-    if (nd < NVL) sxc[el * NVL + nd] = xcv;
+    if constexpr (!IF) { if (nd < NVL) sxc[el * NVL + nd] = xcv; }
+  }
+  if constexpr (IF) {                          // (the indices came back with the wait above: the coarse values go out behind it)
+    asm volatile("" ::: "memory");
+    xcv = d.xc[iv];
+    x0 = d.xc[ev.x]; x1 = d.xc[ev.y]; x2 = d.xc[ev.z]; x3 = d.xc[ev.w];
   }
   NSK_STAMP(3);
   lds_barrier();
@@ -2773,6 +2813,7 @@ __device__ __forceinline__ void divgs_t_body(const A& d, int j, const unsigned b
     sA[(2 * EPB + el) * NM + nd] = a1v;
     sA[(3 * EPB + el) * NM + nd] = a2v;
   }
+  if constexpr (IF) { if (act && nd < NVL) sxc[el * NVL + nd] = xcv; }        // (read below by this element's lanes nd < MM)
   tile_barrier<N * N>();
   double w = 0.0;
   if (pact) {
@@ -2849,12 +2890,12 @@ template <int N, bool T32, bool CM = false>
 __global__ __launch_bounds__(256, 2) void k_divgs_t(Dev d, int j) {
   divgs_t_body<N, T32, false, CM>(d, j, blockIdx.x, gridDim.x);
 }
-template <int N, bool T32, bool CM = false>
+template <int N, bool T32, bool CM = false, bool IF = false>
 __global__ __launch_bounds__(256, 2) void k_divgs_t_l(GmresScal* gsc, const int4* gs_tab, int nel, int boff, unsigned grid, int j, DivgsRest r) {
   DivgsArgs d;
   static_cast<DivgsHead&>(d) = DivgsHead{gsc, gs_tab, nel, boff};
   static_cast<DivgsRest&>(d) = r;
-  divgs_t_body<N, T32, false, CM>(d, j, blockIdx.x, grid);
+  divgs_t_body<N, T32, false, CM, IF>(d, j, blockIdx.x, grid);
 }
 
 // after GMRES: dp = h2 * sum_i y_i Z_i (+ projected part) ; p = p* + dp ; yl = D^T dp
