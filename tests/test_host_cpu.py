@@ -111,6 +111,9 @@ def test_two_rank_gloo_host_transport_and_timing(tmp_path):
         "t = torch.tensor([0.05 * (r + 1)], dtype=torch.float64); dist.all_reduce(t, op=dist.ReduceOp.MAX)\n"
         "units = torch.tensor([10.0]); dist.all_reduce(units)\n"
         "assert abs(t.item() - 0.1) < 1e-12 and units.item() == 20.0\n"
+        # (leave together, as test_local_setup_exchange_over_gloo does: a rank that exits with the group still open closes its
+        #  sockets under the other rank's gloo threads, which then abort that process -- SIGABRT on rank 1, now and then)
+        "dist.barrier(); dist.destroy_process_group()\n"
         "print('ok', r)\n" % ROOT)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                           "--master-addr", "127.0.0.1", "--master-port", "29611", str(script)],
