@@ -186,9 +186,8 @@ struct nsk_ctx {
   int nscal = 0;                        // scalar fields theta(:, 1..ldimt) carried behind the pressure (option "nscal")
   double dt = 0, re = 0, endtime = 0;
   int nsteps = 0;
-  int max_helm = 60, max_pres = 40, min_pres = 0, pres_cap = 0, layers = 1;
-  int cur_helm[NCLS] = {}, cur_pres[NCLS] = {};       // adaptive launch budgets per BDF order
-  int bh_helm[NCLS][8] = {}, bh_pres[NCLS][8] = {}, bh_n = 0;                         // iteration maxima of the last maps (budgets_update)
+  int pres_cap = 0, layers = 1;
+  LaunchBudgets lb;                     // the solvers' caps, the adaptive launch budgets per step class and per time step, their record (nsk_budgets_host.hpp)
   int use_graph = 1;
   int gmres_cycle = MAXMR;              // pressure GMRES restarts after this many iterations (option "gmres_cycle": tests use short cycles)
   int mfma_convect = 1;                 // hexahedra, lx1 = 8 and 10: convection kernel with the contractions on the fp64 matrix cores (nsk3_mfma.hpp: k_convect_mfma8, k_convect_mfma<10>, and the full equations' k_convect_mfma_nl<10>)
@@ -196,7 +195,6 @@ struct nsk_ctx {
   unsigned* sync = nullptr;             // grid-barrier counters of the persistent kernels
   int in_test = 0;
   int helm_guess = 1;
-  int budget_freeze = 0;
   int helm_fdm = -1;                    // hexahedra: element-block fast-diagonalisation preconditioner of the velocity solves (NSK_HELM_FDM=1 builds it; measured slower than Jacobi-CG, off)
   int eapply_pipe = 4;                  // hexahedra, the Schwarz + D^T kernel: 0 = one workgroup per element, 1 = resident workgroups with the next element's loads in flight (k_schwarz_p), 2 = one wavefront per element (k_schwarz_w), 3 = 2 + k_divgs_w, 4 = the default form: one wavefront per element, sixteen per CU (k_schwarz_w16) at lx1 <= 8, four wavefronts per element (k_schwarz_q, = 5) at lx1 = 10
   int zero_metrics = 1;                 // hexahedra: arrays of the mapping / base-flow constants that are zero on every node are cleaned at set-up and not loaded by the kernels (Dev::zmask, Dev::bfmask); NSK_ZERO_METRICS=0: set-up as rounds 1-4 (rounding noise kept); option zero_metrics = 0: cleaned arrays, every one loaded
@@ -228,16 +226,8 @@ struct nsk_ctx {
   // per-step record of the last SBW maps (Dev::step_iters) the budget of step s follows the largest count seen at steps
   // s-2..s+2 in those maps + head-room: measured on 56 maps of config 2 (scripts/step_iters_dump.py, profiles/r05_step_budgets.txt)
   // 14.4 + 9.9 launches per step instead of 20.5 + 13.7, no overflow.  One captured graph per (step class, budget pair), kept
-  // in `gcache` (a few dozen pairs occur); a map that overflows is redone with the class budgets.
-  static constexpr int SBW = 8, SBN = 2;
+  // in `gcache` (a few dozen pairs occur); a map that overflows is redone with the class budgets.  (LaunchBudgets::update_steps)
   int step_budgets = 1;
-  struct StepBudgets {                   // one history per kind of map (0 direct, 1 adjoint): their solves differ
-    std::vector<int> hist_h[SBW], hist_p[SBW];
-    int n = 0;                           // maps in the history (ring slot = n % SBW)
-    std::vector<int> bh, bp;             // budgets of the next map of this kind (empty: class budgets)
-  } sb[2];
-  int last_map_kind = 0;
-  bool sb_force_class = false;           // the redo of an overflowed map runs on the (doubled) class budgets
   // ---- persistent tails (nsk_persist.hpp: k_helm_tail, k_pres_tail; option "tail").  Behind the launches of a solve ONE persistent
   // launch runs whatever iterations are left, to the solver's caps: no budget can overflow, no map is redone.
   //   0: never.   1: HEADS = the median count of the step over the last maps, the tail does the rest (0.25 + 0.52 tail iterations per
@@ -263,7 +253,6 @@ struct nsk_ctx {
   int helm_pack = -1;                   // 16-byte accesses in the quadrilateral velocity solve (k_helm<N, true>, k_helm_tail<N, true>, k_pres_rhs<N, .., true>): -1 = where allowed and where it pays (StepForm::helmpack: lx1 <= 10), 0 = never, 1 = wherever allowed; option "helm_pack"
   long long convfuse_steps = 0;          // time steps run with convection and the velocity right-hand side in one launch (option "conv_fuse")
   long long sb_maps = 0, sb_steps = 0, sb_launch_h = 0, sb_launch_p = 0;     // maps / time steps run on per-step budgets and their budgeted launches (diagnostics)
-  bool last_map_per_step = false;        // the map just run took the per-step budgets
   std::map<std::array<int, 4>, hipGraphExec_t> gcache;         // (adjoint, class, nh, np) -> captured step
   std::vector<nsk_ctx*> graph_members;  // sharded step graphs (held by the first rank of a process): the ranks they were captured for
   int merged_iters = 24;                // ... for the first merged_iters iterations of a solve (see pres_solve_launch; 12 until round 4: 24 covers the tightened solves of time steps 1-3 too, +2 % on config 2 at identical iteration counts)
@@ -318,8 +307,8 @@ struct nsk_ctx {
   // (first call; freed with the context).  `sfd` is set while such a map runs (eager steps only), else off.
   double *sfd_state = nullptr, *sfd_part = nullptr, *sfd_hist = nullptr;
   int sfd_hist_cap = 0;
-  int sfd_helm[NCLS] = {}, sfd_pres[NCLS] = {};     // class launch budgets the SFD maps of this context grew to (0: none yet): kept
-                                                    // apart from cur_helm / cur_pres, which belong to the unforced maps
+  ClassBudgets sfd_budgets;             // class launch budgets the SFD maps of this context grew to (0: none yet): kept apart from
+                                        // lb's, which belong to the unforced maps
   struct SfdRun {
     bool on = false;
     const double* q0 = nullptr;         // the caller's qbar: the filter state the map starts from (read by call 0 of every attempt)
@@ -335,7 +324,7 @@ struct nsk_ctx {
   double *bcv_X = nullptr, *bcv_Y = nullptr, *bcv_small = nullptr, *bcv_tot = nullptr, *bcv_part = nullptr, *bcv_hist = nullptr, *bcv_save = nullptr;
   int bcv_snp = 0, bcv_rot = 0, bcv_hist_cap = 0;
   long long bcv_count = 0;
-  int bcv_helm[NCLS] = {}, bcv_pres[NCLS] = {};     // class launch budgets the BoostConv maps of this context grew to (as sfd_helm)
+  ClassBudgets bcv_budgets;             // class launch budgets the BoostConv maps of this context grew to (as sfd_budgets)
   struct BcvRun {
     bool on = false;
     int skip = 1, ncall = 0, attempt = 0;             // ncall: calls of this attempt
@@ -420,7 +409,7 @@ static void invalidate_graphs(nsk_ctx* c) {
   for (auto& a : c->graphs) for (auto& g : a) g.nh = -1;
   for (auto& kv : c->gcache) if (kv.second) (void)hipGraphExecDestroy(kv.second);
   c->gcache.clear();
-  for (auto& b : c->sb) { b.n = 0; b.bh.clear(); b.bp.clear(); }
+  c->lb.forget_steps();
 }
 
 static int dalloc_bytes(nsk_ctx* c, void** p, size_t bytes) {
@@ -511,15 +500,14 @@ struct DevTmp {
 // graphs and the budgets belong to the unforced maps.  Saved here, put back by restore() or at the end of the scope (a map that
 // outgrew its budgets doubled them for its redo).
 struct EagerRun {
-  struct Saved { int use_graph, freeze, helm[NCLS], pres[NCLS]; };
+  struct Saved { int use_graph, freeze; ClassBudgets budgets; };
   std::vector<nsk_ctx*>& G; std::vector<Saved> keep; bool done = false;
   explicit EagerRun(std::vector<nsk_ctx*>& G_) : G(G_), keep(G_.size()) {
     for (size_t r = 0; r < G.size(); ++r) {
       nsk_ctx* c = G[r];
-      keep[r].use_graph = c->use_graph; keep[r].freeze = c->budget_freeze;
-      for (int k = 0; k < NCLS; ++k) { keep[r].helm[k] = c->cur_helm[k]; keep[r].pres[k] = c->cur_pres[k]; }
+      keep[r] = {c->use_graph, c->lb.freeze, c->lb.save()};
       c->use_graph = 0;                                          // group_graph_ok: eager
-      c->budget_freeze = 1;
+      c->lb.freeze = 1;
     }
   }
   void restore() {
@@ -527,8 +515,8 @@ struct EagerRun {
     done = true;
     for (size_t r = 0; r < G.size(); ++r) {
       nsk_ctx* c = G[r];
-      c->use_graph = keep[r].use_graph; c->budget_freeze = keep[r].freeze;
-      for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = keep[r].helm[k]; c->cur_pres[k] = keep[r].pres[k]; }
+      c->use_graph = keep[r].use_graph; c->lb.freeze = keep[r].freeze;
+      c->lb.restore(keep[r].budgets);
     }
   }
   ~EagerRun() { restore(); }
@@ -681,8 +669,8 @@ static int build_open(nsk_ctx* c, const nsk_case& cs, int ndim, int EPB) {
   c->EPB = EPB; c->nel = cs.nel; c->nblk = (cs.nel + EPB - 1) / EPB;
   c->nloc = (long long)cs.nel * c->NN; c->npr = (long long)cs.nel * c->MM; c->nstate = ndim * c->nloc + c->npr;
   c->re = cs.re; c->endtime = cs.endtime;
-  if (cs.max_helm_iter > 0) c->max_helm = cs.max_helm_iter;
-  if (cs.max_pres_iter > 0) c->max_pres = std::min(cs.max_pres_iter, 4 * MAXMR);     // beyond MAXMR: restarted GMRES cycles
+  if (cs.max_helm_iter > 0) c->lb.max_helm = cs.max_helm_iter;
+  if (cs.max_pres_iter > 0) c->lb.max_pres = std::min(cs.max_pres_iter, 4 * MAXMR);     // beyond MAXMR: restarted GMRES cycles
   HIPCHK(hipStreamCreate(&c->stream));
   Dev& d = c->d;
   d.ndim = ndim; d.nel = cs.nel; d.nblk = c->nblk; d.nloc = c->nloc; d.npr = c->npr; d.nu = 1.0 / cs.re;
@@ -691,7 +679,7 @@ static int build_open(nsk_ctx* c, const nsk_case& cs, int ndim, int EPB) {
   c->h_gid.assign(cs.gid, cs.gid + c->nloc);
   d.tol_helm = cs.tol_helm > 0 ? cs.tol_helm : 1e-9;
   d.tol_pres = cs.tol_pres > 0 ? cs.tol_pres : 1e-7;
-  d.tol_relative = cs.tol_relative; d.max_mr = std::min(c->max_pres, MAXMR); d.has_outflow = cs.has_outflow;
+  d.tol_relative = cs.tol_relative; d.max_mr = std::min(c->lb.max_pres, MAXMR); d.has_outflow = cs.has_outflow;
   // projection space also with the pressure null space (adjoint runs, closed domains): with the restart policy of k_proj_update it
   // cuts config 4's pressure iterations from 26 to 15 per step (rounds 1-2 switched it off there: their merge policy made such solves slower)
   d.nproj_max = (cs.has_outflow || !std::getenv("NSK_NO_PROJ_SINGULAR")) ? std::min(cs.nproj, MAXPROJ) : 0;
@@ -1210,8 +1198,7 @@ static int build(nsk_ctx* c, const nsk_case& cs) {
     d.use_tot = 1;
     if ((rc = alloc_totals(c))) return rc;
   }
-  for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
-  c->bh_n = 0;
+  c->lb.reset_to_caps(true);
   if ((rc = dalloc_mut(c, &c->sync, 2 * SYNC_WORDS))) return rc;      // two sets: the tails alternate (nsk_persist.hpp)
   // persistent velocity solve: available where the grid is resident, OFF by default -- measured on config 2 it is not faster
   // than the launch-per-iteration form (13.6 vs 13.5 us per CG iteration: DESIGN.md section 5); option "fused" / NSK_FUSED=1
@@ -1336,7 +1323,7 @@ static StepForm step_form(nsk_ctx* c) {
   F.fuse2 = c->fuse2 && d.Tc && d.Wr && d.ecv && d.rch && c->ndim == 2 && d.nvl == nsk::k2::UC_NVL && d.coarse_lda % 768 == 0 && d.coarse_lda <= 3072 &&
             d.p_stride == (((M + 4) * (M + 4) + 3) / 4) * 4;
   F.f2start = F.merged && F.fuse2 && c->fuse2_start && d.nproj_max > 0 && d.nproj_max <= MAXPROJ && std::min(c->merged_iters, c->gmres_cycle) > 0;
-  F.absorb = c->proj_absorb != 0 && !c->fused && !c->in_test && !c->parent && !F.hostcheck && F.f2start && c->max_pres > 0;
+  F.absorb = c->proj_absorb != 0 && !c->fused && !c->in_test && !c->parent && !F.hostcheck && F.f2start && c->lb.max_pres > 0;
   F.convfuse = c->conv_fuse != 0 && quad1 && !c->force && !c->sfd.on && !c->in_test;
   F.helmpack = c->helm_pack != 0 && quad1 && !(c->helm_pack < 0 && c->N > 10);
   F.leanargs = c->lean_args != 0 && quad1;
@@ -1554,7 +1541,7 @@ static void launch_gs_lag3(nsk_ctx* c, const Dev& d, int j, double scale, int or
   if constexpr (N <= 10) {
     launch_gs_lag_pass3<N>(c, d, j);
     tot_rows(c, d.gpart2, j + 2, d.gtot2, &d.gsc->done);
-    hipLaunchKernelGGL(nsk::k3::k_gmres_col, dim3(1), dim3(64), 0, c->stream, d, j, scale, c->min_pres, ord);
+    hipLaunchKernelGGL(nsk::k3::k_gmres_col, dim3(1), dim3(64), 0, c->stream, d, j, scale, c->lb.min_pres, ord);
   }
 }
 
@@ -1629,7 +1616,7 @@ static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, 
   d.tol_pres = early_tol(d, tol_mul);
   // time steps >= 4: optionally a bounded solve (min_pres_iter .. pres_cap iterations): nothing is launched beyond the cap
   if (c->pres_cap > 0 && ord >= 3 && allow_cap && c->ndim == 2) {   // validated on quadrilateral linearised maps only
-    d.pres_cap = std::max(c->pres_cap, c->min_pres); np = std::min(np, d.pres_cap);
+    d.pres_cap = std::max(c->pres_cap, c->lb.min_pres); np = std::min(np, d.pres_cap);
   }
   const double scale = 1.0 / (h2 * std::sqrt(d.vol));
   const bool lag = F.gs_lag;
@@ -1647,7 +1634,7 @@ static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, 
     if (absorb && !f2start) return fail(NSK_EINVAL, "internal: deferred projection update in a step whose pressure solve does not start inside A_0");
     if (f2start) launch_proj_apply_e<N>(c, d);
     else if (d.nproj_max > 0 && !c->in_test) { hipLaunchKernelGGL(k_proj_apply, dim3(c->nblk), dim3(256), 0, c->stream, d); tot_rows(c, d.gpart, 1, d.gtot); }
-    if (!f2start) hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, -1, scale, c->min_pres, ord);
+    if (!f2start) hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, -1, scale, c->lb.min_pres, ord);
     // merged bookkeeping (k_update_coarse): quadrilateral single-rank contexts with the dense in-LDS coarse solve.
     // Only the first `merged_iters` (24) iterations of a solve: x_c(v_j) by linearity is a recurrence, its rounding error grows by
     // ~|h_jj / h_{j+1,j}| per iteration (harmless in a preconditioner for a dozen iterations, a stalled solve after forty:
@@ -1657,7 +1644,7 @@ static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, 
     // range in one launch, and iterations beyond it (classic form) keep the class budget
     const bool tl = tail && merged && d.pres_cap == 0;
     const int nhead = tl ? std::max(0, std::min(np, std::min(c->merged_iters, c->gmres_cycle) - 1)) : 0;
-    if (tl) np = std::max(c->cur_pres[ord], std::min(c->max_pres, std::min(c->merged_iters, c->gmres_cycle)));
+    if (tl) np = std::max(c->lb.cur_pres[ord], std::min(c->lb.max_pres, std::min(c->merged_iters, c->gmres_cycle)));
     const int nm = merged ? std::min(np, std::min(c->merged_iters, c->gmres_cycle)) : 0;
     if (hc && c->hc_pres[ord] <= 1) {                     // the projection space may have solved this right-hand side alone
       bool done = false;
@@ -1671,16 +1658,16 @@ static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, 
     for (int j = 0; j < (tl ? nhead : nm); ++j) {
       if (f2) {                                            // two launches per iteration (round 6)
         Dev d0 = d; d0.uc_start = (f2start && j == 0) ? 1 : 0;
-        launch_schwarz_uc<N>(c, F, d0, j, scale, c->min_pres, ord);
+        launch_schwarz_uc<N>(c, F, d0, j, scale, c->lb.min_pres, ord);
         launch_divgs_t<N>(c, F, d, j);
         continue;
       }
-      launch_update_coarse(c, d, j, scale, c->min_pres, ord);
+      launch_update_coarse(c, d, j, scale, c->lb.min_pres, ord);
       hipLaunchKernelGGL(k_schwarz<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)(d.V + (size_t)j * d.ps), d.Z + (size_t)j * d.npr, 1, 1);
       if (c->ndim == 2) launch_divgs2<N>(c, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2);
       else hipLaunchKernelGGL(k_divgs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, (const double*)d.yl, d.V + (size_t)(j + 1) * d.ps, j, 2);
     }
-    if (tl && nhead < nm) launch_pres_tail<N>(c, F, d, nhead, nm, scale, c->min_pres, ord, f2start && nhead == 0);
+    if (tl && nhead < nm) launch_pres_tail<N>(c, F, d, nhead, nm, scale, c->lb.min_pres, ord, f2start && nhead == 0);
     // a velocity tail ran in this step but no pressure tail will: the velocity tail's barrier words (set 0) are re-zeroed by
     // the pressure tail only, so zero them here (a dirty set lets the next velocity tail's first barriers fall through)
     if (tail && !(tl && nhead < nm) && c->sync) (void)hipMemsetAsync(c->sync, 0, SYNC_WORDS * sizeof(unsigned), c->stream);
@@ -1692,11 +1679,11 @@ static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, 
         // two-launch form, budget below the merged range: the last column is closed by A_nm -- the SAME code (uc_rotate) that closes
         // every other column and that the persistent tail runs, so that a solve of exactly nm iterations ends with the same bits
         // whatever budget or tail mode ended it (k_gmres_update's own copy of the rotation differs from it by rounding)
-        launch_schwarz_uc<N>(c, F, d, nm, scale, c->min_pres, ord);
+        launch_schwarz_uc<N>(c, F, d, nm, scale, c->lb.min_pres, ord);
       } else {
         Dev dcl = d;
         if (f2) dcl.wraw = d.Wr;                           // the raw w of B_{nm-1}; classic iterations follow: they need v_nm normalised and its corner restrictions
-        hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, dcl, nm - 1, scale, c->min_pres, ord);
+        hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, dcl, nm - 1, scale, c->lb.min_pres, ord);
       }
     }
     for (int jt = nm; jt < np; ++jt) {
@@ -1704,7 +1691,7 @@ static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, 
       if (jt > 0 && j == 0) {                            // cycle full and not converged: restart on the residual
         hipLaunchKernelGGL(k_gmres_restart, dim3(c->nblk), dim3(256), 0, c->stream, d, c->gmres_cycle);
         tot_rows(c, d.gpart, 1, d.gtot, &d.gsc->done);
-        hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, -2, scale, c->min_pres, ord);
+        hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, -2, scale, c->lb.min_pres, ord);
       }
       if (c->ndim == 3) {
         hipLaunchKernelGGL(k_coarse_restrict_csr, dim3(d.coarse_lda / 256), dim3(256), 0, c->stream, d, c->rc_big);
@@ -1736,7 +1723,7 @@ static int pres_solve_launch(nsk_ctx* c, const StepForm& F, double h2, int ord, 
           tot_rows(c, d.gpart2, j + 2, d.gtot2, &d.gsc->done);
         }
         Dev d2 = d; d2.gs2 = two ? 1 : 0;
-        hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d2, j, scale, c->min_pres, ord);
+        hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d2, j, scale, c->lb.min_pres, ord);
       }
       // large meshes: an iteration takes milliseconds, a flag read microseconds -> after every iteration; otherwise from three
       // iterations before the previous solve's count on
@@ -1756,7 +1743,7 @@ template <int N>
 static void launch_fused(nsk_ctx* c, const StepCoef& sc, int max_it = -1, const Dev* dd = nullptr) {
   if (c->ndim != 2) return;
   hipLaunchKernelGGL(nsk::k2::k_helm_fused<N>, dim3(c->nblk), dim3(nsk::k2::Cfg<N>::NT), 0, c->stream, dd ? *dd : c->d, sc,
-                     max_it < 0 ? c->max_helm : max_it, c->sync);
+                     max_it < 0 ? c->lb.max_helm : max_it, c->sync);
 }
 // Can every workgroup of the grid be resident at once?  (grid barrier => all or nothing.)  The occupancy query can be
 // one block per CU high at 81..112 SGPRs (MI355X_MICROARCH.md, residency), so one block per CU of margin is kept.
@@ -1906,7 +1893,7 @@ static int step(nsk_ctx* c, const StepForm& F, int istep, int adjoint, int nh_ov
   if (F.idxfirst && !in_map) c->idxfirst_steps++;
   if (cfuse) da.bstep_late = ((d.bf_stride || d.forb) && adjoint != 2) ? 1 : 0;
   if (cfuse && !in_map) c->convfuse_steps++;            // (the steps of a map are counted by run_map: a captured step is replayed)
-  int nh = hc ? c->max_helm : (nh_over > 0 ? nh_over : c->cur_helm[sc.cls]);
+  int nh = hc ? c->lb.max_helm : (nh_over > 0 ? nh_over : c->lb.cur_helm[sc.cls]);
   DISPATCH_N(c->key, {
     constexpr int NT = Cfg<N>::NT;
     if (d.forb && adjoint != 2)       // Fourier orbit: the base flow of this step into the steady slot (hexahedra: cUr is the 12-constant array)
@@ -1924,7 +1911,7 @@ static int step(nsk_ctx* c, const StepForm& F, int istep, int adjoint, int nh_ov
       if (cfuse) launch_convect_rhs<N>(c, da, sc, absorb);
       else if (c->ndim == 2) launch_rhs<N>(c, da, sc, absorb);
       else hipLaunchKernelGGL(k_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc);
-      if (tail) nh = std::max(1, std::min(nh, c->max_helm - 1));      // HEAD launches; the persistent tail runs launches nh .. max_helm-1
+      if (tail) nh = std::max(1, std::min(nh, c->lb.max_helm - 1));      // HEAD launches; the persistent tail runs launches nh .. max_helm-1
       for (int it = 0; it < nh; ++it) {
         launch_helm_iter<N>(c, F, d, sc, it, (const double*)d.rloc);
         tot_rows(c, d.hpart + (size_t)(it & 1) * c->hrows * c->nblk, c->hrows, d.htot + (it & 1) * c->hstride);
@@ -1935,7 +1922,7 @@ static int step(nsk_ctx* c, const StepForm& F, int istep, int adjoint, int nh_ov
           if (done) { c->hc_helm[sc.cls] = std::max(1, it - 1); nh = it + 1; break; }
         }
       }
-      if (tail) { launch_helm_tail<N>(c, F, d, sc, nh, c->max_helm); nh = c->max_helm; }
+      if (tail) { launch_helm_tail<N>(c, F, d, sc, nh, c->lb.max_helm); nh = c->lb.max_helm; }
       // (quadrilaterals: `da` is `d` with this step's absorb and bstep_late, the two k_pres_rhs reads besides helm_pk)
       if (c->ndim == 2) launch_pres_rhs<N>(c, da, sc, absorb, (nh - 1) & 1, nh - 1);
       else hipLaunchKernelGGL(k_pres_rhs<N>, dim3(c->nblk), dim3(NT), 0, c->stream, d, sc, (nh - 1) & 1, nh - 1);
@@ -1943,7 +1930,7 @@ static int step(nsk_ctx* c, const StepForm& F, int istep, int adjoint, int nh_ov
   });
   // The first steps of a map project out whatever divergence the input vector has (a noise seed is far from
   // solenoidal): an error there survives to the end of the map, so those solves are converged further.
-  int rc = pres_solve_launch(c, F, sc.h2, sc.cls, hc ? c->max_pres : (np_over > 0 ? np_over : c->cur_pres[sc.cls]), istep <= 3 ? c->early_pres_mul : 1.0, adjoint != 2, hc, tail, absorb);
+  int rc = pres_solve_launch(c, F, sc.h2, sc.cls, hc ? c->lb.max_pres : (np_over > 0 ? np_over : c->lb.cur_pres[sc.cls]), istep <= 3 ? c->early_pres_mul : 1.0, adjoint != 2, hc, tail, absorb);
   if (rc) return rc;
   const bool flat = F.flat_proj;
   Dev df = da; df.flat_proj = flat ? 1 : 0;
@@ -1968,45 +1955,38 @@ static int step(nsk_ctx* c, const StepForm& F, int istep, int adjoint, int nh_ov
   return 0;
 }
 
-static const int CLS_ISTEP[NCLS] = {1, 2, 3, 4, 7, 17};    // first step of every class
-
-static int ensure_graph(nsk_ctx* c, const StepForm& F, int cls, int adjoint) {
-  nsk_ctx::StepGraph& g = c->graphs[adjoint][cls];
-  if (g.exec && g.nh == c->cur_helm[cls] && g.np == c->cur_pres[cls]) return 0;
+// Capture what `body` queues on the context's stream into an executable graph: *out (an older graph there is destroyed first) is
+// the new one, or null on failure.  The captured hipGraph_t is destroyed on every path; the time spent is booked as a re-capture.
+// `what` completes the message of a capture that could not be ended.
+template <class Body>
+static int capture_exec(nsk_ctx* c, Body&& body, hipGraphExec_t* out, const char* what) {
   const auto t_cap0 = std::chrono::steady_clock::now();
-  if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+  if (*out) { (void)hipGraphExecDestroy(*out); *out = nullptr; }
   hipGraph_t graph = nullptr;
   HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = step(c, F, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
+  int rc = body();
   hipError_t e = hipStreamEndCapture(c->stream, &graph);
+  if (!rc && e != hipSuccess) rc = fail(NSK_EHIP, std::string("hipStreamEndCapture") + what + ": " + hipGetErrorString(e));
+  if (!rc && (e = hipGraphInstantiate(out, graph, nullptr, nullptr, 0)) != hipSuccess) rc = fail(NSK_EHIP, std::string("hipGraphInstantiate") + what + ": " + hipGetErrorString(e));
+  if (graph) (void)hipGraphDestroy(graph);
   if (rc) return rc;
-  if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  HIPCHK(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
   c->recaptures++;
-  HIPCHK(hipGraphDestroy(graph));
-  g.nh = c->cur_helm[cls]; g.np = c->cur_pres[cls];
   c->recapture_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_cap0).count();
   return 0;
 }
 
-static int ensure_graph_multi(nsk_ctx* c, const StepForm& F, int adjoint) {
-  nsk_ctx::StepGraph& g = c->graphs[adjoint][NCLS];
-  const int cls = NCLS - 1;
-  if (g.exec && g.nh == c->cur_helm[cls] && g.np == c->cur_pres[cls]) return 0;
-  const auto t_cap0 = std::chrono::steady_clock::now();
-  if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-  hipGraph_t graph = nullptr;
-  HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = 0;
-  for (int r = 0; r < c->graph_steps && !rc; ++r) rc = step(c, F, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
-  hipError_t e = hipStreamEndCapture(c->stream, &graph);
+// the captured step of class `cls` on the class budgets: slot `cls`; slot NCLS (cls = NCLS - 1): `graph_steps` steps in one graph
+static int ensure_graph(nsk_ctx* c, const StepForm& F, int slot, int adjoint) {
+  nsk_ctx::StepGraph& g = c->graphs[adjoint][slot];
+  const int cls = std::min(slot, NCLS - 1), reps = slot == NCLS ? c->graph_steps : 1;
+  if (g.exec && g.nh == c->lb.cur_helm[cls] && g.np == c->lb.cur_pres[cls]) return 0;
+  int rc = capture_exec(c, [&] {
+    int r = 0;
+    for (int i = 0; i < reps && !r; ++i) r = step(c, F, CLS_ISTEP[cls], adjoint, -1, -1, false, true);
+    return r;
+  }, &g.exec, "");
   if (rc) return rc;
-  if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  HIPCHK(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-  c->recaptures++;
-  HIPCHK(hipGraphDestroy(graph));
-  g.nh = c->cur_helm[cls]; g.np = c->cur_pres[cls];
-  c->recapture_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_cap0).count();
+  g.nh = c->lb.cur_helm[cls]; g.np = c->lb.cur_pres[cls];
   return 0;
 }
 
@@ -2017,26 +1997,15 @@ static int graph_for(nsk_ctx* c, const StepForm& F, int adjoint, int cls, int nh
   auto it = c->gcache.find(key);
   if (it != c->gcache.end()) { *out = it->second; return 0; }
   // (the cache is bounded by run_map, BEFORE it builds a plan: evicting here would leave handles of the plan under construction dangling)
-  const auto t_cap0 = std::chrono::steady_clock::now();
-  hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = step(c, F, CLS_ISTEP[cls], adjoint, nh, np, tail, true);
-  hipError_t e = hipStreamEndCapture(c->stream, &graph);
-  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-  if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-  HIPCHK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-  HIPCHK(hipGraphDestroy(graph));
-  c->recaptures++;
-  c->recapture_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_cap0).count();
+  int rc = capture_exec(c, [&] { return step(c, F, CLS_ISTEP[cls], adjoint, nh, np, tail, true); }, &exec, "");
+  if (rc) return rc;
   c->gcache[key] = exec;
   *out = exec;
   return 0;
 }
 static bool step_budgets_ready(const nsk_ctx* c, int kind) {
-  if (kind < 0 || kind > 1) return false;
-  const nsk_ctx::StepBudgets& b = c->sb[kind];
-  return c->step_budgets && !c->sb_force_class && !c->fused && !c->budget_freeze && c->d.step_iters && (int)b.bh.size() == c->nsteps && (int)b.bp.size() == c->nsteps;
+  return c->step_budgets && c->d.step_iters && c->lb.steps_ready(kind, c->nsteps, c->fused != 0);
 }
 
 // Fourier orbit: row i of the table holds cos / sin (2 pi frac(k s_i)), k = 1..M, s_i = phase + i dt / T -- the base flow of
@@ -2072,6 +2041,25 @@ static int forb_trig_ensure(nsk_ctx* c, bool* rebuilt = nullptr) {
   return 0;
 }
 
+// The preamble of a map attempt, for single-rank contexts and for every rank of a sharded map: the device counters zeroed, the
+// input vector in the stepper's fields, the step counter of a time-periodic base flow (stored orbit / row of the trig table) at 0.
+static int map_begin(nsk_ctx* c, const double* q, int adjoint) {
+  Dev& d = c->d;
+  HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
+  { int rc = state_load(c, q); if (rc) return rc; }
+  if (d.bf_stride || d.forb) {
+    if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
+    HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
+  }
+  return 0;
+}
+// BoostConv map: every rank opens an attempt; the reference's call at istep = 0 (lag = 0) opens a run
+static int bcv_open(std::vector<nsk_ctx*>& G) {
+  if (!G[0]->bcv.on) return 0;
+  for (nsk_ctx* c : G) { int rc = bcv_begin_attempt(c); if (rc) return rc; }
+  return G[0]->bcv.step0 == 0 ? bcv_call(G, nullptr, false) : 0;
+}
+
 static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   Dev& d = c->d;
   if (d.forb && adjoint != 2) { int rc = forb_trig_ensure(c); if (rc) return rc; }
@@ -2080,7 +2068,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   const StepForm F = step_form(c);                          // one form for every step of this map, captured or eager, and for its counters
   const bool use_graph = c->use_graph && c->nsteps > 2 && !F.hostcheck;
   const bool per_step = use_graph && step_budgets_ready(c, adjoint);
-  c->last_map_per_step = per_step; c->last_map_kind = adjoint;
+  c->lb.last_per_step = per_step; c->lb.last_kind = adjoint;
   std::vector<hipGraphExec_t> plan;
   if (per_step) {                                           // every graph of the plan exists before the first launch (captures end the stream's queue)
     // bound the cache of captured steps here, where no plan holds a handle of it (never seen: a few dozen budget pairs occur);
@@ -2092,7 +2080,7 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
     }
     plan.resize(c->nsteps);
     for (int istep = 1; istep <= c->nsteps; ++istep) {
-      const nsk_ctx::StepBudgets& b = c->sb[adjoint];
+      const LaunchBudgets::StepBudgets& b = c->lb.sb[adjoint];
       int rc = graph_for(c, F, adjoint, step_class(istep), b.bh[istep - 1], b.bp[istep - 1], &plan[istep - 1]);
       if (rc) return rc;
       c->sb_launch_h += b.bh[istep - 1]; c->sb_launch_p += b.bp[istep - 1];
@@ -2102,18 +2090,10 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   } else if (use_graph)
     for (int k = 0; k < NCLS; ++k) { int rc = ensure_graph(c, F, k, adjoint); if (rc) return rc; }
   const int gsteps = (use_graph && !per_step && c->graph_steps > 1 && c->nsteps >= CLS_ISTEP[NCLS - 1] + 2 * c->graph_steps) ? c->graph_steps : 1;
-  if (gsteps > 1) { int rc = ensure_graph_multi(c, F, adjoint); if (rc) return rc; }
-  { int rc = state_load(c, q); if (rc) return rc; }
-  if (d.bf_stride || d.forb) {
-    if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
-    HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
-  }
+  if (gsteps > 1) { int rc = ensure_graph(c, F, NCLS, adjoint); if (rc) return rc; }
+  { int rc = map_begin(c, q, adjoint); if (rc) return rc; }
   std::vector<nsk_ctx*> G1(1, c);
-  if (c->bcv.on) {                                            // BoostConv map: the reference's call at istep = 0 (lag = 0) opens a run
-    int rc = bcv_begin_attempt(c);
-    if (!rc && c->bcv.step0 == 0) rc = bcv_call(G1, nullptr, false);
-    if (rc) return rc;
-  }
+  { int rc = bcv_open(G1); if (rc) return rc; }
   if (F.absorb) { c->up_host = true; c->absorb_maps++; }
   if (F.convfuse) c->convfuse_steps += c->nsteps;
   if (F.helmpack) c->helmpack_steps += c->nsteps;
@@ -2157,99 +2137,17 @@ static int run_map(nsk_ctx* c, int adjoint, double* f, const double* q) {
   return 0;
 }
 
-// Launch budgets of the step classes from the iteration maxima of the maps run so far.  The maxima of one
-// class move by +-3 between consecutive Krylov vectors; budgets that follow the last map alone are cut after a
-// cheap map, the next map runs out of launches and is redone as a whole (measured on cfg 2: 29 redone maps and
-// 449 graph re-captures in 130 maps).  So: a window of the last BW maps; grow at once; shrink to the window
-// maximum + head-room only when the window is full, or when the budget is more than twice what the window asks
-// for (start-up budgets, doubled budgets after a redone map).
-constexpr int BW = 8;
-static int bhead() { static const int v = std::getenv("NSK_BHEAD") ? std::max(0, std::atoi(std::getenv("NSK_BHEAD"))) : 3; return v; }      // head-room above the window maximum (A/B switch)
+// The launch budgets behind a map attempt that stands (nsk_budgets_host.hpp has the rules): the class budgets from the attempt's
+// counters, and on single-rank contexts the per-step budgets from its per-step record.  The head-rooms' A/B switches are read here.
+static int env_int(const char* name, int dflt) { const char* g = std::getenv(name); return g ? std::atoi(g) : dflt; }
 static void budgets_update(nsk_ctx* c, const Stats& h) {
-  if (c->budget_freeze) return;                         // measurement switch (scripts/noop_cost.py): budgets stay where the caller put them
-  const int slot = c->bh_n % BW;
-  for (int k = 0; k < NCLS; ++k) { c->bh_helm[k][slot] = (int)h.max_helm_k[k]; c->bh_pres[k][slot] = (int)h.max_pres_k[k]; }
-  c->bh_n++;
-  const int nv = std::min(c->bh_n, BW);
-  for (int k = 0; k < NCLS; ++k) {
-    if (CLS_ISTEP[k] > c->nsteps) break;
-    int mh = 0, mp = 0;
-    for (int i = 0; i < nv; ++i) { mh = std::max(mh, c->bh_helm[k][i]); mp = std::max(mp, c->bh_pres[k][i]); }
-    // the classes of time steps 1..6 hold one to three steps per map and their counts vary most (pressure
-    // solves of steps 2-3: 4 to 23 iterations): spare launches there cost microseconds, a redone map 0.1 s
-    const int xh = k <= 3 ? std::max(4, mh / 2) : (k == 4 ? 1 : 0), xp = k <= 3 ? std::max(4, mp) : (k == 4 ? 1 : 0);
-    // the first maps of a run differ most from one another (noise seed, empty projection space): wider margin
-    const int sh = nv < 4 ? std::max(2, mh / 4) : 0, sp = nv < 4 ? std::max(4, mp) : 0;
-    const int th = std::min(c->max_helm, mh + bhead() + xh + sh), tp = std::min(c->max_pres, mp + bhead() + xp + sp);
-    // before the window is full only the long classes are cut (their spare launches are what costs); the classes of
-    // steps 1-6 keep what they have: the second Krylov vector of a run can need 34 pressure iterations where the
-    // noise seed needed 4
-    const bool early = nv < BW && k >= 4;
-    if (!c->fused && (th > c->cur_helm[k] || (nv == BW ? th < c->cur_helm[k] - 1 : (early && c->cur_helm[k] > 2 * th)))) c->cur_helm[k] = th;   // fused: the solve ends on the device
-    if (tp > c->cur_pres[k] || (nv == BW ? tp < c->cur_pres[k] - 1 : (early && c->cur_pres[k] > 2 * tp))) c->cur_pres[k] = tp;
-  }
+  static const int bhead = std::max(0, env_int("NSK_BHEAD", 3));
+  c->lb.update_class(h.max_helm_k, h.max_pres_k, c->nsteps, c->fused != 0, bhead);
 }
-
-// Per-step budgets of the NEXT map from the per-step iteration counts of the last SBW maps (see nsk_ctx::step_budgets).
-// Helmholtz: launches = largest count at steps s-SBN..s+SBN + 3 (a solve that took I iterations needs I + 1 launches: 2 spare);
-// pressure: + 2.  Steps 1-6 and the first maps of a run vary most (the class budgets' rule): wider margins there.
 static void step_budgets_update(nsk_ctx* c) {
-  const int ns = c->step_rec_n, kind = c->last_map_kind;
-  if (kind < 0 || kind > 1) return;
-  nsk_ctx::StepBudgets& b = c->sb[kind];
-  if (!c->step_budgets || !c->h_step_iters || ns != c->nsteps || ns < 3) { b.bh.clear(); b.bp.clear(); return; }
-  if (b.n > 0 && (int)b.hist_h[0].size() != ns) b.n = 0;                     // (nsteps changed under us: start again)
-  const int slot = b.n % nsk_ctx::SBW;
-  b.hist_h[slot].resize(ns); b.hist_p[slot].resize(ns);
-  for (int s = 0; s < ns; ++s) { b.hist_h[slot][s] = c->h_step_iters[2 * s]; b.hist_p[slot][s] = c->h_step_iters[2 * s + 1]; }
-  b.n++;
-  const int nv = std::min(b.n, nsk_ctx::SBW);
-  b.bh.assign(ns, 0); b.bp.assign(ns, 0);
-  // (tail = 2: the budgets below + a persistent tail behind them as a SAFETY NET: a solve that outruns its budget continues
-  //  in the tail instead of costing a redone map)
-  const bool net = step_form(c).tails;
-  static const int env_h = std::getenv("NSK_SB_HEAD_H") ? std::atoi(std::getenv("NSK_SB_HEAD_H")) : -1;
-  static const int env_p = std::getenv("NSK_SB_HEAD_P") ? std::atoi(std::getenv("NSK_SB_HEAD_P")) : -1;
-  // (options "tail_off_h" / "tail_off_p" > 0 add to the head-room of the plain budgets too: tests use it for a reference run that cannot overflow)
-  const int head_h = (env_h >= 0 ? env_h : (net ? 1 : 3)) + std::max(0, c->tail_off_h), head_p = (env_p >= 0 ? env_p : (net ? 0 : 2)) + std::max(0, c->tail_off_p);
-  if (net && c->tail == 1) {
-    // HEADS for the persistent tails: the MEDIAN count of this step over the window (offline on 56 maps of config 2: the cheapest
-    // predictor, 0.44 launches that find nothing to do and 0.56 tail iterations per pressure solve; profiles/r05_step_budgets.txt).
-    // Velocity: a solve of I iterations is found finished by launch I (0-based), i.e. I + 1 launches.
-    const int off_h = c->tail_off_h, off_p = c->tail_off_p;
-    int vh[nsk_ctx::SBW], vp[nsk_ctx::SBW];
-    for (int s = 0; s < ns; ++s) {
-      for (int i = 0; i < nv; ++i) { vh[i] = b.hist_h[i][s]; vp[i] = b.hist_p[i][s]; }
-      std::sort(vh, vh + nv); std::sort(vp, vp + nv);
-      const int mh = vh[nv / 2], mp = vp[nv / 2];
-      b.bh[s] = std::max(1, std::min(c->max_helm - 1, mh + 1 + off_h));
-      b.bp[s] = std::max(0, std::min(c->max_pres, mp + off_p));
-    }
-    return;
-  }
-  // (option "sb_pct" < 100, with the safety-net tail only: the budget is that PERCENTILE of the counts at steps s-1..s+1 of the window
-  //  instead of the largest at s-2..s+2 -- fewer launches that find nothing to do, more solves that end in the tail; offline on the
-  //  recorded counts of 64 maps the 85th-90th percentile is the cheapest: DESIGN.md section 7)
-  const int pct = (net && nv >= 4) ? std::max(50, std::min(100, c->sb_pct)) : 100;
-  const int win = pct < 100 ? 1 : nsk_ctx::SBN;
-  for (int s = 0; s < ns; ++s) {
-    int mh = 0, mp = 0;
-    if (pct < 100) {
-      int vh[nsk_ctx::SBW * 3], vp[nsk_ctx::SBW * 3], n = 0;
-      for (int i = 0; i < nv; ++i)
-        for (int t = std::max(0, s - win); t <= std::min(ns - 1, s + win); ++t) { vh[n] = b.hist_h[i][t]; vp[n] = b.hist_p[i][t]; ++n; }
-      std::sort(vh, vh + n); std::sort(vp, vp + n);
-      const int k = std::min(n - 1, (int)std::ceil(0.01 * pct * (n - 1)));
-      mh = vh[k]; mp = vp[k];
-    } else
-    for (int i = 0; i < nv; ++i)
-      for (int t = std::max(0, s - nsk_ctx::SBN); t <= std::min(ns - 1, s + nsk_ctx::SBN); ++t) { mh = std::max(mh, b.hist_h[i][t]); mp = std::max(mp, b.hist_p[i][t]); }
-    int xh = 0, xp = 0;
-    if (s < 6) { xh = std::max(4, mh / 2); xp = std::max(4, mp); }                    // time steps 1-6: counts vary most (noise left by the input vector)
-    if (nv < 4 && !net) { xh += std::max(2, mh / 4); xp += std::max(3, mp / 2); }    // first maps of a run: noise seed, empty projection space (with the safety-net tail an early overflow costs a tail iteration, not a map)
-    b.bh[s] = std::min(c->max_helm, mh + head_h + xh);
-    b.bp[s] = std::min(c->max_pres, std::max(c->min_pres, mp) + head_p + xp);
-  }
+  static const int env_h = env_int("NSK_SB_HEAD_H", -1), env_p = env_int("NSK_SB_HEAD_P", -1);
+  c->lb.update_steps(c->lb.last_kind, c->step_budgets ? c->h_step_iters : nullptr, c->step_rec_n, c->nsteps, step_form(c).tails, c->tail,
+                     c->tail_off_h, c->tail_off_p, c->sb_pct, env_h, env_p);
 }
 
 // run one map with the adaptive launch budgets: every inner solve early-exits on its
@@ -2286,11 +2184,18 @@ static int ensure_step_record(nsk_ctx* c) {
   return 0;
 }
 
+// the facts LaunchBudgets::verdict judges an attempt by: the device counters, and how the attempt ran
+static MapFacts map_facts(const nsk_ctx* c, const Stats& h, bool per_step, bool hostchecked) {
+  MapFacts m;
+  m.unconverged = h.unconverged; m.nonfinite = h.nonfinite; m.allred_mismatch = h.allred_mismatch; m.sync_timeouts = h.sync_timeouts;
+  m.per_step = per_step; m.hostchecked = hostchecked; m.nsteps = c->nsteps; m.fused = c->fused != 0; m.tail = c->tail;
+  return m;
+}
+
 static int map_launch(nsk_ctx* c, int adjoint, double* f, const double* src) {
   if (c->state_dirty) { int rc0 = reset_solver_state(c); if (rc0) return rc0; }
   { int rc0 = ensure_step_record(c); if (rc0) return rc0; }
   const int nrec = std::min(c->nsteps, nsk_ctx::STEP_CAP);
-  HIPCHK(hipMemsetAsync(c->d.stats, 0, sizeof(Stats), c->stream));
   HIPCHK(hipMemsetAsync(c->d.stepctr, 0, sizeof(int), c->stream));
   HIPCHK(hipMemsetAsync(c->d.step_iters, 0, (size_t)2 * nrec * sizeof(int), c->stream));
   int rc = run_map(c, adjoint, f, src);
@@ -2315,13 +2220,20 @@ static int map_finish(nsk_ctx* c) {
   }
   if (c->debug >= 2) {
     fprintf(stderr, "map: unconverged %llu | helm max/budget", (unsigned long long)h.unconverged);
-    for (int k = 0; k < NCLS; ++k) fprintf(stderr, " %llu/%d", (unsigned long long)h.max_helm_k[k], c->cur_helm[k]);
+    for (int k = 0; k < NCLS; ++k) fprintf(stderr, " %llu/%d", (unsigned long long)h.max_helm_k[k], c->lb.cur_helm[k]);
     fprintf(stderr, " | pres max/budget");
-    for (int k = 0; k < NCLS; ++k) fprintf(stderr, " %llu/%d", (unsigned long long)h.max_pres_k[k], c->cur_pres[k]);
+    for (int k = 0; k < NCLS; ++k) fprintf(stderr, " %llu/%d", (unsigned long long)h.max_pres_k[k], c->lb.cur_pres[k]);
     fprintf(stderr, "\n");
   }
-  if (h.sync_timeouts) {
-    if (!c->fused && c->tail != 0 && c->last_map_per_step) {
+  const bool hcm = step_form(c).hostcheck;     // host-checked eager steps iterate to the caps whatever the budgets say
+  switch (c->lb.verdict(map_facts(c, h, c->lb.last_per_step, hcm))) {
+    case Verdict::STANDS:
+      if (c->nsteps > 2 && !hcm) { budgets_update(c, h); step_budgets_update(c); }
+      return 0;
+    case Verdict::REDO:
+      c->retries++;
+      return 1;
+    case Verdict::TAILS_OFF_REDO:
       // a grid barrier of a persistent tail gave up (its workgroups were not all resident: another process on the device, fewer
       // CUs than the occupancy query promised): this context goes back to launch budgets for good and the map is redone
       fprintf(stderr, "libnekstab_hip: a grid barrier of the persistent tails timed out (%lld): tails off for this context, map redone on launch budgets\n", (long long)h.sync_timeouts);
@@ -2330,37 +2242,18 @@ static int map_finish(nsk_ctx* c) {
       (void)reset_solver_state(c);
       c->retries++;
       return 1;
-    }
-    return fail(NSK_EHIP, "grid barrier of the persistent velocity solve timed out (workgroups not co-resident?): set option fused = 0");
+    case Verdict::FAIL_SYNC:
+      return fail(NSK_EHIP, "grid barrier of the persistent velocity solve timed out (workgroups not co-resident?): set option fused = 0");
+    case Verdict::FAIL_NAN:               // the MAP says so (the reference's only guard is the NaN check of the next inner product, core/krylov_subspace.f:52-55)
+      (void)reset_solver_state(c);        // ... and the next map of this context starts clean
+      return fail(NSK_ENAN, "non-finite state inside the map: " + std::to_string((long long)h.nonfinite) + " time steps with a NaN / Inf pressure right-hand side (input vector not finite?)");
+    case Verdict::FAIL_COMM:              // (one rank: no all-reduce is verified)
+      return fail(NSK_ECOMM, "all-reduce mismatch on a single-rank context");
+    case Verdict::FAIL_NOCONV:
+      c->hstats.unconverged += h.unconverged;
+      return fail(NSK_ENOCONV, "inner solve hit its iteration cap (" + std::to_string(h.unconverged) + " solves)");
   }
-  if (h.nonfinite) {                    // the MAP says so (the reference's only guard is the NaN check of the next inner product, core/krylov_subspace.f:52-55)
-    (void)reset_solver_state(c);        // ... and the next map of this context starts clean
-    return fail(NSK_ENAN, "non-finite state inside the map: " + std::to_string((long long)h.nonfinite) + " time steps with a NaN / Inf pressure right-hand side (input vector not finite?)");
-  }
-  const bool hcm = step_form(c).hostcheck;     // host-checked eager steps iterate to the caps whatever the budgets say
-  if (h.unconverged == 0) {
-    if (c->nsteps > 2 && !hcm) { budgets_update(c, h); step_budgets_update(c); }
-    c->sb_force_class = false;
-    return 0;
-  }
-  if (c->last_map_per_step) {           // a per-step budget overflowed: the redo runs on the class budgets as they stand (they cover the class maxima of the last maps)
-    c->sb_force_class = true;
-    c->retries++;
-    return 1;
-  }
-  bool capped = true;
-  for (int k = 0; k < NCLS; ++k) capped = capped && c->cur_helm[k] >= c->max_helm && c->cur_pres[k] >= c->max_pres;
-  if (hcm) capped = true;               // ... so an unconverged solve there IS capped: redoing the map with doubled budgets the mode ignores would repeat it (as group_run_map)
-  if (capped) {
-    c->hstats.unconverged += h.unconverged;
-    return fail(NSK_ENOCONV, "inner solve hit its iteration cap (" + std::to_string(h.unconverged) + " solves)");
-  }
-  c->retries++;
-  for (int k = 0; k < NCLS; ++k) {
-    c->cur_helm[k] = std::min(c->max_helm, 2 * c->cur_helm[k] + 4);
-    c->cur_pres[k] = std::min(c->max_pres, 2 * c->cur_pres[k] + 4);
-  }
-  return 1;
+  return fail(NSK_EINVAL, "map_finish: unknown verdict");
 }
 
 // run one map with the adaptive launch budgets: every inner solve early-exits on its
@@ -2803,8 +2696,7 @@ int nsk_set_tolerances(nsk_ctx* c, double th, double tp, int relative) {
   if (!c) return fail(NSK_EINVAL, "null ctx");
   c->d.tol_helm = th; c->d.tol_pres = tp; c->d.tol_relative = relative;
   invalidate_graphs(c);   // Dev is captured by value: re-capture
-  for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
-  c->bh_n = 0;
+  c->lb.reset_to_caps(true);
   return 0;
 }
 
@@ -2861,7 +2753,7 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
   else if (n == "fuse2_start") { c->fuse2_start = (int)value; invalidate_graphs(c); }
   else if (n == "sb_pct") { c->sb_pct = (int)value; }
   else if (n == "skip_close") { c->skip_close = (int)value; invalidate_graphs(c); }
-  else if (n == "min_pres_iter") c->min_pres = (int)value;
+  else if (n == "min_pres_iter") c->lb.min_pres = (int)value;
   else if (n == "pres_cap") {
     if (value > 0 && c->ndim != 2) return fail(NSK_EINVAL, "pres_cap is validated on quadrilateral linearised maps only (DESIGN.md section 1)");
     c->pres_cap = (int)value;
@@ -2905,18 +2797,18 @@ int nsk_set_option(nsk_ctx* c, const char* name, double value) {
     if (value != 0 && c->cm) return fail(NSK_EINVAL, "fused: the persistent velocity solve (k_helm_fused) has no component-mask form (context of nsk_init_masks)");
     if (value != 0 && !fused_possible(c)) return fail(NSK_EINVAL, "persistent velocity solve not available for this context (needs a quadrilateral single-rank context whose workgroups are all resident)");
     c->fused = value != 0;
-    for (int k = 0; k < NCLS; ++k) c->cur_helm[k] = c->max_helm;
+    c->lb.set_all(false, false, c->lb.max_helm);          // (no velocity budget: the solve ends on the device)
   }
   else if (n == "early_pres_mul") c->early_pres_mul = value;
   else if (n == "proj_reset") c->d.proj_reset = (int)value;
   else if (n == "proj_restart") c->d.proj_restart = (int)value;
   else if (n == "pres_floor") c->d.tol_pres_floor = value;
   else if (n == "dbg") { int v = (int)value; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_dbg), &v, sizeof(int))); }
-  else if (n == "budget_helm") { for (int k = 0; k < NCLS; ++k) c->cur_helm[k] = std::min(c->max_helm, std::max(1, (int)value)); }
-  else if (n == "budget_pres") { for (int k = 0; k < NCLS; ++k) c->cur_pres[k] = std::min(c->max_pres, std::max(1, (int)value)); }
-  else if (n == "budget_add_helm") { for (int k = 0; k < NCLS; ++k) c->cur_helm[k] = std::min(c->max_helm, std::max(1, c->cur_helm[k] + (int)value)); }
-  else if (n == "budget_add_pres") { for (int k = 0; k < NCLS; ++k) c->cur_pres[k] = std::min(c->max_pres, std::max(1, c->cur_pres[k] + (int)value)); }
-  else if (n == "budget_freeze") c->budget_freeze = (int)value;
+  else if (n == "budget_helm") c->lb.set_all(false, false, (int)value);
+  else if (n == "budget_pres") c->lb.set_all(true, false, (int)value);
+  else if (n == "budget_add_helm") c->lb.set_all(false, true, (int)value);
+  else if (n == "budget_add_pres") c->lb.set_all(true, true, (int)value);
+  else if (n == "budget_freeze") c->lb.freeze = (int)value;
   else if (n == "step_budgets") c->step_budgets = (int)value;
   else if (n == "tail") c->tail = (int)value;
   else if (n == "tail_off_h") c->tail_off_h = (int)value;
@@ -3015,7 +2907,7 @@ int nsk_get_stats(nsk_ctx* c, nsk_stats* s) {
   s->steps = h.steps; s->helm_iters = h.helm_iters; s->pres_iters = h.pres_iters;
   s->unconverged = h.unconverged; s->last_helm_res = h.last_helm_res; s->last_pres_res = h.last_pres_res;
   s->max_helm_iter = h.max_helm; s->max_pres_iter = h.max_pres;
-  s->budget_helm = c->cur_helm[5]; s->budget_pres = c->cur_pres[5];
+  s->budget_helm = c->lb.cur_helm[5]; s->budget_pres = c->lb.cur_pres[5];
   s->recaptures = c->recaptures; s->retries = c->retries;
   s->capped_solves = h.capped_solves; s->worst_cap_ratio = h.worst_cap_ratio;
   s->total_capped_solves = c->tot_capped; s->total_worst_cap_ratio = c->tot_worst_cap;
@@ -3157,7 +3049,7 @@ static int set_baseflow_body(std::vector<nsk_ctx*>& G, bool sharded, const doubl
     if (!sharded) { const int rc = scan_bfmask(c); if (rc) return rc; }
     invalidate_graphs(c);                                  // coefficients are baked into the captured graphs
     // shards start again from the full launch budgets; a full-mesh context keeps its own: Newton sets a base flow every iteration
-    if (sharded) { for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; } c->bh_n = 0; }
+    if (sharded) c->lb.reset_to_caps(true);
   }
   return 0;
 }
@@ -3345,8 +3237,7 @@ static int orbit_integrate(std::vector<nsk_ctx*>& G, bool sharded, const double*
     d.spng_vr = vr; d.nl_spng_str = spng_str;
     if (!d.bstep && (rc = dalloc(c, &d.bstep, 4))) return rc;
     invalidate_graphs(c);
-    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
-    c->bh_n = 0;
+    c->lb.reset_to_caps(true);
     HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
     if ((rc = state_load(c, q0[r]))) return rc;
   }
@@ -4180,13 +4071,13 @@ static int sfd_map(std::vector<nsk_ctx*>& G, const char* who, bool group, nsk_ve
     c->sfd.on = true; c->sfd.q0 = (const double*)qbar[r]; c->sfd.qw = (double*)f[r]; c->sfd.chi = chi; c->sfd.omega_c = omega_c;
     // an SFD map that outran the budgets was redone with doubled ones: the SFD maps that follow start from those (a run is a
     // chain of hundreds of maps), the unforced maps get theirs back below
-    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = std::max(c->cur_helm[k], c->sfd_helm[k]); c->cur_pres[k] = std::max(c->cur_pres[k], c->sfd_pres[k]); }
+    c->lb.at_least(c->sfd_budgets);
   }
   if (group) rc = group_run_map(G, 2, (double* const*)f, (const double* const*)q);
   else { G[0]->hstats = Stats{}; rc = run_map_adaptive(G[0], 2, (double*)f[0], (const double*)q[0]); }
   for (nsk_ctx* c : G) {
     c->sfd = nsk_ctx::SfdRun{};
-    for (int k = 0; k < NCLS; ++k) { c->sfd_helm[k] = c->cur_helm[k]; c->sfd_pres[k] = c->cur_pres[k]; }
+    c->sfd_budgets = c->lb.save();
   }
   eager.restore();
   if (rc) return rc;
@@ -4294,7 +4185,7 @@ static int bcv_map(std::vector<nsk_ctx*>& G, const char* who, bool group, nsk_ve
     c->bcv = nsk_ctx::BcvRun{};
     c->bcv.on = true; c->bcv.skip = skip; c->bcv.step0 = step0;
     c->bcv_count0 = c->bcv_count; c->bcv_rot0 = c->bcv_rot;
-    for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = std::max(c->cur_helm[k], c->bcv_helm[k]); c->cur_pres[k] = std::max(c->cur_pres[k], c->bcv_pres[k]); }
+    c->lb.at_least(c->bcv_budgets);
   }
   if (group) rc = group_run_map(G, 2, (double* const*)f, (const double* const*)q);
   else { G[0]->hstats = Stats{}; rc = run_map_adaptive(G[0], 2, (double*)f[0], (const double*)q[0]); }
@@ -4302,7 +4193,7 @@ static int bcv_map(std::vector<nsk_ctx*>& G, const char* who, bool group, nsk_ve
   for (nsk_ctx* c : G) {
     if (rc) (void)bcv_restore(c);
     c->bcv = nsk_ctx::BcvRun{};
-    for (int k = 0; k < NCLS; ++k) { c->bcv_helm[k] = c->cur_helm[k]; c->bcv_pres[k] = c->cur_pres[k]; }
+    c->bcv_budgets = c->lb.save();
   }
   eager.restore();
   if (rc) return rc;
@@ -4444,7 +4335,7 @@ int nsk_clone(nsk_ctx* P, nsk_ctx** out) {
   c->nel = P->nel; c->nblk = P->nblk; c->nvert = P->nvert; c->nloc = P->nloc; c->npr = P->npr; c->nstate = P->nstate; c->nscal = 0;
   if (P->nscal) { delete c; return fail(NSK_EINVAL, "nsk_clone: not with scalar fields"); }
   c->dt = P->dt; c->re = P->re; c->endtime = P->endtime; c->nsteps = P->nsteps;
-  c->max_helm = P->max_helm; c->max_pres = P->max_pres; c->min_pres = P->min_pres; c->pres_cap = P->pres_cap; c->layers = P->layers;
+  c->lb.max_helm = P->lb.max_helm; c->lb.max_pres = P->lb.max_pres; c->lb.min_pres = P->lb.min_pres; c->pres_cap = P->pres_cap; c->layers = P->layers;
   c->use_graph = P->use_graph; c->gmres_cycle = P->gmres_cycle; c->helm_guess = P->helm_guess; c->early_pres_mul = P->early_pres_mul;
   c->merged_iters = P->merged_iters; c->merged_update = P->merged_update; c->gs2_from = P->gs2_from; c->gs_lag = P->gs_lag; c->debug = P->debug;
   c->dbg_max_order = P->dbg_max_order; c->dbg_ab2 = P->dbg_ab2; c->dbg_pext = P->dbg_pext;
@@ -4455,7 +4346,7 @@ int nsk_clone(nsk_ctx* P, nsk_ctx** out) {
   // lanes run their maps on launch budgets only
   if (P->tail != 0) { P->tail = 0; invalidate_graphs(P); }
   c->tail = 0;
-  for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
+  c->lb.reset_to_caps(false);
   if (hipStreamCreate(&c->stream) != hipSuccess) { delete c; return fail(NSK_EHIP, "hipStreamCreate"); }
   Dev& d = c->d;
   d = P->d;                                               // every immutable pointer: geometry, bases, gather tables, preconditioner
@@ -4809,7 +4700,7 @@ int nsk_test_op3(nsk_ctx* c, int which, const double* in, double* out, int a, in
     const StepCoef sc = make_coef(c, a, 0);
     const StepForm F = step_form(c);
     DISPATCH_N(c->key, {
-      for (int it = 0; it < c->max_helm; ++it) {
+      for (int it = 0; it < c->lb.max_helm; ++it) {
         launch_helm_iter<N>(c, F, d, sc, it, (const double*)d.rloc);
         tot_rows(c, d.hpart + (size_t)(it & 1) * c->hrows * c->nblk, c->hrows, d.htot + (it & 1) * c->hstride);
       }
@@ -4859,7 +4750,7 @@ int nsk_test_helm_solve(nsk_ctx* c, const double* rx, const double* ry, int orde
   HIPCHK(hipMemcpy(d.bloc, d.rloc, 2 * d.cs * sizeof(double), hipMemcpyDeviceToDevice));
   HIPCHK(hipMemset(d.stats, 0, sizeof(Stats)));
   const StepCoef sc = make_coef(c, order, 0);
-  const int nh = c->max_helm;
+  const int nh = c->lb.max_helm;
   DISPATCH_N(c->key, {
     for (int it = 0; it < nh; ++it) {
       hipLaunchKernelGGL(k_helm<N>, dim3(c->nblk), dim3(Cfg<N>::NT), 0, c->stream, d, sc, it, (const double*)d.rloc);
@@ -4885,7 +4776,7 @@ int nsk_test_pres_solve(nsk_ctx* c, const double* g, double* out, int* iters) {
   HIPCHK(hipMemcpy(d.gpart, part.data(), c->nblk * sizeof(double), hipMemcpyHostToDevice));
   StepCoef sc = make_coef(c, 3, 0);
   const int savep = d.nproj_max; d.nproj_max = 0; c->in_test = 1;
-  int rc = pres_solve_launch(c, step_form(c), 1.0, 3, c->max_pres);
+  int rc = pres_solve_launch(c, step_form(c), 1.0, 3, c->lb.max_pres);
   c->in_test = 0;
   if (rc) return rc;
   sc.h2 = 1.0;

@@ -1056,7 +1056,7 @@ static int build3(nsk_ctx* c, const nsk_case& cs) {
     } else if ((rc = coarse_build3(c, rows, cs.has_outflow != 0))) return rc;
   }
   tick("coarse operator probed + coarse solve built");
-  for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
+  c->lb.reset_to_caps(false);
   d.proj_reset = 1;       // hexahedra: a map that starts from the previous map's projection space needs 15-20 % more Helmholtz iterations (DESIGN section 8)
   env_overrides(c);
   if (c->cm) {

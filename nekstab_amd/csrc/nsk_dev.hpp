@@ -3,6 +3,7 @@
 // pressure (Gauss) node = e*M*M + b*M + a, dealiasing node = e*ND*ND + b*ND + a.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "nsk_budgets_host.hpp"
 
 namespace nsk {
 
@@ -57,13 +58,7 @@ struct GmresScal {               // device-resident small state of one pressure 
   int up_np, up_s, up_restart;   // vectors before the update, slot written, restart on the total solution
 };
 
-// Step classes: one captured hipGraph and one launch budget each.  Time steps 1, 2, 3 differ in BDF/EXT order and
-// in how much of the input's divergence they remove; steps 4-6 and 7-16 still carry that transient.  Cutting the
-// tail (>= 17) further does not pay: its per-class iteration maxima are the same (measured with 8 classes).
-constexpr int NCLS = 6;
-__host__ __device__ inline int step_class(int istep) {
-  return istep <= 3 ? istep - 1 : (istep <= 6 ? 3 : (istep <= 16 ? 4 : 5));
-}
+// (NCLS, CLS_ISTEP and step_class: nsk_budgets_host.hpp, with the launch budgets that go by them)
 
 struct Stats {
   long long helm_iters, pres_iters, unconverged, steps;

@@ -91,7 +91,7 @@ static int shard_fill(nsk_ctx* c, nsk_ctx* P, const int* part, int rank, int nra
   c->ndim = P->ndim; c->key = P->key;
   // (Dev::use_tot is cleared below: shards take the all-reduced totals path)
   c->dt = P->dt; c->re = P->re; c->endtime = P->endtime; c->nsteps = P->nsteps;
-  c->max_helm = P->max_helm; c->max_pres = P->max_pres; c->min_pres = P->min_pres; c->layers = P->layers;
+  c->lb.max_helm = P->lb.max_helm; c->lb.max_pres = P->lb.max_pres; c->lb.min_pres = P->lb.min_pres; c->layers = P->layers;
   c->helm_guess = P->helm_guess; c->early_pres_mul = P->early_pres_mul; c->use_graph = P->use_graph; c->PS = PS; c->coarse_lda = P->coarse_lda;
   c->coarse_iter = P->coarse_iter; c->cA_width = P->cA_width; c->cheb_deg = P->cheb_deg; c->cheb_theta = P->cheb_theta; c->cheb_delta = P->cheb_delta;
   c->cA_rp = P->cA_rp; c->cA_ci = P->cA_ci; c->cA_va = P->cA_va; c->cA_dinv = P->cA_dinv;      // replicated coarse operator (shared)
@@ -99,7 +99,7 @@ static int shard_fill(nsk_ctx* c, nsk_ctx* P, const int* part, int rank, int nra
   c->circ_Binv = P->circ_Binv; c->circ_F = P->circ_F; c->circ_cols = P->circ_cols; c->circ_rh = P->circ_rh; c->circ_xh = P->circ_xh;
   c->cw_d0 = P->cw_d0; c->cw_d1 = P->cw_d1; c->cw_r = P->cw_r;                                    // work vectors: ranks of one process run in stream order
   c->stream = P->stream;                                   // virtual ranks share the parent's stream
-  for (int k = 0; k < NCLS; ++k) { c->cur_helm[k] = c->max_helm; c->cur_pres[k] = c->max_pres; }
+  c->lb.reset_to_caps(false);
   // local element order: BOUNDARY elements (a node of theirs is shared with another rank) first, interior elements behind, each
   // group in ascending global id -- so that the workgroups whose results travel in the halo are the first ones of a launch
   // (halo / interior overlap of the velocity solve, group_step)
@@ -556,8 +556,8 @@ static int group_step(std::vector<nsk_ctx*>& G, int istep, int adjoint) {
   const StepCoef sc = make_coef(c0, istep, adjoint);
   const bool hc = group_hostcheck(G) && !stream_capturing(c0->stream);
   // host-checked: iterate until the device flags say converged (up to the caps); otherwise the launch budgets of the step class
-  int nh = hc ? c0->max_helm : c0->cur_helm[sc.cls];
-  const int np = hc ? c0->max_pres : c0->cur_pres[sc.cls];                              // beyond gmres_cycle iterations: restarted cycles
+  int nh = hc ? c0->lb.max_helm : c0->lb.cur_helm[sc.cls];
+  const int np = hc ? c0->lb.max_pres : c0->lb.cur_pres[sc.cls];                              // beyond gmres_cycle iterations: restarted cycles
   const double scale = 1.0 / (sc.h2 * std::sqrt(c0->d.vol));
   const int nd = c0->ndim, hrows = c0->hrows, hstride = c0->hstride;
   const bool proj = c0->d.nproj_max > 0, singular = !c0->d.has_outflow;
@@ -634,7 +634,7 @@ static int group_step(std::vector<nsk_ctx*>& G, int istep, int adjoint) {
       if ((rc = totals(&Dev::gpart, 0, 1, &Dev::gtot, 0))) return rc;
     }
     const double emul = istep <= 3 ? c0->early_pres_mul : 1.0;      // same early-step tolerance as the single-rank driver
-    FORALL { Dev de = c->d; de.tol_pres = early_tol(de, emul); hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, de, -1, scale, c->min_pres, sc.cls); }
+    FORALL { Dev de = c->d; de.tol_pres = early_tol(de, emul); hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, de, -1, scale, c->lb.min_pres, sc.cls); }
     bool pres_done0 = false;
     if (hc && c0->hc_pres[sc.cls] <= 1) {                   // the last solve of this class needed (almost) nothing: the projection may have solved this one
       if ((rc = group_flags_done(G, 1, 0, &pres_done0))) return rc;
@@ -645,7 +645,7 @@ static int group_step(std::vector<nsk_ctx*>& G, int istep, int adjoint) {
       if (jt > 0 && j == 0) {                              // cycle full and not converged: restart on the residual (as pres_solve_launch)
         FORALL hipLaunchKernelGGL(k_gmres_restart, dim3(c->nblk), dim3(256), 0, c->stream, c->d, c->gmres_cycle);
         if ((rc = totals(&Dev::gpart, 0, 1, &Dev::gtot, 0))) return rc;
-        FORALL { Dev de = c->d; de.tol_pres = early_tol(de, emul); hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, de, -2, scale, c->min_pres, sc.cls); }
+        FORALL { Dev de = c->d; de.tol_pres = early_tol(de, emul); hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, de, -2, scale, c->lb.min_pres, sc.cls); }
       }
       if (ov) {
         // halo / interior overlap of the pressure iteration: the coarse restriction and its all-reduce first (the exchange stream
@@ -703,7 +703,7 @@ static int group_step(std::vector<nsk_ctx*>& G, int istep, int adjoint) {
         FORALL hipLaunchKernelGGL(k_gmres_reorth<N>, dim3(c->nblk), dim3(NT), 0, c->stream, c->d, j);
         if ((rc = totals(&Dev::gpart2, 0, j + 2, &Dev::gtot2, 0))) return rc;
       }
-      FORALL { Dev de = c->d; de.tol_pres = early_tol(de, emul); de.gs2 = two ? 1 : 0; hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, de, j, scale, c->min_pres, sc.cls); }
+      FORALL { Dev de = c->d; de.tol_pres = early_tol(de, emul); de.gs2 = two ? 1 : 0; hipLaunchKernelGGL(k_gmres_update<N>, dim3(c->nblk), dim3(NT), 0, c->stream, de, j, scale, c->lb.min_pres, sc.cls); }
       if (hc && jt + 1 < np && jt + 4 >= c0->hc_pres[sc.cls]) {          // (iteration counts of consecutive steps differ more than the velocity solve's: every iteration from three before the last count)
         bool done = false;
         if ((rc = group_flags_done(G, 1, 0, &done))) return rc;
@@ -736,24 +736,14 @@ static bool group_graph_ok(const std::vector<nsk_ctx*>& G) {
 static int group_ensure_graph(std::vector<nsk_ctx*>& G, int cls, int adjoint) {
   nsk_ctx* c = G[0];
   nsk_ctx::StepGraph& g = c->graphs[adjoint][cls];
-  if (g.exec && g.nh == c->cur_helm[cls] && g.np == c->cur_pres[cls] && c->graph_members == G) return 0;
-  const auto t_cap0 = std::chrono::steady_clock::now();
-  if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+  if (g.exec && g.nh == c->lb.cur_helm[cls] && g.np == c->lb.cur_pres[cls] && c->graph_members == G) return 0;
   if (c->graph_members != G) {                              // another set of ranks: every class is stale
     for (auto& a : c->graphs) for (auto& x : a) if (x.exec) { (void)hipGraphExecDestroy(x.exec); x.exec = nullptr; x.nh = -1; }
     c->graph_members = G;
   }
-  hipGraph_t graph = nullptr;
-  HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  int rc = group_step(G, CLS_ISTEP[cls], adjoint);
-  hipError_t e = hipStreamEndCapture(c->stream, &graph);
-  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-  if (e != hipSuccess) return fail(NSK_EHIP, std::string("hipStreamEndCapture (sharded step): ") + hipGetErrorString(e));
-  HIPCHK(hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
-  c->recaptures++;
-  HIPCHK(hipGraphDestroy(graph));
-  g.nh = c->cur_helm[cls]; g.np = c->cur_pres[cls];
-  c->recapture_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_cap0).count();
+  int rc = capture_exec(c, [&] { return group_step(G, CLS_ISTEP[cls], adjoint); }, &g.exec, " (sharded step)");
+  if (rc) return rc;
+  g.nh = c->lb.cur_helm[cls]; g.np = c->lb.cur_pres[cls];
   return 0;
 }
 
@@ -774,20 +764,8 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
   for (;;) {
     if (graph)
       for (int k = 0; k < NCLS; ++k) { int rc = group_ensure_graph(G, k, adjoint); if (rc) return rc; }
-    for (size_t r = 0; r < G.size(); ++r) {
-      nsk_ctx* c = G[r];
-      Dev& d = c->d;
-      HIPCHK(hipMemsetAsync(d.stats, 0, sizeof(Stats), c->stream));
-      { int rc = state_load(c, q[r]); if (rc) return rc; }
-      if (d.bf_stride || d.forb) {                           // time-periodic base flow: step counter of the stored orbit / row of the trig table
-        if (d.bf_stride && adjoint != 2 && c->nsteps > c->orbit_steps) return fail(NSK_EINVAL, "map longer than the stored base-flow orbit");
-        HIPCHK(hipMemsetAsync(d.bstep, 0, sizeof(int), c->stream));
-      }
-    }
-    if (G[0]->bcv.on) {                                      // BoostConv map (nsk_group_boostconv_map), as run_map
-      for (nsk_ctx* c : G) { int rc = bcv_begin_attempt(c); if (rc) return rc; }
-      if (G[0]->bcv.step0 == 0) { int rc = bcv_call(G, nullptr, false); if (rc) return rc; }
-    }
+    for (size_t r = 0; r < G.size(); ++r) { int rc = map_begin(G[r], q[r], adjoint); if (rc) return rc; }
+    { int rc = bcv_open(G); if (rc) return rc; }             // BoostConv map (nsk_group_boostconv_map), as run_map
     for (int istep = 1; istep <= G[0]->nsteps; ++istep) {
       if (graph) { HIPCHK(hipGraphLaunch(G[0]->graphs[adjoint][step_class(istep)].exec, G[0]->stream)); continue; }
       int rc = group_step(G, istep, adjoint);
@@ -809,39 +787,31 @@ static int group_run_map(std::vector<nsk_ctx*>& G, int adjoint, double* const* f
     Stats h;
     HIPCHK(hipMemcpyAsync(&h, G[0]->d.stats, sizeof(Stats), hipMemcpyDeviceToHost, G[0]->stream));
     HIPCHK(hipStreamSynchronize(G[0]->stream));
-    if (h.allred_mismatch) {            // (exact integer sums: every rank reaches this verdict together)
-      for (nsk_ctx* c : G) (void)reset_solver_state(c);
+    // The verdict (LaunchBudgets::verdict): the counters come from all-reduced sums, and the ranks of a group hold the same budgets:
+    // every rank reaches the same one (and grows its own budgets for a redo); host-checked steps iterate to the caps whatever
+    // the budgets say.  The error paths that reset the solver state or fail without booking leave hstats as it was.
+    const bool hcm = !graph && group_hostcheck(G);
+    Verdict v = Verdict::STANDS;
+    for (size_t r = G.size(); r-- > 0;) v = G[r]->lb.verdict(map_facts(G[r], h, false, hcm));      // (G[0]'s is the one that counts)
+    if (v == Verdict::FAIL_COMM || v == Verdict::FAIL_NAN) for (nsk_ctx* c : G) (void)reset_solver_state(c);
+    if (v == Verdict::FAIL_COMM)
       return fail(NSK_ECOMM, "the ranks received different results from " + std::to_string((long long)h.allred_mismatch) + " of the verified all-reduces: the collective is not "
                   "rank-deterministic, device-side convergence flags would diverge (sharded map refused)");
-    }
-    if (h.nonfinite) {                  // (the norms come from all-reduced totals: every rank sees the same flag and returns the same code)
-      for (nsk_ctx* c : G) (void)reset_solver_state(c);
+    if (v == Verdict::FAIL_NAN)
       return fail(NSK_ENAN, "non-finite state inside the sharded map: " + std::to_string((long long)h.nonfinite) + " time steps with a NaN / Inf pressure right-hand side");
-    }
-    bool grow = h.unconverged > 0;
-    bool capped = true;                 // budgets the map just ran with (as run_map_adaptive: test before growing)
-    for (int k = 0; k < NCLS; ++k) capped = capped && G[0]->cur_helm[k] >= G[0]->max_helm && G[0]->cur_pres[k] >= G[0]->max_pres;
-    // host-checked steps iterate to the caps whatever the budgets say: an unconverged solve there IS capped (redoing the map with
-    // doubled budgets the mode ignores would repeat it several times -- or for ever on maps shorter than the later step classes)
-    if (!graph && group_hostcheck(G)) capped = true;
-    if (grow && capped) {
-      for (nsk_ctx* c : G) { c->hstats = h; c->hstats.steps = c->nsteps; }
+    if (v == Verdict::FAIL_SYNC || v == Verdict::TAILS_OFF_REDO)      // (shards run no persistent tails)
+      return fail(NSK_EHIP, "grid barrier of the persistent velocity solve timed out (workgroups not co-resident?): set option fused = 0");
+    // Stats booking: a shard's hstats IS the last attempt's counters (a full-mesh context accumulates the attempts and maps of
+    // one nsk_matvec instead: map_finish)
+    for (nsk_ctx* c : G) { c->hstats = h; c->hstats.steps = c->nsteps; }
+    if (v == Verdict::FAIL_NOCONV)
       return fail(NSK_ENOCONV, "inner solve hit its iteration cap (sharded run): " + std::to_string(h.unconverged) + " solves, worst Helmholtz " +
                   std::to_string(h.max_helm) + " / pressure " + std::to_string(h.max_pres) + " iterations");
+    if (v == Verdict::STANDS) {
+      for (nsk_ctx* c : G) budgets_update(c, h);
+      break;
     }
-    for (nsk_ctx* c : G) {
-      if (grow) c->retries++;
-      c->hstats = h; c->hstats.steps = c->nsteps;
-      if (grow) {
-        for (int k = 0; k < NCLS; ++k) {
-          if (CLS_ISTEP[k] > c->nsteps) break;
-          c->cur_helm[k] = std::min(c->max_helm, 2 * c->cur_helm[k] + 4); c->cur_pres[k] = std::min(c->max_pres, 2 * c->cur_pres[k] + 4);
-        }
-      } else {
-        budgets_update(c, h);
-      }
-    }
-    if (!grow) break;
+    for (nsk_ctx* c : G) c->retries++;
   }
   for (size_t r = 0; r < G.size(); ++r) { int rc = state_store(G[r], f[r]); if (rc) return rc; }
   HIPCHK(hipStreamSynchronize(G[0]->stream));
